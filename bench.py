@@ -32,6 +32,9 @@ Prints ONE JSON line (rank 0): value = frames/s of the whole job, plus
                  `llvmpipe_container`: the reference itself (numpy FFT + its GLSL on Mesa llvmpipe), measured in the build container.
   export_host  — the same frames through a real export to /dev/null including the read-out to host memory (N = 1: pinned ring
                  + writer thread; N > 1: every rank over its own PCIe link into the shared-memory ring, "host" mode).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the frames its last timed step rendered as DIR/*.npy (dump_outputs()). The
+inputs are synthetic and seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -81,6 +84,9 @@ def parse_args():
                    help="do not collect the dominant kernel's instruction counters in this run (two short rocprofv3 children of this script); "
                         "the roofline then rests on the tracked profile alone")
     p.add_argument("--cpu-seconds", type=float, default=18.0, help="budget of the CPU baseline (all cores + one thread)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the frames of the last timed step (rank 0's) to DIR/*.npy: float32 / float64, at most 64 MB "
+                        "(the whole step when it fits, a fixed seeded sample of its pixels otherwise)")
     return p.parse_args()
 
 
@@ -329,6 +335,45 @@ def issue_model(cs: dict, launch_ns: float | None, census: dict | None = None) -
             "lane_utilisation": round(cs["SQ_THREAD_CYCLES_VALU"]/(cs["SQ_INSTS_VALU"]*64.0), 4) if cs.get("SQ_THREAD_CYCLES_VALU") else None}
 
 
+DUMP_BYTES = 64 << 20                  # --dump-outputs: every file together
+DUMP_SAMPLE_PIXELS = 2_000_000         # pixels of the sample when the whole step does not fit: 2 x 24 MB (values + positions)
+DUMP_SEED = 0
+
+
+def dump_outputs(directory: str, frames) -> list[str]:
+    """The frames of the last timed step — `frames`: the device's uint8 RGB buffer as (F, H, W, 3), rows in the buffer's order — as
+    .npy files under `directory`, at most DUMP_BYTES in all:
+      frames.npy                float32 (F, H, W, 3): the whole step, when it fits
+      frames_sample.npy         float32 (K, 3): otherwise the RGB of K pixels, K = min(F*H*W, DUMP_SAMPLE_PIXELS), drawn without
+                                replacement by numpy's default_rng(DUMP_SEED) and sorted: the same pixels for the same F, H, W
+      frames_sample_pixels.npy  float32 (K, 3): (frame, row, column) of each sampled pixel (exact: every index is below 2**24)
+      frame_channel_sums.npy    float64 (F, 3): every pixel of each frame summed per channel (exact), so no pixel goes unchecked"""
+    import numpy as np
+    import torch
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    count, height, width, _ = frames.shape
+    pixels = count*height*width
+    # per frame: a uint8 sum in int64 would materialise the whole step as int64 first
+    sums = torch.stack([frame.reshape(-1, 3).sum(dim=0, dtype=torch.int64) for frame in frames]).cpu().numpy().astype(np.float64)
+    arrays = {"frame_channel_sums": sums}
+    if pixels*3*4 + sums.nbytes <= DUMP_BYTES:
+        arrays["frames"] = frames.cpu().numpy().astype(np.float32)
+    else:
+        chosen = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, size=min(pixels, DUMP_SAMPLE_PIXELS), replace=False))
+        picked = frames.reshape(-1, 3).index_select(0, torch.as_tensor(chosen, device=frames.device))
+        arrays["frames_sample"] = picked.cpu().numpy().astype(np.float32)
+        frame, rest = np.divmod(chosen, height*width)
+        arrays["frames_sample_pixels"] = np.stack([frame, *np.divmod(rest, width)], axis=1).astype(np.float32)
+    assert sum(array.nbytes for array in arrays.values()) <= DUMP_BYTES
+    written = []
+    for name, array in arrays.items():
+        np.save(out/f"{name}.npy", array)
+        written.append(str(out/f"{name}.npy"))
+    return written
+
+
 def refuse(sentence: str) -> "NoReturn":
     """One sentence on stderr and a non-zero exit: a line that says `n_gpus: 1` when N were asked for must never be printed"""
     print(f"bench.py: {sentence}", file=sys.stderr, flush=True)
@@ -407,6 +452,8 @@ def main() -> None:
     args = parse_args()
     if args.gpus < 1:
         refuse(f"--gpus {args.gpus}")
+    if args.dump_outputs and args.steps < 1:
+        refuse(f"--dump-outputs writes the last timed step, and --steps {args.steps} times none")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # (before torch, before the HIP library, before any GPU call)
         raise SystemExit(spawn_ranks(args, sys.argv[1:]))
@@ -686,6 +733,11 @@ def main() -> None:
             legs.append(run_leg(transport, False))
         for transport in transports:
             legs.append(run_leg(transport, True))
+    if args.dump_outputs and rank == 0:
+        # every leg renders the same frame ranges: the last timed step of the last leg is what a caller of step() was handed
+        last = args.warmup + args.steps - 1
+        written = dump_outputs(args.dump_outputs, buffers[last % 2].view(fpb, h, w, 3))
+        print(f"bench.py: the last timed step's frames → {', '.join(written)}", file=sys.stderr)
     # the headline: rgb24 frames (the reference's stream) resident in rank 0's HBM through the faster of the measured transports
     chosen = max((leg for leg in legs if leg["payload"] == "rgb24"), key=lambda leg: leg["value"] or 0.0)
     elapsed = chosen["elapsed_s"]

@@ -176,35 +176,6 @@ def test_alias_covers_every_submodule_with_one_module_object():
         importlib.import_module("shaderflow.no_such_module")
 
 
-REFERENCE_DEMO = Path("/root/reference/examples/basic/demo.py")
-
-
-@pytest.mark.skipif(not REFERENCE_DEMO.exists(), reason="the reference checkout is not present on this machine")
-def test_the_references_own_demo_imports_unchanged():
-    """The drop-in claim for examples/basic/demo.py: the reference's own file, read where it lies and executed unchanged under
-    install_alias(), defines its scenes on THIS package's classes (no GPU needed to import and subclass)"""
-    import importlib.util
-
-    import shaderflow_amd
-    shaderflow_amd.install_alias()
-    spec = importlib.util.spec_from_file_location("reference_demo", REFERENCE_DEMO)
-    demo = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(demo)
-    from shaderflow_amd.scene import ShaderScene
-    scenes = [getattr(demo, n) for n in ("Basic", "ShaderToy", "MultiShader", "Multipass", "MotionBlur", "Dynamics", "Video", "Audio",
-                                         "Waveform", "MusicBars", "Visualizer", "RayMarch", "Life")]
-    assert all(issubclass(scene, ShaderScene) for scene in scenes)
-    assert demo.shaders == REFERENCE_DEMO.parent/"shaders"
-    # the lazy imports inside the scenes' build() methods resolve too (demo.py:134-137, 149-151, 164-166, 178-182, 196-200)
-    from shaderflow.audio import ShaderAudio                          # noqa: F401
-    from shaderflow.audio.spectrogram import ShaderSpectrogram        # noqa: F401
-    from shaderflow.audio.waveform import ShaderWaveform              # noqa: F401
-    from shaderflow.piano import PianoNote                            # noqa: F401
-    from shaderflow.video import ShaderVideo
-    import shaderflow_amd.video
-    assert ShaderVideo is shaderflow_amd.video.ShaderVideo
-
-
 def test_library_exports_every_declared_symbol():
     """include/shaderflow_hip.h ↔ libshaderflow_hip.so ↔ the ctypes prototype table"""
     from shaderflow_amd import _native as N
