@@ -344,7 +344,14 @@ int sfx_tape_build(sfx_handle tape, int nframes, const int64_t* tell, const sfx_
                    const sfx_dyn_coeff_f32* spectrogram, const sfx_dyn_coeff_f64* volume,
                    const sfx_dyn_coeff_f64* std);
 enum { SFX_TAPE_SPECTROGRAM = 0, SFX_TAPE_WAVEFORM = 1, SFX_TAPE_UNIFORMS = 2, SFX_TAPE_TARGETS = 3, SFX_TAPE_LOUDNESS = 4,
-       SFX_TAPE_SCROLL = 5 /* the scrolling texture as each frame sees it: [n][bins][length_samples][channels] f32 */ };
+       SFX_TAPE_SCROLL = 5 /* the scrolling texture as each frame sees it: [n][bins][length_samples][channels] f32 */,
+       SFX_TAPE_STATE = 6  /* sfx_tape_snapshot: [n][2][6] f64 (volume, std) then [n][6][bins*channels] f32 (the spectrogram bins); the six
+                              are value, target, previous, derivative, acceleration, integral after the frame's update() (dynamics.py:197-250) */ };
+/* Keep every frame's whole DynamicNumber state (SFX_TAPE_STATE): what `ShaderAudio.update` / `ShaderSpectrogram.update` /
+ * the two loudness ShaderDynamics leave on the host objects in the frame loop (audio/module.py:446-458, spectrogram.py:304-311),
+ * for a host mirror of those modules under user update() code (tapeloop.py). Copied to pinned memory behind each build; reading it
+ * waits for the build, not for the renders. Call before the first sfx_tape_build. */
+int sfx_tape_snapshot(sfx_handle tape, int enable);
 /* Copies tape content to the host for inspection: SPECTROGRAM [n][bins][channels] f32, WAVEFORM
  * [n][points][channels] f32, UNIFORMS [n][8] f32 (iTime iTau iAudioVolume iAudioVolumeIntegral iAudioSTD
  * iSpectrogramOffset iFrame pad), TARGETS (unsmoothed) [n][bins][channels] f32, LOUDNESS [n][2] f32 */

@@ -18,7 +18,7 @@ OK = 0
 U8, F32, U16, F16 = 0, 1, 2, 3
 NEAREST, LINEAR = 0, 1
 T_FLOAT, T_INT, T_BOOL, T_VEC2, T_VEC3, T_VEC4, T_MAT2, T_MAT3, T_MAT4 = range(9)
-TAPE_SPECTROGRAM, TAPE_WAVEFORM, TAPE_UNIFORMS, TAPE_TARGETS, TAPE_LOUDNESS, TAPE_SCROLL = range(6)
+TAPE_SPECTROGRAM, TAPE_WAVEFORM, TAPE_UNIFORMS, TAPE_TARGETS, TAPE_LOUDNESS, TAPE_SCROLL, TAPE_STATE = range(7)
 E_UNSUPPORTED = -4
 
 Handle = C.c_uint64
@@ -166,6 +166,7 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_tape_create": (C.c_int, [Handle, Handle, P(TapeDesc), C.c_int, P(Handle)]),
     "sfx_clock_tape_create": (C.c_int, [Handle, C.c_int, P(Handle)]),
     "sfx_tape_reset": (C.c_int, [Handle]),
+    "sfx_tape_snapshot": (C.c_int, [Handle, C.c_int]),
     "sfx_clock_sequence_run": (C.c_int, [Handle, P(SequencePass), C.c_int, P(SequenceMatrix), C.c_int, P(ClockTick), C.c_int, Handle, C.c_int, C.c_int,
                                          P(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "sfx_tape_build": (C.c_int, [Handle, C.c_int, P(C.c_int64), P(FrameClock), P(DynCoeffF32), P(DynCoeffF64), P(DynCoeffF64)]),

@@ -292,7 +292,7 @@ struct DynCoeffF64 { double dt, k1, k2, k3; };
 struct FrameClock { float iTime, iTau, iSpectrogramOffset; int iFrame; };
 struct ScalarState { double value, derivative, previous, integral; };
 
-__device__ __forceinline__ void scalar_step(ScalarState& s, double target, const DynCoeffF64& c, double precision, int integrate) {
+__device__ __forceinline__ void scalar_step(ScalarState& s, double target, const DynCoeffF64& c, double precision, int integrate, double* kept_acceleration = nullptr) {
     if (c.dt == 0.0) return;                                          // dynamics.py:210-211
     if (fabs(target - s.value) < precision) {                         // :222-225
         if (integrate) s.integral += (s.value*c.dt);
@@ -303,6 +303,7 @@ __device__ __forceinline__ void scalar_step(ScalarState& s, double target, const
     s.value += (s.derivative*c.dt);                                   // :245
     const double acceleration = (target + c.k3*velocity - s.value - c.k1*s.derivative)/c.k2;   // :246
     s.derivative += (acceleration*c.dt);                              // :247
+    if (kept_acceleration) *kept_acceleration = acceleration;
     if (integrate) s.integral += (s.value*c.dt);                      // :248-249
 }
 
@@ -314,7 +315,10 @@ __device__ __forceinline__ void scalar_step(ScalarState& s, double target, const
 // KEEPER_WAVE: the float64 volume/std systems and the uniforms of a frame are stepped by lane 0 of an extra wave of their own — both
 // halves are chains of dependent operations (IEEE divisions in float32 here, in float64 there) that a single wave would run one after
 // the other; they share nothing, so no barrier is needed between them.
-template <int THREADS, int PER, bool KEEPER_WAVE = false>
+// SNAPSHOT (tapeloop.py): every frame's whole DynamicNumber state — value, target, previous, derivative, acceleration, integral — goes
+// to `snap` ([frame][6][n] float32; the bins never integrate) and `snap64` ([frame][2][6] float64, volume then std), the state the frame
+// loop's host objects hold after that frame's update(). The acceleration then lives in `state` as a fourth array of n.
+template <int THREADS, int PER, bool KEEPER_WAVE = false, bool SNAPSHOT = false>
 __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_scan(int nframes, int n /* bins*channels */,
                                                         const float* __restrict__ targets,     // [frame][n]
                                                         const DynCoeffF32* __restrict__ coeff,
@@ -325,15 +329,17 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
                                                         const DynCoeffF64* __restrict__ vol_coeff, const DynCoeffF64* __restrict__ std_coeff,
                                                         double scalar_precision, int vol_integrate, int std_integrate,
                                                         ScalarState* __restrict__ scalars,     // [2]
-                                                        const FrameClock* __restrict__ clock, FrameDyn* __restrict__ dyn) {
+                                                        const FrameClock* __restrict__ clock, FrameDyn* __restrict__ dyn,
+                                                        float* __restrict__ snap, double* __restrict__ snap64) {
     constexpr int WAVES = THREADS/64;
     if (KEEPER_WAVE && threadIdx.x >= THREADS) n = 0;                 // the keeper's wave holds no values
     __shared__ float red[WAVES > 1 ? WAVES : 1];
     __shared__ int skip_shared;
-    float value[PER], deriv[PER], prev[PER], target[PER], upcoming[PER];
+    float value[PER], deriv[PER], prev[PER], target[PER], upcoming[PER], accel_kept[PER];
 #pragma unroll
     for (int e = 0; e < PER; e++) {
         const int i = threadIdx.x + e*THREADS;
+        accel_kept[e] = (SNAPSHOT && i < n) ? state[3*n + i] : 0.0f;
         value[e] = (i < n) ? state[i] : 0.0f;
         deriv[e] = (i < n) ? state[n + i] : 0.0f;
         prev[e] = (i < n) ? state[2*n + i] : 0.0f;
@@ -341,7 +347,8 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
     }
     const bool keeper = threadIdx.x == (KEEPER_WAVE ? THREADS : 0) && dyn;   // the thread that steps the float64 systems and writes the uniforms
     ScalarState v{}, s{};
-    if (keeper) { v = scalars[0]; s = scalars[1]; }
+    double accel64[2] = {0.0, 0.0};                                   // SNAPSHOT: after the two states in `scalars`
+    if (keeper) { v = scalars[0]; s = scalars[1]; if (SNAPSHOT) { const double* kept = (const double*)(scalars + 2); accel64[0] = kept[0]; accel64[1] = kept[1]; } }
     DynCoeffF32 c_next = nframes > 0 ? coeff[0] : DynCoeffF32{};
     // the keeper's per-frame inputs, requested one frame ahead as well
     FrameClock clock_next{}; float loud_next[2] = {0.0f, 0.0f}; DynCoeffF64 vol_next{}, std_next{};
@@ -393,6 +400,7 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
                     value[e] = value[e] + (deriv[e]*c.dt);
                     const float accel = (((target[e] + (c.k3*velocity)) - value[e]) - (c.k1*deriv[e]))/c.k2;
                     deriv[e] = deriv[e] + (accel*c.dt);
+                    if constexpr (SNAPSHOT) accel_kept[e] = accel;
                 }
             }
             if constexpr (WAVES > 1) __syncthreads();
@@ -401,11 +409,17 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
         for (int e = 0; e < PER; e++) {
             const int i = threadIdx.x + e*THREADS;
             if (i < n) columns[(long)f*n + i] = value[e];
+            if constexpr (SNAPSHOT) {
+                if (i < n) {
+                    float* o = snap + (long)f*6*n + i;
+                    o[0] = value[e]; o[n] = target[e]; o[2*n] = prev[e]; o[3*n] = deriv[e]; o[4*n] = accel_kept[e]; o[5*n] = 0.0f;
+                }
+            }
         }
         if (keeper) {
             if (loudness) {
-                scalar_step(v, (double)loud_now[0], vol_now, scalar_precision, vol_integrate);
-                scalar_step(s, (double)loud_now[1], std_now, scalar_precision, std_integrate);
+                scalar_step(v, (double)loud_now[0], vol_now, scalar_precision, vol_integrate, SNAPSHOT ? &accel64[0] : nullptr);
+                scalar_step(s, (double)loud_now[1], std_now, scalar_precision, std_integrate, SNAPSHOT ? &accel64[1] : nullptr);
             }
             FrameDyn d;
             d.iTime = clock_now.iTime; d.iTau = clock_now.iTau; d.iFrame = clock_now.iFrame;
@@ -413,13 +427,22 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
             d.iAudioVolume = (float)v.value; d.iAudioVolumeIntegral = (float)v.integral; d.iAudioSTD = (float)s.value;
             d.pad = 0;
             dyn[f] = d;
+            if constexpr (SNAPSHOT) {
+                double* o = snap64 + (long)f*12;
+                const double targets[2] = {(double)loud_now[0], (double)loud_now[1]};
+                const ScalarState* systems[2] = {&v, &s};
+                for (int q = 0; q < 2; q++) {
+                    o[6*q + 0] = systems[q]->value; o[6*q + 1] = targets[q]; o[6*q + 2] = systems[q]->previous;
+                    o[6*q + 3] = systems[q]->derivative; o[6*q + 4] = accel64[q]; o[6*q + 5] = systems[q]->integral;
+                }
+            }
         }
     }
-    if (keeper) { scalars[0] = v; scalars[1] = s; }
+    if (keeper) { scalars[0] = v; scalars[1] = s; if (SNAPSHOT) { double* kept = (double*)(scalars + 2); kept[0] = accel64[0]; kept[1] = accel64[1]; } }
 #pragma unroll
     for (int e = 0; e < PER; e++) {
         const int i = threadIdx.x + e*THREADS;
-        if (i < n) { state[i] = value[e]; state[n + i] = deriv[e]; state[2*n + i] = prev[e]; }
+        if (i < n) { state[i] = value[e]; state[n + i] = deriv[e]; state[2*n + i] = prev[e]; if (SNAPSHOT) state[3*n + i] = accel_kept[e]; }
     }
 }
 

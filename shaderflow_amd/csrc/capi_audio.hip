@@ -212,12 +212,17 @@ static int check_audio(const Plan* p, const Audio* a) {
 // per thread for up to 16 384: the early-out's maximum is still ONE block-wide reduction per frame (the recurrence couples the values
 // through it, so the scan stays in one block; at 16 waves a thread may hold 128 registers)
 constexpr int DYNAMICS_SCAN_LIMIT = 16384;
-template <class... Args> static void launch_dynamics_scan(hipStream_t s, int nframes, int n, Args... args) {
-    if (n <= 256) hipLaunchKernelGGL((k_dynamics_scan<64, 4, true>), dim3(1), dim3(128), 0, s, nframes, n, args...);
-    else if (n <= 2048) hipLaunchKernelGGL((k_dynamics_scan<1024, 2>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
-    else if (n <= 4096) hipLaunchKernelGGL((k_dynamics_scan<1024, 4>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
-    else if (n <= 8192) hipLaunchKernelGGL((k_dynamics_scan<1024, 8>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
-    else hipLaunchKernelGGL((k_dynamics_scan<1024, 16>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
+template <bool SNAPSHOT, class... Args> static void launch_dynamics_scan_as(hipStream_t s, int nframes, int n, Args... args) {
+    if (n <= 256) hipLaunchKernelGGL((k_dynamics_scan<64, 4, true, SNAPSHOT>), dim3(1), dim3(128), 0, s, nframes, n, args...);
+    else if (n <= 2048) hipLaunchKernelGGL((k_dynamics_scan<1024, 2, false, SNAPSHOT>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
+    else if (n <= 4096) hipLaunchKernelGGL((k_dynamics_scan<1024, 4, false, SNAPSHOT>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
+    else if (n <= 8192) hipLaunchKernelGGL((k_dynamics_scan<1024, 8, false, SNAPSHOT>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
+    else hipLaunchKernelGGL((k_dynamics_scan<1024, 16, false, SNAPSHOT>), dim3(1), dim3(1024), 0, s, nframes, n, args...);
+}
+// `snap` / `snap64` non-null: the variant that also writes every frame's whole state (sfx_tape_snapshot)
+template <class... Args> static void launch_dynamics_scan(hipStream_t s, int nframes, int n, float* snap, double* snap64, Args... args) {
+    if (snap) launch_dynamics_scan_as<true>(s, nframes, n, args..., snap, snap64);
+    else launch_dynamics_scan_as<false>(s, nframes, n, args..., (float*)nullptr, (double*)nullptr);
 }
 
 // device-side launches shared by the per-frame entry points and the tape
@@ -374,7 +379,7 @@ extern "C" int sfx_dynamics_scan(sfx_handle h, int nframes, int n, const float* 
         hipMemcpyAsync(d_targets, targets, frame_bytes, hipMemcpyHostToDevice, s);
         hipMemcpyAsync(d_state, state, sizeof(float)*3*n, hipMemcpyHostToDevice, s);
         hipMemcpyAsync(d_coeff, coeff, sizeof(DynCoeffF32)*nframes, hipMemcpyHostToDevice, s);
-        launch_dynamics_scan(s, nframes, n, d_targets, d_coeff, precision, d_state, d_values,
+        launch_dynamics_scan(s, nframes, n, (float*)nullptr, (double*)nullptr, d_targets, d_coeff, precision, d_state, d_values,
                              (const float*)nullptr, (const DynCoeffF64*)nullptr, (const DynCoeffF64*)nullptr, 0.0, 0, 0,
                              (ScalarState*)nullptr, (const FrameClock*)nullptr, (FrameDyn*)nullptr);
         rc = launch_status();
@@ -431,6 +436,8 @@ struct TapeBank {
     FrameDyn* d_dyn = nullptr; DynCoeffF32* d_coeff = nullptr; DynCoeffF64 *d_vol = nullptr, *d_std = nullptr; FrameClock* d_clock = nullptr;
     VisualizerConsts* d_vis = nullptr; float *d_bars = nullptr, *d_scroll = nullptr;
     char* staging = nullptr;         // pinned: the host's schedule arrays of the batch, laid out like d_schedule
+    float* d_snap = nullptr; double* d_snap64 = nullptr;   // sfx_tape_snapshot: every frame's DynamicNumber state ([F][6][n] f32, [F][2][6] f64)
+    char* snap_host = nullptr;       // pinned: both, copied behind the build ([F][2][6] f64, then [F][6][n] f32)
     char* d_schedule = nullptr;      // d_tell | d_clock | d_coeff | d_vol | d_std in one allocation: one copy per build
     hipEvent_t built = nullptr, rendered = nullptr;
 };
@@ -448,7 +455,8 @@ struct Tape : Object {
     TapeBank bank[2]; int current = 0; bool built_once = false;
     hipStream_t audio_stream = nullptr;
     FilterbankScratch scratch;       // of this tape's builds (audio_stream)
-    float* d_state = nullptr; ScalarState* d_scalars = nullptr;
+    float* d_state = nullptr; ScalarState* d_scalars = nullptr;   // d_state: value | derivative | previous | acceleration, n each
+    bool snapshot = false;           // (d_scalars: the two states, then their two accelerations)
     void* d_screen = nullptr; size_t screen_bytes = 0;   // iScreen scratch of the two-pass path (frames of a batch)
     // scrolling spectrogram (length_samples > 1, spectrogram.py:298-311): ring of the last columns
     int width = 1, ring_frames = 0; long frames_done = 0;
@@ -493,8 +501,8 @@ extern "C" int sfx_tape_reset(sfx_handle h) {
     if (!t) return fail(SFX_E_INVALID, "invalid tape handle");
     if (!t->plan) return SFX_OK;                                    // clock tape: no recurrences to reset
     USE_DEVICE(t->ctx);
-    HIP_TRY(hipMemsetAsync(t->d_state, 0, sizeof(float)*3*t->n, t->audio_stream));   // in order with the builds before and after it
-    HIP_TRY(hipMemsetAsync(t->d_scalars, 0, sizeof(ScalarState)*2, t->audio_stream));
+    HIP_TRY(hipMemsetAsync(t->d_state, 0, sizeof(float)*4*t->n, t->audio_stream));   // in order with the builds before and after it
+    HIP_TRY(hipMemsetAsync(t->d_scalars, 0, sizeof(ScalarState)*2 + 2*sizeof(double), t->audio_stream));
     t->frames_done = 0;                                             // the scrolling texture starts empty again
     return SFX_OK;
 }
@@ -534,8 +542,8 @@ extern "C" int sfx_tape_create(sfx_handle hp, sfx_handle ha, const sfx_tape_desc
     const int pts = desc->points > 0 ? desc->points : 1;
     t->width = desc->length_samples > 1 ? desc->length_samples : 1;
     bool allocated = tape_open_streams(t) &&
-        hipMalloc(&t->d_state, sizeof(float)*3*t->n) == hipSuccess &&
-        hipMalloc(&t->d_scalars, sizeof(ScalarState)*2) == hipSuccess;
+        hipMalloc(&t->d_state, sizeof(float)*4*t->n) == hipSuccess &&
+        hipMalloc(&t->d_scalars, sizeof(ScalarState)*2 + 2*sizeof(double)) == hipSuccess;
     for (TapeBank& k : t->bank)
         allocated = allocated &&
             hipMalloc((void**)&k.d_schedule, schedule_layout(max_frames).at[5]) == hipSuccess &&
@@ -611,7 +619,7 @@ extern "C" int sfx_tape_build(sfx_handle h, int nframes, const int64_t* tell, co
         hipLaunchKernelGGL(k_waveform_rows, dim3((t->desc.points*a->channels + 3)/4, nframes), dim3(256), 0, s,
                            a->pcm, a->samples, a->channels, k.d_tell, t->desc.chunk_size, t->desc.points, t->desc.reducer, k.d_rows);
     hipLaunchKernelGGL(k_volume_std, dim3(nframes), dim3(256), 0, s, a->pcm, a->samples, a->channels, k.d_tell, t->desc.volume_window, k.d_loudness);
-    launch_dynamics_scan(s, nframes, t->n, k.d_targets, k.d_coeff, (float)t->desc.precision,
+    launch_dynamics_scan(s, nframes, t->n, k.d_snap, k.d_snap64, k.d_targets, k.d_coeff, (float)t->desc.precision,
                          t->d_state, k.d_columns, k.d_loudness, k.d_vol, k.d_std, t->desc.precision,
                          t->desc.volume_integrate, t->desc.std_integrate, t->d_scalars, k.d_clock, k.d_dyn);
     if (t->width > 1) {
@@ -621,11 +629,32 @@ extern "C" int sfx_tape_build(sfx_handle h, int nframes, const int64_t* tell, co
         hipLaunchKernelGGL(k_spectrogram_scroll, dim3((unsigned)((texels + 255)/256)), dim3(256), 0, s, t->d_ring, t->ring_frames, t->frames_done, nframes,
                            p->bins, p->channels, t->width, k.d_scroll);
     }
+    if (t->snapshot) {                                              // into pinned memory on the tape's stream: read once per batch
+        HIP_TRY(hipMemcpyAsync(k.snap_host, k.d_snap64, sizeof(double)*12*nframes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(k.snap_host + sizeof(double)*12*t->max_frames, k.d_snap, sizeof(float)*6*(size_t)t->n*nframes, hipMemcpyDeviceToHost, s));
+    }
     t->frames_done += nframes;
     const int rc = launch_status();
     HIP_TRY(hipEventRecord(k.built, s));
     tape_select(t, b); t->built_once = true;
     return rc;
+}
+
+extern "C" int sfx_tape_snapshot(sfx_handle h, int enable) {
+    Tape* t = get<Tape>(h, MAGIC_TAPE);
+    if (!t) return fail(SFX_E_INVALID, "invalid tape handle");
+    if (!t->plan) return fail(SFX_E_INVALID, "a clock tape has no DynamicNumber state");
+    if (t->built_once) return fail(SFX_E_INVALID, "sfx_tape_snapshot after the first build: the acceleration state was not kept");
+    if (!enable || t->snapshot) { t->snapshot = t->snapshot && enable; return SFX_OK; }
+    USE_DEVICE(t->ctx);
+    const size_t F = t->max_frames;
+    for (TapeBank& k : t->bank) {
+        if (hipMalloc(&k.d_snap, sizeof(float)*6*(size_t)t->n*F) != hipSuccess || hipMalloc(&k.d_snap64, sizeof(double)*12*F) != hipSuccess ||
+            hipHostMalloc((void**)&k.snap_host, (sizeof(float)*6*(size_t)t->n + sizeof(double)*12)*F, hipHostMallocDefault) != hipSuccess)
+            return fail(SFX_E_HIP, "state snapshot of %zu frames x %d values: out of memory", F, t->n);
+    }
+    t->snapshot = true;
+    return SFX_OK;
 }
 
 extern "C" int sfx_tape_read(sfx_handle h, int what, int frame0, int nframes, void* out, size_t nbytes) {
@@ -636,6 +665,17 @@ extern "C" int sfx_tape_read(sfx_handle h, int what, int frame0, int nframes, vo
     const char* src; size_t per;
     const int pts = t->desc.points > 0 ? t->desc.points : 1;
     if (!t->plan && what != SFX_TAPE_UNIFORMS) return fail(SFX_E_INVALID, "a clock tape holds the per-frame uniforms only");
+    if (what == SFX_TAPE_STATE) {
+        // from the pinned copy the build queued: waits for the tape's stream only, never for the renders on the context's
+        if (!t->snapshot) return fail(SFX_E_INVALID, "the tape keeps no state snapshot (sfx_tape_snapshot before the first build)");
+        const size_t per64 = sizeof(double)*12, per32 = sizeof(float)*6*(size_t)t->n;
+        if (nbytes != (per64 + per32)*nframes) return fail(SFX_E_INVALID, "tape read of %zu bytes, section needs %zu", nbytes, (per64 + per32)*nframes);
+        const TapeBank& k = t->bank[t->current];
+        HIP_TRY(hipEventSynchronize(k.built));
+        memcpy(out, k.snap_host + per64*frame0, per64*nframes);
+        memcpy((char*)out + per64*nframes, k.snap_host + per64*t->max_frames + per32*frame0, per32*nframes);
+        return SFX_OK;
+    }
     switch (what) {
         case SFX_TAPE_SPECTROGRAM: src = (const char*)t->d_columns; per = sizeof(float)*t->n; break;
         case SFX_TAPE_WAVEFORM: src = (const char*)t->d_rows; per = sizeof(float)*pts*t->audio->channels; break;
@@ -662,8 +702,9 @@ extern "C" int sfx_tape_destroy(sfx_handle h) {
     hipStreamSynchronize(t->ctx->stream);
     for (TapeBank& k : t->bank) {
         hipFree(k.d_schedule); hipFree(k.d_power); hipFree(k.d_targets); hipFree(k.d_columns); hipFree(k.d_rows); hipFree(k.d_loudness);
-        hipFree(k.d_dyn); hipFree(k.d_vis); hipFree(k.d_bars); hipFree(k.d_scroll);
+        hipFree(k.d_dyn); hipFree(k.d_vis); hipFree(k.d_bars); hipFree(k.d_scroll); hipFree(k.d_snap); hipFree(k.d_snap64);
         if (k.staging) hipHostFree(k.staging);
+        if (k.snap_host) hipHostFree(k.snap_host);
         if (k.built) hipEventDestroy(k.built);
         if (k.rendered) hipEventDestroy(k.rendered);
     }

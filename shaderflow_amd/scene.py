@@ -15,6 +15,8 @@ Two execution modes produce the same frames:
   * frame tape  — when nothing in the scene needs python between frames (see `tape.py`), the audio state of a
                   whole batch of frames is computed on the device and the frames are rendered back-to-back
                   with no host round trips. `main(batch=None)` picks it automatically.
+  * tape loop   — audio scenes with python logic of their own (`tapeloop.py`): the audio state from the device tape,
+                  the user's modules frame by frame on top of it. Also picked by `main(batch=None)`.
 """
 from __future__ import annotations
 
@@ -61,6 +63,7 @@ class ShaderScene(ShaderModule):
     """Scenes in which only the clock moves between frames take clockloop.ClockLoop (same frames, a fifth of the python per frame)"""
     """Shade + resolve in one kernel when final.glsl's taps stay inside the pixel's own supersamples"""
 
+    tape_loop = None                                          # plain class attribute: the TapeLoop of the last main(), if it took one
     _fused_this_frame: bool = False
     _skip_render: bool = False
     shard_warmup = "auto"                                     # plain class attribute: subclasses override it like `life_period`
@@ -330,6 +333,7 @@ class ShaderScene(ShaderModule):
         self.rdt = 0.0
         self.relay(ShaderMessage.Shader.Compile)
         self.scheduler.clear()
+        self.tape_loop = None
 
         _width, _height = self.resize(width=width, height=height, ratio=ratio, scale=scale)
 
@@ -371,6 +375,11 @@ class ShaderScene(ShaderModule):
         from shaderflow_amd.clockloop import ClockLoop
         if self.freewheel and batch is None and self.clock_loop and ClockLoop.applicable(self):
             return ClockLoop(self).run(export, turbo)
+        # audio scenes with python logic of their own: the audio from the device tape, the user's update() frame by frame (tapeloop.py)
+        from shaderflow_amd.tapeloop import TapeLoop
+        if batch is None and TapeLoop.applicable(self):
+            self.tape_loop = TapeLoop(self)
+            return self.tape_loop.run(export, turbo)
         while (task := self.scheduler.next()):
             if (task is not self.vsync):
                 continue

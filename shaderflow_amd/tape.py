@@ -84,6 +84,12 @@ class FrameTape:
             return False
         if not (audios or spectrograms or waveforms):
             return True                                           # clock tape: only iTime/iTau/iFrame change between frames
+        return FrameTape.audio_fits(audios, spectrograms, waveforms)
+
+    @staticmethod
+    def audio_fits(audios: list, spectrograms: list, waveforms: list) -> bool:
+        """Whether these audio modules of a scene (at least one of them) are what a tape computes: one ShaderAudio with device PCM, at
+        most one spectrogram and one waveform of it, a magnitude the STFT kernel evaluates, and sizes the scan and one batch hold"""
         if len(audios) != 1 or len(spectrograms) > 1 or len(waveforms) > 1:
             return False
         audio = audios[0]
