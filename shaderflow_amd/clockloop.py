@@ -155,7 +155,7 @@ class ClockLoop:
                 tables[m] = N.SequenceMatrix(texture.temporal, texture.layers, handles, names)
             return tables
         planar = None
-        if export.planar and export._yuv_slots:
+        if export._yuv_slots:                                           # (staging exists for a planar sink only)
             planar = (C.c_void_p*len(export._yuv_slots))(*export._yuv_slots)
         piping = export.fileno is not None and export.ring is not None
         done = 0

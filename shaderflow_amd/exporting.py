@@ -82,6 +82,13 @@ class ExportingHelper:
     def to_yuv(self, rgb: int, yuv: int, frames: int = 1) -> None:
         self.scene.context.rgb_to_yuv420(rgb, yuv, self.scene.width, self.scene.height, frames, 1 if self.yuv_matrix == "bt709" else 0)
 
+    def to_sink(self, rgb: int, target: int, frames: int = 1) -> None:
+        """`frames` RGB8 frames on the device → sink frames at `target`, on the context's stream"""
+        if self.planar:
+            self.to_yuv(rgb, target, frames)
+        else:
+            self.scene.context.copy(target, rgb, frames*self.frame_bytes)
+
     @property
     def finished(self) -> bool:
         return (self.frame >= self.total_frames)
@@ -220,14 +227,14 @@ class ExportingHelper:
         if self.ring is not None and self.ring.value:
             N.check(N.lib().sfx_ring_pipe_sync(self.ring, -1))
 
-    def pipe_device(self, device_ptr: int, turbo: bool = True, fence: Optional[int] = None) -> None:
-        """Same, for a frame that lives in a raw device buffer (frame tape batches)"""
+    def pipe_device(self, device_ptr: int, *, rgb: bool, turbo: bool = True, fence: Optional[int] = None) -> None:
+        """Same, for a frame in a raw device buffer: an RGB8 frame (`rgb`, converted here for a planar sink) or a sink frame"""
         if (self.fileno is None) or (self.ring is None):
             return
         self._check_encoder()
         slot = self.frame % self.slots
-        if self.planar and not getattr(self, "_device_frames_are_planar", False):
-            N.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))     # (an RGB frame in a device buffer: the sharded frame loop's path)
+        if rgb and self.planar:
+            N.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
             self.to_yuv(device_ptr, self._yuv_slots[slot])
             device_ptr, fence = self._yuv_slots[slot], None
         if fence is None:
@@ -239,11 +246,11 @@ class ExportingHelper:
             N.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
 
     def pipe_device_frames(self, device_ptr: int, stride: int, count: int, turbo: bool = True, fence: Optional[int] = None) -> None:
-        """`count` consecutive frames of a batch in one native call (the per-frame python loop costs more than the frames themselves
+        """`count` consecutive SINK frames of a batch in one native call (the per-frame python loop costs more than the frames themselves
         when they are small); with a progress relay, or without turbo, frame by frame as before"""
         if self.relay is not None or not turbo or self.fileno is None or self.ring is None:
             for i in range(count):
-                self.pipe_device(device_ptr + i*stride, turbo=turbo, fence=fence)
+                self.pipe_device(device_ptr + i*stride, rgb=False, turbo=turbo, fence=fence)
                 self.update()
             return
         self._check_encoder()
@@ -280,3 +287,35 @@ class ExportingHelper:
         took = self.took or 1e-9
         logger.info(f"Finished rendering ({output if not isinstance(output, bytes) else f'{len(output)} bytes'}) • "
                     f"took {took:.2f}s at {self.frame/took:.2f} fps | {self.scene.runtime/took:.2f}x realtime, {self.frame} frames")
+
+
+class SinkBatches:
+    """`count` device buffers of `batch` sink frames, and the rule that fills them: a batch is rendered straight into place as rgb24, or
+    into one RGB8 scratch of a batch and converted right behind as yuv420p — both on the context's stream, so one scratch serves every
+    buffer (allocated by the first batch rendered through it)."""
+
+    def __init__(self, export: ExportingHelper, batch: int, count: int = 2):
+        self.export, self.batch, self.context = export, batch, export.scene.context
+        self.rgb_bytes = export.scene.width*export.scene.height*3
+        self.scratch: Optional[int] = None
+        self.last_rgb: Optional[int] = None                 # the last RGB8 frame of the last batch rendered (for iFinal)
+        self.buffers = [self.context.alloc(export.frame_bytes*batch) for _ in range(count)]
+
+    def render(self, target: int, count: int, draw: Callable[[int, int], None]) -> None:
+        """`draw(count, pointer)` renders `count` RGB8 frames at `pointer`; they end up as sink frames at `target`"""
+        assert 0 < count <= self.batch, (count, self.batch)
+        rgb = target
+        if self.export.planar:
+            if self.scratch is None:
+                self.scratch = self.context.alloc(self.rgb_bytes*self.batch)
+            rgb = self.scratch
+        draw(count, rgb)
+        if rgb != target:
+            self.export.to_yuv(rgb, target, count)
+        self.last_rgb = rgb + (count - 1)*self.rgb_bytes
+
+    def close(self) -> None:
+        self.context.synchronize()
+        for pointer in self.buffers + ([self.scratch] if self.scratch is not None else []):
+            self.context.free(pointer)
+        self.buffers, self.scratch = [], None

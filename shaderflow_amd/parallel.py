@@ -3,7 +3,7 @@ Multi-GPU offline export (one process per GPU; the reference is single-process, 
 
 Frames are independent once the audio tape is known, except for the DynamicNumber recurrences, which every rank replays on
 its own device (a few kernels over ~1 KB per frame: far cheaper than communicating state, bit-identical by construction).
-What is left to decide is how the finished RGB8 frames reach the ONE process that owns the sink (rank 0). Two modes
+What is left to decide is how the finished frames reach the ONE process that owns the sink (rank 0). Three modes
 (`SHADERFLOW_SHARD`, default "host"):
 
 * **device** — the north star's design: every rank renders ONE CONTIGUOUS frame range (`shard_frames`) into HBM — a whole
@@ -19,13 +19,14 @@ What is left to decide is how the finished RGB8 frames reach the ONE process tha
   for the pair of GPUs, up to four copies in flight): the engines move the bytes over the rank's own xGMI link at close to link rate
   and no compute unit is taken from the render — what RCCL's point-to-point kernels cannot offer. A gloo side channel carries
   "chunk k has landed".
-* every mode moves SINK frames: rgb24, or — `scene.main(pixel_format="yuv420p")` — planar frames converted on the rank that rendered
-  them (half the bytes per link; round 5).
 * **host** — every rank reads its finished frames out over ITS OWN PCIe link into a shared-memory ring and rank 0's native
   writer thread interleaves them in frame order (`HostDelivery`, csrc/shm_ring.inc): no collective on the data path, ceiling
   N x min(render, PCIe) until the sink or host memory bandwidth binds. Here batches alternate between the ranks (batch b on
   rank b % N): the sink consumes in frame order, so with contiguous ranges only one rank's link would be busy at a time unless
-  whole ranges were buffered on the host; alternating batches keep every link busy with two batches of host ring per rank.
+  whole ranges were buffered on the host; alternating batches keep every link busy with a ring of about a batch per rank.
+
+Every mode moves SINK frames: rgb24, or — `scene.main(pixel_format="yuv420p")` — planar frames converted on the rank that rendered them
+(half the bytes per link). Frame-loop scenes take gathered round-robin rounds in the device modes (`sharded_frame_loop`).
 
 torch.distributed (backend "nccl" = RCCL on ROCm; "gloo" in the tests) provides rendezvous, barriers and the device-mode sends.
 """
@@ -322,25 +323,46 @@ def interleaved_host_export(world: int, rank: int, batches: list[tuple[int, int]
         advance(first, count, buffer)   the tape / host state of those frames (all ranks, all batches; `buffer` is None for batches
                                         of other ranks — frame-loop scenes shade their own frames into it while they step)
         render(count, buffer)           render them into `buffer` (the owner), asynchronously on the context's stream
-        delivery.push(buffer, count) / delivery.wait(frames)
+        delivery.push(buffer, count) / delivery.wait(frames)    (its owner, host_export, aborts it when this raises)
     """
     marks: list[int] = []                                            # frames pushed after each of this rank's batches
+    for index, (first, count) in enumerate(batches):
+        if index % world != rank:
+            advance(first, count, None)
+            continue
+        mine = len(marks)
+        if mine >= len(buffers):
+            delivery.wait(marks[mine - len(buffers)])               # the batch that last lived in this buffer has been copied out
+        buffer = buffers[mine % len(buffers)]
+        advance(first, count, buffer)
+        render(count, buffer)
+        delivery.push(buffer, count)
+        marks.append(delivery.pushed)
+
+
+def host_export(export, world: int, rank: int, batches: list[tuple[int, int]], batch: int, slots: int, advance, draw=None) -> None:
+    """Host mode end to end (tape and frame-loop scenes): a cross-process ring of `slots` sink frames per rank (or SHADERFLOW_SHM_SLOTS),
+    two batch buffers of sink frames (exporting.SinkBatches) and `interleaved_host_export`. `draw(count, pointer)` renders RGB8 frames
+    for a batch; None when `advance` keeps the frames itself (frame loop)."""
+    from shaderflow_amd.exporting import SinkBatches
+    slots = int(os.environ.get("SHADERFLOW_SHM_SLOTS", 0)) or slots
+    delivery = HostDelivery(export.scene.context, world, rank, export.frame_bytes, slots, export.fileno if rank == 0 else None,
+                            interleaved_runs(world, batches))
+    sink: Optional[SinkBatches] = None
     try:
-        for index, (first, count) in enumerate(batches):
-            if index % world != rank:
-                advance(first, count, None)
-                continue
-            mine = len(marks)
-            if mine >= len(buffers):
-                delivery.wait(marks[mine - len(buffers)])           # the batch that last lived in this buffer has been copied out
-            buffer = buffers[mine % len(buffers)]
-            advance(first, count, buffer)
-            render(count, buffer)
-            delivery.push(buffer, count)
-            marks.append(delivery.pushed)
+        sink = SinkBatches(export, batch)
+        render = (lambda count, buffer: sink.render(buffer, count, draw)) if draw is not None else (lambda count, buffer: None)
+        interleaved_host_export(world, rank, batches, advance, render, delivery, sink.buffers)
     except BaseException:
-        delivery.abort()                                            # a producer that raises tells the others now, not after their time-out
+        delivery.abort()                                            # a rank that raises tells the others now, not after their time-out
         raise
+    finally:
+        try:
+            delivery.finish()                                       # the ring copies out of the buffers until here
+        finally:
+            if sink is not None:
+                sink.close()
+    export.frame = export.total_frames
 
 
 # ---- device mode: contiguous ranges, resident in HBM, sent to rank 0 ---------------------------------------------------------

@@ -59,9 +59,9 @@ class ShaderScene(ShaderModule):
     _final: ShaderProgram = None
 
     fuse: bool = True
+    """Shade + resolve in one kernel when final.glsl's taps stay inside the pixel's own supersamples"""
     clock_loop: bool = os.environ.get("SHADERFLOW_CLOCK_LOOP", "1") != "0"
     """Scenes in which only the clock moves between frames take clockloop.ClockLoop (same frames, a fifth of the python per frame)"""
-    """Shade + resolve in one kernel when final.glsl's taps stay inside the pixel's own supersamples"""
 
     tape_loop = None                                          # plain class attribute: the TapeLoop of the last main(), if it took one
     _fused_this_frame: bool = False
@@ -245,6 +245,12 @@ class ShaderScene(ShaderModule):
         """(height, width, components) uint8, top row first (scene.py:439-443)"""
         return np.flipud(self._final.texture.texture.read())
 
+    def write_final(self, pointer: int, top_down: bool) -> None:
+        """iFinal ← the RGB8 frame at `pointer` on the device (rows top-down when `top_down`), as the frame loop would have left it"""
+        self.context.synchronize()
+        frame = self.context.read(pointer, self.width*self.height*3).reshape(self.height, self.width, 3)
+        self._final.texture.texture.write(np.ascontiguousarray(frame[::-1] if top_down else frame))
+
     # frame loop -------------------------------------------------------------------------------------------------
 
     scheduler: Scheduler = Factory(Scheduler)
@@ -400,11 +406,10 @@ class ShaderScene(ShaderModule):
         """Multi-GPU export of a frame-loop scene (python logic between frames, layered/temporal textures): every rank steps
         through all frames so that host state stays in lock step, launches shaders only for its own batches and their
         warm-up, and rank 0 receives the finished frames in order (parallel.sharded_frame_loop)."""
-        from shaderflow_amd.parallel import (FrameGather, HostDelivery, frame_modes, interleaved_host_export, interleaved_runs, shard_batches,
-                                             shard_mode, sharded_frame_loop)
+        from shaderflow_amd.parallel import FrameGather, frame_modes, host_export, shard_batches, shard_mode, sharded_frame_loop
         total = export.total_frames
-        # the frames a rank keeps, sends and delivers are SINK frames: rgb24 copies of iFinal, or — pixel_format "yuv420p" — planar frames
-        # converted on the rank that rendered them, straight into the batch buffer (half the bytes over every link)
+        # the frames a rank keeps, sends and delivers are SINK frames, converted on the rank that rendered them (half the bytes over
+        # every link as yuv420p)
         frame_bytes = export.frame_bytes
         batches = shard_batches(0, total, batch)
         warmup = self.shard_warmup
@@ -415,86 +420,52 @@ class ShaderScene(ShaderModule):
         context = self.context
         distributed = is_sharded()
 
-        def keep(target: int) -> None:                          # iFinal of the frame just rendered → its place in the batch buffer
-            if export.planar:
-                export.to_yuv(self._final.texture.texture.device_ptr(), target)
-            else:
-                context.copy(target, self._final.texture.texture.device_ptr(), frame_bytes)
-        export._device_frames_are_planar = export.planar       # what the sink's rank pipes from device buffers is converted already
-        if distributed and shard_mode() == "host":
-            # every rank reads the frames of its own batches out over its own PCIe link into shared memory; rank 0's writer thread
-            # hands them to the sink in frame order (parallel.HostDelivery)
-            import os
-            slots = int(os.environ.get("SHADERFLOW_SHM_SLOTS", 0)) or max(4, min(2*batch, (4 << 30)//frame_bytes))
-            delivery = HostDelivery(context, world, rank, frame_bytes, slots, export.fileno if rank == 0 else None, interleaved_runs(world, batches))
-            pointers = [context.alloc(frame_bytes*batch) for _ in range(2)]
-
-            def advance(first: int, count: int, pointer) -> None:
-                for i in range(count):
-                    mode = modes[first + i]
-                    self._skip_render = (mode == 0)
-                    self._one_frame()
-                    if mode == 2:
-                        keep(pointer + i*frame_bytes)
-
-            try:
-                interleaved_host_export(world, rank, batches, advance, lambda count, pointer: None, delivery, pointers)
-            finally:
-                self._skip_render = False
-                delivery.finish()
-                context.synchronize()
-                for pointer in pointers:
-                    context.free(pointer)
-            export.frame = total
-            return export.finish()
-        if distributed:
-            import torch
-            device = torch.device("cuda", context.device)
-            tensors = [torch.zeros(frame_bytes*batch, dtype=torch.uint8, device=device) for _ in range(2)]
-            torch.cuda.synchronize(device)                  # the fill runs on torch's stream, the renders on the context's
-            pointer_of = lambda buffer: buffer.data_ptr()
-            gather = FrameGather(world, rank, frame_bytes*batch, device)
-        else:                                                   # one rank's share, no process group: frames of foreign batches are dropped
-            tensors = [context.alloc(frame_bytes*batch) for _ in range(2)]
-            pointer_of = lambda buffer: buffer
-            gather = None
-
-        def step(frame: int, mode: int, buffer, offset: int) -> None:
-            self._skip_render = (mode == 0)
+        def step(frame: int, target: Optional[int]) -> None:
+            self._skip_render = (modes[frame] == 0)
             self._one_frame()
-            if mode == 2:
-                keep(pointer_of(buffer) + offset)
+            if modes[frame] == 2:                               # iFinal of the frame just rendered → its place in the batch buffer
+                export.to_sink(self._final.texture.texture.device_ptr(), target)
+
+        def advance(first: int, count: int, buffer: Optional[int]) -> None:
+            for i in range(count):
+                step(first + i, None if buffer is None else buffer + i*frame_bytes)
 
         def emit(buffer, count: int) -> None:                   # rank 0 of a process group: frames arrive in order
             for i in range(count):
-                export.pipe_device(pointer_of(buffer) + i*frame_bytes, turbo=turbo)
+                export.pipe_device(buffer.data_ptr() + i*frame_bytes, rgb=False, turbo=turbo)
                 export.update()
             export.drain()                                      # the gathered buffer is overwritten by a later gather
 
+        buffer = None
         try:
-            if gather is None:
-                # no process group: walk every frame, hand this rank's own batches to the sink
-                for index, (first, count) in enumerate(batches):
-                    for i in range(count):
-                        step(first + i, modes[first + i], tensors[0], i*frame_bytes)
-                    if index % world == rank:
-                        context.synchronize()
-                        for i in range(count):
-                            export.pipe_device(tensors[0] + i*frame_bytes, turbo=False)
-                            export.update()
-                export.frame = total
-            else:
-                sharded_frame_loop(world, rank, batches, modes, step, context.synchronize, emit, gather, tensors, frame_bytes)
+            if distributed and shard_mode() == "host":
+                # every rank reads the frames of its own batches out over its own PCIe link into shared memory (parallel.host_export)
+                host_export(export, world, rank, batches, batch, max(4, min(2*batch, (4 << 30)//frame_bytes)), advance)
+            elif distributed:
+                import torch
+                device = torch.device("cuda", context.device)
+                tensors = [torch.zeros(frame_bytes*batch, dtype=torch.uint8, device=device) for _ in range(2)]
+                torch.cuda.synchronize(device)                  # the fill runs on torch's stream, the renders on the context's
+                gather = FrameGather(world, rank, frame_bytes*batch, device)
+                sharded_frame_loop(world, rank, batches, modes, lambda frame, mode, tensor, offset: step(frame, tensor.data_ptr() + offset),
+                                   context.synchronize, emit, gather, tensors, frame_bytes)
                 if rank != 0:
                     export.frame = total
+            else:
+                # one rank's share, no process group: walk every frame, hand this rank's own batches to the sink, drop the others
+                buffer = context.alloc(frame_bytes*batch)
+                for index, (first, count) in enumerate(batches):
+                    advance(first, count, buffer)
+                    if index % world == rank:
+                        context.synchronize()
+                        export.pipe_device_frames(buffer, frame_bytes, count, turbo=False)
+                export.frame = total
             return export.finish()
         finally:
             self._skip_render = False
-            export._device_frames_are_planar = False
             context.synchronize()
-            if gather is None:
-                for pointer in tensors:
-                    context.free(pointer)
+            if buffer is not None:
+                context.free(buffer)
 
     # module ----------------------------------------------------------------------------------------------------
 

@@ -11,6 +11,9 @@ scalars: the scheduler's float64 clock, the PCM chunk schedule, and the per-fram
 
 A scene qualifies when it is made only of the stock modules and nothing overrides `update()`/`pipeline()`;
 anything else runs through the frame loop (`ShaderScene.next`), which produces the same frames.
+
+`FrameTape.export` runs one function per delivery mode (`delivery_mode`): `export_single` (one process), `export_host` and
+`export_device` (sharded over a process group, parallel.py); each renders its batches as sink frames (exporting.SinkBatches).
 """
 from __future__ import annotations
 
@@ -27,7 +30,10 @@ from shaderflow_amd.audio.spectrogram import ShaderSpectrogram
 from shaderflow_amd.audio.waveform import ShaderWaveform, WaveformReducer
 from shaderflow_amd.camera import ShaderCamera
 from shaderflow_amd.dynamics import ShaderDynamics, dynamics_coefficients
+from shaderflow_amd.exporting import SinkBatches
 from shaderflow_amd.module import ShaderModule
+from shaderflow_amd.parallel import (DeviceArray, PeerWindowsUnavailable, RangeTransfer, SdmaTransfer, contiguous_device_export, host_export,
+                                     is_sharded, rank_world, shard_batches, shard_frames, shard_mode)
 from shaderflow_amd.piano import PianoNote
 from shaderflow_amd.scheduler import freewheel_clock
 from shaderflow_amd.shader import ShaderProgram
@@ -230,177 +236,140 @@ class FrameTape:
     # whole export ---------------------------------------------------------------------------------------------------
 
     def export(self, export: "ExportingHelper", turbo: bool = True):
-        """The whole export. With an initialised torch.distributed process group (one process per GPU) the frames are sharded over
-        the ranks and delivered to rank 0, which owns the sink: per-rank read-out into shared memory ("host", the default) or
-        contiguous HBM-resident ranges sent over RCCL ("device") — shaderflow_amd/parallel.py."""
-        from shaderflow_amd.parallel import (DeviceArray, HostDelivery, PeerWindowsUnavailable, RangeTransfer, SdmaTransfer, contiguous_device_export,
-                                             interleaved_host_export, interleaved_runs, is_sharded, rank_world, shard_batches, shard_frames, shard_mode)
+        """The whole export: the tape of every frame, one delivery mode (`delivery_mode`) to move the finished frames to the sink, and the
+        scene's clock left at the last frame's"""
         scene = self.scene
-        total = export.total_frames
-        rank, world = rank_world()
-        self.prepare(total)
+        self.prepare(export.total_frames)
         self.bind_static_uniforms()
         N.check(N.lib().sfx_tape_reset(self.handle))
-        frame_bytes = scene.width*scene.height*3
-        context = scene.context
-        batches = shard_batches(0, total, self.batch)
-
-        def emit_frames(pointer: int, count: int, fence: Optional[int] = None, stride: int = frame_bytes) -> None:
-            export.pipe_device_frames(pointer, stride, count, turbo=turbo, fence=fence)
-
-        mode = shard_mode() if is_sharded() else "single"
-        if mode.startswith("device"):
-            # device modes keep every frame of the export resident in rank 0's HBM (a 60 s 4K clip: 89.6 GB of 288). A clip that does
-            # not fit falls back to host mode — for ALL ranks: rank 0 decides, everybody follows (ADVICE round 2)
-            import torch
-            import torch.distributed as dist
-            verdict = [True]
-            if rank == 0:
-                free, _ = torch.cuda.mem_get_info(context.device)
-                verdict[0] = total*export.frame_bytes + (4 << 30) < free
-            dist.broadcast_object_list(verdict, src=0)
-            if not verdict[0]:
-                if rank == 0:
-                    print(f"shaderflow_amd: {total} frames of {export.frame_bytes >> 20} MiB do not fit rank 0's free device memory: "
-                          f"SHADERFLOW_SHARD={mode} falls back to host mode", flush=True)
-                mode = "host"
+        mode = self.delivery_mode(export)
         try:
             if mode == "single":
-                buffers = [context.alloc(frame_bytes*self.batch) for _ in range(2)]
-                # pixel_format "yuv420p": every batch is converted on the device right behind its render (12 bytes of 8 read and 1.5
-                # written per pixel: microseconds) and the PLANAR frames are what crosses PCIe — half the bytes
-                planar = [context.alloc(export.frame_bytes*self.batch) for _ in range(2)] if export.planar else None
-                export._device_frames_are_planar = export.planar
-
-                def render_batch(which: int, count: int) -> None:
-                    self.render(count, buffers[which])
-                    if planar is not None:
-                        export.to_yuv(buffers[which], planar[which], count)
-                    export.fence(which)
-                try:
-                    # software pipeline: batch b+1 is rendering while the frames of batch b travel to the host
-                    self.build(*batches[0])
-                    render_batch(0, batches[0][1])
-                    for index, (first, count) in enumerate(batches):
-                        if index + 1 < len(batches):
-                            export.render_waits_for_last_read()          # buffers[(index+1) % 2] held batch index-1
-                            self.build(*batches[index + 1])
-                            render_batch((index + 1) % 2, batches[index + 1][1])
-                        emit_frames((planar or buffers)[index % 2], count, fence=index % 2, stride=export.frame_bytes)
-                    # leave the last frame in iFinal, where the frame loop would have left it (scene.screenshot(), scene.py:439-443)
-                    context.synchronize()
-                    last = context.read(buffers[(len(batches) - 1) % 2] + (batches[-1][1] - 1)*frame_bytes, frame_bytes)
-                    last = last.reshape(scene.height, scene.width, 3)
-                    scene._final.texture.texture.write(np.ascontiguousarray(last[::-1] if export.top_down else last))
-                finally:
-                    context.synchronize()
-                    export._device_frames_are_planar = False
-                    for pointer in buffers + (planar or []):
-                        context.free(pointer)
+                self.export_single(export, turbo)
             elif mode == "host":
-                # every rank reads its own batches out over its own PCIe link into shared memory; rank 0's writer thread hands
-                # them to the sink in frame order (parallel.HostDelivery): no collective on the data path. pixel_format "yuv420p":
-                # the rank that rendered a batch converts it (one kernel behind the render) and the PLANAR frames travel — 12.4
-                # instead of 24.9 MB per 4K frame over every link
-                sink_bytes = export.frame_bytes
-                # (a batch and a few: the writer takes the ranks' batches in turn, so a rank needs room for the batch it is producing while its
-                # previous one is being taken — with two batches per rank an 8-rank 4K export asked /dev/shm for 24 GB)
-                slots = int(os.environ.get("SHADERFLOW_SHM_SLOTS", 0)) or max(4, min(self.batch + 8, (4 << 30)//sink_bytes))
-                delivery = HostDelivery(context, world, rank, sink_bytes, slots, export.fileno if rank == 0 else None,
-                                        interleaved_runs(world, batches))
-                buffers = [context.alloc(sink_bytes*self.batch) for _ in range(2)]
-                scratch = context.alloc(frame_bytes*self.batch) if export.planar else None      # (stream-ordered: one RGB batch suffices)
-
-                def render_sink_frames(count: int, buffer: int) -> None:
-                    if scratch is None:
-                        self.render(count, buffer)
-                    else:
-                        self.render(count, scratch)
-                        export.to_yuv(scratch, buffer, count)
-                try:
-                    interleaved_host_export(world, rank, batches, lambda first, count, buffer: self.build(first, count), render_sink_frames, delivery, buffers)
-                finally:
-                    delivery.finish()
-                    context.synchronize()
-                    for pointer in buffers + ([scratch] if scratch is not None else []):
-                        context.free(pointer)
-                export.frame = total
+                self.export_host(export)
             else:
-                # the north star's layout: one contiguous frame range per rank, resident in HBM, sent to rank 0 over RCCL
-                import torch
-                device = torch.device("cuda", context.device)
-                first, last = shard_frames(total, world, rank)
-                frames_here = total if rank == 0 else (last - first)
-                # what is resident, sent and handed to the sink are SINK frames: rgb24, or — pixel_format "yuv420p" — the planar frames
-                # the rendering rank converts behind every batch (half the bytes over every xGMI link and over rank 0's PCIe link)
-                sink_bytes = export.frame_bytes
-                scratch = context.alloc(frame_bytes*self.batch) if export.planar else None
-                export._device_frames_are_planar = export.planar
-                window = None
-                if mode == "device-sdma":
-                    # peer windows: rank 0's buffer is ONE raw allocation (IPC handles name whole allocations), mapped by every rank
-                    if rank == 0:
-                        window = context.alloc(max(1, frames_here)*sink_bytes)
-                        resident = torch.as_tensor(DeviceArray(window, max(1, frames_here)*sink_bytes), device=device)
-                    else:
-                        resident = torch.zeros(max(1, frames_here)*sink_bytes, dtype=torch.uint8, device=device)
-                    torch.cuda.synchronize(device)
-                    try:
-                        transfer = SdmaTransfer(world, rank, context, sink_bytes, window, probe_at=first*sink_bytes,
-                                                probe_bytes=min(4096, max(0, last - first)*sink_bytes))
-                    except PeerWindowsUnavailable as unavailable:
-                        # decided by every rank together (the outcomes were all-gathered): the windows do not work here, the chunks travel
-                        # as RCCL point-to-point calls instead — the same resident buffers, nothing rendered yet
-                        if rank == 0:
-                            print(f"shaderflow_amd: peer windows unavailable ({unavailable}): SHADERFLOW_SHARD=device-sdma falls back to device mode", flush=True)
-                        mode = "device"
-                        transfer = RangeTransfer(world, rank, device)
-                else:
-                    resident = torch.zeros(max(1, frames_here)*sink_bytes, dtype=torch.uint8, device=device)
-                    torch.cuda.synchronize(device)              # the fill runs on torch's stream, the renders on the context's
-                    transfer = RangeTransfer(world, rank, device)
-
-                def render(first_frame, count, view):
-                    if scratch is None:
-                        self.render(count, view.data_ptr())
-                    else:
-                        self.render(count, scratch)
-                        export.to_yuv(scratch, view.data_ptr(), count)
-                    context.synchronize()                       # the context's stream is not torch's: complete before the send
-
-                def emit(view, count):
-                    emit_frames(view.data_ptr(), count, stride=sink_bytes)
-
-                # a rank that raises mid-export must not leave the others waiting for its chunks, nor rank 0's whole-export allocation
-                # and the peers' mappings behind (ADVICE round 3): the outcome is exchanged, then every rank tears down
-                failure: Optional[BaseException] = None
-                try:
-                    contiguous_device_export(world, rank, total, self.batch, sink_bytes, self.build, render, emit, resident, transfer)
-                    export.drain()                              # `resident` outlives the queued reads
-                except BaseException as error:
-                    failure = error
-                    transfer.abort()
-                finally:
-                    export._device_frames_are_planar = False
-                    if scratch is not None:
-                        context.synchronize()
-                        context.free(scratch)
-                    try:
-                        if isinstance(transfer, SdmaTransfer):
-                            import torch.distributed as dist
-                            transfer.close()                        # the peers' mappings of the window
-                            dist.barrier(group=transfer.control)    # every peer has closed its mapping
-                    finally:
-                        if window is not None:                      # (also after the fall-back to RCCL: the frames still live in the raw allocation)
-                            del resident
-                            context.synchronize()
-                            context.free(window)
-                if failure is not None:
-                    raise failure
-                if rank != 0:
-                    export.frame = total
+                self.export_device(export, mode, turbo)
             scene.time, scene.dt, scene.rdt = self.times[-1], self.dts[-1], self.dts[-1]      # clock of the last frame
             return export.finish()
         finally:
-            context.synchronize()
+            scene.context.synchronize()
             self.release()
+
+    def delivery_mode(self, export: "ExportingHelper") -> str:
+        """"single" without a sharded process group, else SHADERFLOW_SHARD's mode. The device modes keep every frame of the export resident
+        in rank 0's HBM (a 60 s 4K clip: 89.6 GB of 288): a clip that does not fit falls back to host mode — for ALL ranks: rank 0
+        decides, everybody follows"""
+        if not is_sharded():
+            return "single"
+        mode = shard_mode()
+        if not mode.startswith("device"):
+            return mode
+        import torch
+        import torch.distributed as dist
+        rank, total = rank_world()[0], export.total_frames
+        verdict = [True]
+        if rank == 0:
+            verdict[0] = total*export.frame_bytes + (4 << 30) < torch.cuda.mem_get_info(self.scene.context.device)[0]
+        dist.broadcast_object_list(verdict, src=0)
+        if verdict[0]:
+            return mode
+        if rank == 0:
+            print(f"shaderflow_amd: {total} frames of {export.frame_bytes >> 20} MiB do not fit rank 0's free device memory: "
+                  f"SHADERFLOW_SHARD={mode} falls back to host mode", flush=True)
+        return "host"
+
+    def export_single(self, export: "ExportingHelper", turbo: bool) -> None:
+        """One process: a software pipeline over two batch buffers — batch b+1 renders while the frames of batch b travel to the host"""
+        batches = shard_batches(0, export.total_frames, self.batch)
+        sink = SinkBatches(export, self.batch)
+
+        def render(index: int) -> None:
+            first, count = batches[index]
+            self.build(first, count)
+            sink.render(sink.buffers[index % 2], count, self.render)
+            export.fence(index % 2)
+        try:
+            render(0)
+            for index, (_, count) in enumerate(batches):
+                if index + 1 < len(batches):
+                    export.render_waits_for_last_read()          # buffers[(index+1) % 2] held batch index-1
+                    render(index + 1)
+                export.pipe_device_frames(sink.buffers[index % 2], export.frame_bytes, count, turbo=turbo, fence=index % 2)
+            # leave the last frame in iFinal, where the frame loop would have left it (scene.screenshot())
+            self.scene.write_final(sink.last_rgb, export.top_down)
+        finally:
+            sink.close()
+
+    def export_host(self, export: "ExportingHelper") -> None:
+        """Every rank reads its own batches out into shared memory, rank 0's writer thread hands them to the sink in frame order
+        (parallel.host_export). The ring holds a batch and a few frames per rank: room for the batch a rank produces while its previous
+        one is being taken (two batches per rank asked /dev/shm for 24 GB at 8 ranks of 4K)"""
+        rank, world = rank_world()
+        batches = shard_batches(0, export.total_frames, self.batch)
+        host_export(export, world, rank, batches, self.batch, max(4, min(self.batch + 8, (4 << 30)//export.frame_bytes)),
+                    lambda first, count, buffer: self.build(first, count), self.render)
+
+    def export_device(self, export: "ExportingHelper", mode: str, turbo: bool) -> None:
+        """The north star's layout: one contiguous frame range per rank, resident in HBM, sent to rank 0 — over RCCL ("device"), or copied
+        into rank 0's buffer through peer windows ("device-sdma", which falls back to RCCL for the whole group when the windows fail)"""
+        import torch
+        import torch.distributed as dist
+        context = self.scene.context
+        rank, world = rank_world()
+        total = export.total_frames
+        device = torch.device("cuda", context.device)
+        first, last = shard_frames(total, world, rank)
+        frames_here = total if rank == 0 else (last - first)
+        sink_bytes = export.frame_bytes
+        window, size = None, max(1, frames_here)*sink_bytes
+        if mode == "device-sdma" and rank == 0:
+            # peer windows: rank 0's buffer is ONE raw allocation (IPC handles name whole allocations), mapped by every rank
+            window = context.alloc(size)
+            resident = torch.as_tensor(DeviceArray(window, size), device=device)
+        else:
+            resident = torch.zeros(size, dtype=torch.uint8, device=device)
+        torch.cuda.synchronize(device)                  # the fill runs on torch's stream, the renders on the context's
+        if mode == "device-sdma":
+            try:
+                transfer = SdmaTransfer(world, rank, context, sink_bytes, window, probe_at=first*sink_bytes,
+                                        probe_bytes=min(4096, max(0, last - first)*sink_bytes))
+            except PeerWindowsUnavailable as unavailable:
+                # decided by every rank together (the outcomes were all-gathered): the windows do not work here, the chunks travel
+                # as RCCL point-to-point calls instead — the same resident buffers, nothing rendered yet
+                if rank == 0:
+                    print(f"shaderflow_amd: peer windows unavailable ({unavailable}): SHADERFLOW_SHARD=device-sdma falls back to device mode", flush=True)
+                transfer = RangeTransfer(world, rank, device)
+        else:
+            transfer = RangeTransfer(world, rank, device)
+        sink = SinkBatches(export, self.batch, count=0)    # the resident buffers are the sink frames' home
+
+        def render(first_frame, count, view):
+            sink.render(view.data_ptr(), count, self.render)
+            context.synchronize()                       # the context's stream is not torch's: complete before the send
+        emit = lambda view, count: export.pipe_device_frames(view.data_ptr(), sink_bytes, count, turbo=turbo)
+
+        # a rank that raises mid-export must not leave the others waiting for its chunks, nor rank 0's whole-export allocation
+        # and the peers' mappings behind (ADVICE round 3): the outcome is exchanged, then every rank tears down
+        failure: Optional[BaseException] = None
+        try:
+            contiguous_device_export(world, rank, total, self.batch, sink_bytes, self.build, render, emit, resident, transfer)
+            export.drain()                              # `resident` outlives the queued reads
+        except BaseException as error:
+            failure = error
+            transfer.abort()
+        finally:
+            sink.close()
+            try:
+                if isinstance(transfer, SdmaTransfer):
+                    transfer.close()                        # the peers' mappings of the window
+                    dist.barrier(group=transfer.control)    # every peer has closed its mapping
+            finally:
+                if window is not None:                      # (also after the fall-back to RCCL: the frames still live in the raw allocation)
+                    del resident
+                    context.synchronize()
+                    context.free(window)
+        if failure is not None:
+            raise failure
+        if rank != 0:
+            export.frame = total

@@ -7,8 +7,8 @@ expects users to write (shaderflow/module.py:55-116) — took the frame loop (`S
 a host round trip, the numpy DynamicNumber steps of every bin and the texture writes of the spectrogram and the waveform.
 
 User code does not change the audio of frame k unless it writes to the audio modules. So here the device still builds the audio
-state of a batch of frames exactly as in `FrameTape.export` (STFT, filterbank, the DynamicNumber scans, the waveform rows), with one
-addition: a per-frame snapshot of every DynamicNumber's whole state (`sfx_tape_snapshot`, read back once per batch into pinned
+state of a batch of frames exactly as an export's `FrameTape.build` does (STFT, filterbank, the DynamicNumber scans, the waveform rows),
+with one addition: a per-frame snapshot of every DynamicNumber's whole state (`sfx_tape_snapshot`, read back once per batch into pinned
 memory). Then, frame by frame, the modules update in the frame loop's order (scene.py:456-479), except that the `update()` of each
 audio module is replaced, at its own place in that order, by a *mirror step*: it sets what that `update()` would have left on the
 host — `audio.tell` (the chunk reader itself still runs), the full state of `audio.volume`, `audio.std` and `spectrogram.dynamics`
@@ -211,20 +211,13 @@ class TapeLoop:
         self.live = False
         export.drain()
         if self.last_frame is not None:
-            scene._final.texture.texture.write(self.read_last())   # iFinal holds the previous frame, as in the frame loop
+            scene.write_final(self.last_frame, self.top_down)    # iFinal holds the previous frame, as in the frame loop
         scene.__dict__.pop("screenshot", None)
         # the textures the mirror did not write: as the last mirrored update() would have left them
         if self.spectrogram is not None and self.expected.get(id(self.spectrogram)) is not None:
             self.spectrogram.texture.write(np.ascontiguousarray(self.columns))
         if self.waveform is not None and self.wave_tell is not None:
             self.waveform.texture.write(self.waveform.rows([self.wave_tell])[0])
-
-    def read_last(self) -> np.ndarray:
-        """The last frame rendered from the tape, rows bottom-up (iFinal's layout)"""
-        scene = self.scene
-        scene.context.synchronize()
-        frame = scene.context.read(self.last_frame, self.frame_bytes).reshape(scene.height, scene.width, 3)
-        return np.ascontiguousarray(frame[::-1] if self.top_down else frame)
 
     # the loop ---------------------------------------------------------------------------------------------------------------------
 
@@ -271,12 +264,17 @@ class TapeLoop:
         self.values = tape.spectrogram.spectrogram_bins*self.audio.channels
         if self.spectrogram is not None:
             self.columns = np.zeros((self.spectrogram.spectrogram_bins, self.spectrogram.length_samples, self.audio.channels), np.float32)
-        self.frame_bytes = frame_bytes = scene.width*scene.height*3
+        frame_bytes = scene.width*scene.height*3
         batches = shard_batches(0, total, tape.batch)
         buffers = [context.alloc(frame_bytes*tape.batch) for _ in range(2)]
         self.last_frame: Optional[int] = None
         original_screenshot = scene.screenshot
-        scene.screenshot = lambda: (np.flipud(self.read_last()) if self.last_frame is not None else original_screenshot())
+
+        def screenshot() -> np.ndarray:                          # the last frame rendered, through iFinal as in the frame loop
+            if self.last_frame is not None:
+                scene.write_final(self.last_frame, self.top_down)
+            return original_screenshot()
+        scene.screenshot = screenshot
         shader, ssaa_x1000 = scene.shader, int(round(scene.ssaa*1000))
         time, dt = 0.0, 0.0
         self.camera_seen, self.camera_identity = None, True
@@ -310,7 +308,7 @@ class TapeLoop:
                         self.last_frame = target
                         self.frames_mirrored += 1
                         # read out frame by frame, as the frame loop does: the host's python of the next frames overlaps the copy
-                        export.pipe_device(target, turbo=turbo)
+                        export.pipe_device(target, rgb=True, turbo=turbo)
                         export.update()
                     else:
                         for program in self.programs:
@@ -323,7 +321,7 @@ class TapeLoop:
                     tape.build(*batches[index + 1])               # on the tape's stream, beside this batch's renders
                     self.read_state(batches[index + 1][1])
             if self.live and self.last_frame is not None:
-                scene._final.texture.texture.write(self.read_last())   # iFinal holds the last frame, as the frame loop leaves it
+                scene.write_final(self.last_frame, self.top_down)  # iFinal holds the last frame, as the frame loop leaves it
             return export.finish()                              # (the scene's clock stays that of the last frame, as in FrameTape)
         finally:
             scene.__dict__.pop("screenshot", None)
