@@ -246,41 +246,99 @@ __global__ __launch_bounds__(256) void k_waveform_rows(const float* __restrict__
 
 // ---- K5 ---------------------------------------------------------------------------------------------------
 // One block per frame over channels*n samples: volume target = 2*sqrt(mean(x²))*sqrt(2) and std target
-// = sqrt(mean((x-mean)²)), rounded to float32 at the points numpy rounds (audio/module.py:74-75,457-458).
+// = sqrt(mean((x-mean)²)), with numpy's float32 arithmetic (audio/module.py:74-75,457-458): its means are float32 PAIRWISE sums
+// (pairwise_sum_FLOAT: runs of at most 128 values summed with eight accumulators, longer runs split in two at a multiple of 8 and
+// the halves added), so the targets are the reference's bits. They have to be: the DynamicNumbers these targets drive stop moving
+// when |target - value| < 1e-6 (dynamics.py:222-225), and a target one ulp away flips that branch — on the benchmark's sweep the
+// volume's trajectory left the reference's for good at frame 803 when the sums were taken in float64.
+// The tree of a sum is fixed by its length: thread 0 lists the leaf runs depth first, every thread sums leaves, thread 0 adds the
+// leaves back up the same tree (no recursion on the device: an explicit stack, depth < 32).
+constexpr int PAIRWISE_LEAVES = 1024;                               // 8 820 values (0.1 s of 44.1 kHz stereo) have 128 leaves
+struct PairwiseScratch { int start[PAIRWISE_LEAVES]; int len[PAIRWISE_LEAVES]; float part[PAIRWISE_LEAVES]; int leaves; };
+
+template <class At>
+__device__ float pairwise_leaf(int start, int n, const At& at) {     // n <= 128
+    if (n < 8) {
+        float res = 0.0f;
+        for (int i = 0; i < n; i++) res = res + at(start + i);
+        return res;
+    }
+    float r[8];
+    for (int j = 0; j < 8; j++) r[j] = at(start + j);
+    int i;
+    for (i = 8; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; j++) r[j] = r[j] + at(start + i + j);
+    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res = res + at(start + i);
+    return res;
+}
+
+// numpy's pairwise sum of at(first) ... at(first + n - 1), called by every thread of the block; the result is valid in thread 0 only
+template <class At>
+__device__ float pairwise_sum_block(int first, int n, const At& at, PairwiseScratch& sh) {
+    struct Node { int s, l, stage; float lo; };
+    if (threadIdx.x == 0) {                                           // the leaves, left to right
+        Node st[32]; int top = 0, leaves = 0;
+        st[0] = {first, n, 0, 0.0f};
+        while (top >= 0) {
+            const Node f = st[top--];
+            if (f.l <= 128) {
+                if (leaves < PAIRWISE_LEAVES) { sh.start[leaves] = f.s; sh.len[leaves] = f.l; }
+                leaves++;
+                continue;
+            }
+            int n2 = f.l/2; n2 -= n2 % 8;
+            st[++top] = {f.s + n2, f.l - n2, 0, 0.0f};
+            st[++top] = {f.s, n2, 0, 0.0f};
+        }
+        sh.leaves = leaves;
+    }
+    __syncthreads();
+    const bool listed = sh.leaves <= PAIRWISE_LEAVES;                 // (longer sums: thread 0 sums the leaves itself below)
+    if (listed)
+        for (int i = threadIdx.x; i < sh.leaves; i += blockDim.x) sh.part[i] = pairwise_leaf(sh.start[i], sh.len[i], at);
+    __syncthreads();
+    float result = 0.0f;
+    if (threadIdx.x == 0) {                                           // lo + hi up the tree, in the order of the recursion
+        Node st[32]; int top = 0, leaf = 0;
+        float ret = 0.0f;
+        st[0] = {first, n, 0, 0.0f};
+        while (top >= 0) {
+            Node& f = st[top];
+            if (f.l <= 128) { ret = listed ? sh.part[leaf] : pairwise_leaf(f.s, f.l, at); leaf++; top--; continue; }
+            int n2 = f.l/2; n2 -= n2 % 8;
+            if (f.stage == 0) { f.stage = 1; st[top + 1] = {f.s, n2, 0, 0.0f}; top++; }
+            else if (f.stage == 1) { f.lo = ret; f.stage = 2; st[top + 1] = {f.s + n2, f.l - n2, 0, 0.0f}; top++; }
+            else { ret = f.lo + ret; top--; }
+        }
+        result = ret;
+    }
+    __syncthreads();                                                  // (sh is reused by the next sum)
+    return result;
+}
+
 __global__ __launch_bounds__(256) void k_volume_std(const float* __restrict__ pcm, long total, int channels,
                                                     const long* __restrict__ tell, int n, float* __restrict__ out) {
-    __shared__ double red[2][4];
-    __shared__ double mean_sh;
+    __shared__ PairwiseScratch sh;
     const int frame = blockIdx.x;
     const long first = tell[frame] - n - 1;
     const int count = n*channels;
-    double s1 = 0.0, s2 = 0.0;
-    for (int e = threadIdx.x; e < count; e += 256) {
-        const double x = (double)stream_at(pcm, total, e / n, first + (e % n));
-        s1 += x; s2 += x*x;
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
+    // the last n samples of every channel as one (channels, n) float32 array, element e = channel e/n, sample e%n
+    auto x = [&](int e) { return stream_at(pcm, total, e / n, first + (e % n)); };
+    const float mean_sq = pairwise_sum_block(0, count, [&](int e) { const float v = x(e); return v*v; }, sh)/(float)count;
+    // np.std: the mean over the (channels, n) array is the channels' pairwise sums added in row order, then the pairwise sum of (x - mean)²
+    float sum = 0.0f;
+    for (int c = 0; c < channels; c++) sum = sum + pairwise_sum_block(c*n, n, x, sh);
+    __shared__ float mean_sh;
+    if (threadIdx.x == 0) mean_sh = sum/(float)count;
     __syncthreads();
+    const float mean = mean_sh;
+    const float var = pairwise_sum_block(0, count, [&](int e) { const float d = x(e) - mean; return d*d; }, sh)/(float)count;
     if (threadIdx.x == 0) {
-        const double sum = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        const double sq = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        const float rms = sqrtf((float)(sq/(double)count));
+        const float rms = sqrtf(mean_sq);
         out[2*frame] = (2.0f*rms)*(float)1.4142135623730951;
-        mean_sh = (double)(float)(sum/(double)count);               // numpy's arrmean is float32
+        out[2*frame + 1] = sqrtf(var);
     }
-    __syncthreads();
-    const double mean = mean_sh;
-    double q = 0.0;
-    for (int e = threadIdx.x; e < count; e += 256) {
-        const float d = stream_at(pcm, total, e / n, first + (e % n)) - (float)mean;   // x - arrmean in float32
-        q += (double)(d*d);
-    }
-    q = wave_sum(q);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = q;
-    __syncthreads();
-    if (threadIdx.x == 0) out[2*frame + 1] = sqrtf((float)((red[0][0] + red[0][1] + red[0][2] + red[0][3])/(double)count));
 }
 
 // ---- K3 ---------------------------------------------------------------------------------------------------

@@ -321,7 +321,9 @@ __device__ __forceinline__ uint32_t visualizer_fast_post(const RenderArgs& a, in
 //   * sm = smoothstep(length(uv)/20) moves by < 1e-5 of itself over a pixel: nothing.
 // A tile takes the pixel tier when (ring + flash bounds)*255 < 0.4 LSB: every supersample's texel then differs from its own evaluation by less
 // than half an LSB BEFORE quantisation, so after final.glsl's mean a frame differs from the per-sample kernel's by at most 1 LSB (in practice
-// by one in a few per cent of the values, none further: tests/test_gpu_fullsize.py compares both with the oracle).
+// by one in a few per cent of the values, none further: tests/test_gpu_fullsize.py compares the two kernels). Against the oracle the bound is
+// the contract's, max <= 1 LSB on every value: tests/test_gpu_tape_parity.py (test_c3_pixel_tier_within_one_lsb_*) holds whole frames with
+// the tier on to it, on flashes and spectra that put many tiles near the budget, and the tape's frames of the benchmark clip likewise.
 struct PixelGains { float A, w; };          // texel_c = (sum_c + space_c*w)*A*vignette, space = (1, 11, 26) (:9; A carries the 255, w the sm/(1 - sm))
 __device__ __forceinline__ PixelGains visualizer_pixel_gains(const RenderArgs& a, const VisTables& t, int frame, const VisualizerConsts& c, const float4 pc1, const float4 pr1) {
     const float norm = 1.0f/(255.0f*10.0f*8.0f);

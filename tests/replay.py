@@ -112,12 +112,25 @@ def dynamics_scene(background, w, h, fps, frames, pick, threads=8):
     return np.stack([out[k] for k in pick])
 
 
-def audio_scene(fragment, pcm, samplerate, background, w, h, ssaa, subsample, fps, frames, pick=None, high=14000.0,
-                waveform_smooth=True, threads=8, screens=None, duration=None):
-    """Visualizer / MusicBars / Waveform (demo.py:157-205): the audio tape of sfo_audio.c feeding the fragments of sfo_pixel.c.
-    `high`: upper note of from_notes (14 kHz Visualizer, 18 kHz MusicBars); `screens`: a dict that receives the supersampled iScreen
-    of every picked frame (the edge-aware bound of the full-size tests needs the samples); `duration`: iDuration when the export is
-    longer than the `frames` replayed here"""
+class OracleTape:
+    """The oracle's audio tape of every frame (sfo_audio.c; the reference's ShaderAudio / ShaderSpectrogram / ShaderWaveform updates):
+    the clock, the spectrogram's unsmoothed filterbank targets and its smoothed columns (frames, bins, 2), the waveform rows
+    (frames, points, 2), the loudness targets and the volume / std DynamicNumbers. Columns and rows hold the bytes the textures get
+    (the reference writes its (2, bins) arrays into (bins, 1, 2) textures), the device tape's layout (FrameTape.read)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def frame(self, k: int) -> dict:
+        """Frame k's per-frame values as oracle_tape_frame takes them"""
+        return dict(iTime=self.times[k], iTau=self.tau[k], iDeltatime=self.dts[k], iFrame=round(self.times[k]*self.fps),
+                    iAudioVolume=self.volume[k], iAudioVolumeIntegral=self.integral[k], iAudioSTD=self.std[k],
+                    iSpectrogram=self.columns[k], iWaveform=self.rows[k])
+
+
+def oracle_audio_tape(pcm, samplerate, fps, frames, high=14000.0, duration=None, points=180) -> OracleTape:
+    """The audio half of audio_scene for every frame. `high`: upper note of from_notes (14 kHz Visualizer, 18 kHz MusicBars);
+    `duration`: the export's runtime (iTau) when it is longer than the `frames` replayed here"""
     planar = np.ascontiguousarray(pcm.T)
     times, dts, rdts = O.clock(fps, frames)
     runtime = frames/fps if duration is None else duration
@@ -125,27 +138,60 @@ def audio_scene(fragment, pcm, samplerate, background, w, h, ssaa, subsample, fp
     fmin, fmax, bins = O.from_notes(O.lib().sfo_note_of_frequency(20.0, 440.0), O.lib().sfo_note_of_frequency(high, 440.0), True)
     indptr, indices, data = O.filterbank(0, 0, fmin, fmax, bins, 12, samplerate)
     volume, std, spec = O.DynF64(0.0, 2, 1, 0, integrate=True), O.DynF64(0.0, 10, 1, 0), O.DynF32(2*bins, 4, 1, 0)
-    bg = O.make_texture(np.flipud(background)) if background is not None else None
-    pick = list(range(frames)) if pick is None else list(pick)
-    out = {}
+    chunk = max(1, int(3*samplerate/points))
+    targets, columns = np.zeros((frames, bins, 2), np.float32), np.zeros((frames, bins, 2), np.float32)
+    rows = np.zeros((frames, points, 2), np.float32)
+    loudness = np.zeros((frames, 2), np.float64)
+    values = np.zeros((frames, 3), np.float64)
     for k in range(frames):
         vt, st = O.volume_std(planar, int(tell[k]), int(0.1*samplerate))
         volume.step(vt, abs(dts[k])); std.step(st, abs(dts[k]))
         target = O.csr_dot(indptr, indices, data, O.fft_power(planar, int(tell[k])))
-        column = spec.step(target.ravel(), abs(dts[k])).copy()
-        if k not in pick:
-            continue
-        row = O.waveform_row(planar, int(tell[k]), max(1, int(3*samplerate/180)), 180)
-        u = O.default_uniforms(w, h, iTime=times[k], iTau=(times[k]/runtime) % 1.0, iDuration=runtime, iDeltatime=dts[k],
-                               iSSAA=float(ssaa), iFramerate=fps, iFrame=round(times[k]*fps), iSubsample=subsample,
-                               iAudioVolume=volume.value.value, iAudioVolumeIntegral=volume.integral.value, iAudioSTD=std.value.value,
-                               iSpectrogramLength=1, iSpectrogramBins=bins, iWaveformLength=180)
-        tex = {"iSpectrogram": O.make_texture(column.reshape(bins, 1, 2), "nearest", True, False),
-               "iWaveform": O.make_texture(row.reshape(1, 180, 2), "linear" if waveform_smooth else "nearest", False, False)}
-        if bg is not None:
-            tex["background"] = bg
-        screen = O.render(fragment, u, tex, int(w*ssaa), int(h*ssaa), threads=threads)
+        columns[k] = spec.step(target.ravel(), abs(dts[k])).reshape(bins, 2)
+        targets[k] = target.reshape(bins, 2)
+        rows[k] = O.waveform_row(planar, int(tell[k]), chunk, points).reshape(points, 2)
+        loudness[k] = (vt, st)
+        values[k] = (volume.value.value, volume.integral.value, std.value.value)
+    return OracleTape(fps=fps, bins=bins, times=times, dts=dts, tell=tell, tau=[(t/runtime) % 1.0 for t in times],
+                      targets=targets, columns=columns, rows=rows, loudness=loudness,
+                      volume=values[:, 0], integral=values[:, 1], std=values[:, 2])
+
+
+def oracle_tape_frame(fragment, values: dict, static: dict, w, h, ssaa, subsample, background=None, waveform_smooth=True,
+                      threads=8, screen=False):
+    """The pixel half of audio_scene: one frame of `fragment` from per-frame `values` (OracleTape.frame, or the same keys read from the
+    device's tape: iTime, iTau, iDeltatime, iFrame, iAudioVolume, iAudioVolumeIntegral, iAudioSTD, iSpectrogram (bins, 2) and
+    iWaveform (points, 2)) and the export's `static` uniforms (iDuration, iFramerate). `background`: an oracle texture.
+    Returns the resolved frame, or (frame, iScreen) with `screen`."""
+    column, row = np.ascontiguousarray(values["iSpectrogram"], np.float32), np.ascontiguousarray(values["iWaveform"], np.float32)
+    bins, points = column.shape[0], row.shape[0]
+    scalars = {name: value for name, value in values.items() if name not in ("iSpectrogram", "iWaveform")}
+    u = O.default_uniforms(w, h, **scalars, **static, iSSAA=float(ssaa), iSubsample=subsample,
+                           iSpectrogramLength=1, iSpectrogramBins=bins, iWaveformLength=points)
+    tex = {"iSpectrogram": O.make_texture(column.reshape(bins, 1, 2), "nearest", True, False),
+           "iWaveform": O.make_texture(row.reshape(1, points, 2), "linear" if waveform_smooth else "nearest", False, False)}
+    if background is not None:
+        tex["background"] = background
+    samples = O.render(fragment, u, tex, int(w*ssaa), int(h*ssaa), threads=threads)
+    frame = O.resolve(samples, w, h, subsample, threads=threads)
+    return (frame, samples) if screen else frame
+
+
+def audio_scene(fragment, pcm, samplerate, background, w, h, ssaa, subsample, fps, frames, pick=None, high=14000.0,
+                waveform_smooth=True, threads=8, screens=None, duration=None):
+    """Visualizer / MusicBars / Waveform (demo.py:157-205): the audio tape of sfo_audio.c feeding the fragments of sfo_pixel.c —
+    oracle_audio_tape, then oracle_tape_frame for every picked frame. `screens`: a dict that receives the supersampled iScreen of every
+    picked frame (the edge-aware bound of the full-size tests needs the samples); `duration`: iDuration when the export is longer than
+    the `frames` replayed here"""
+    tape = oracle_audio_tape(pcm, samplerate, fps, frames, high=high, duration=duration)
+    static = dict(iDuration=frames/fps if duration is None else duration, iFramerate=fps)
+    bg = O.make_texture(np.flipud(background)) if background is not None else None
+    pick = list(range(frames)) if pick is None else list(pick)
+    out = []
+    for k in pick:
+        frame, screen = oracle_tape_frame(fragment, tape.frame(k), static, w, h, ssaa, subsample, background=bg,
+                                          waveform_smooth=waveform_smooth, threads=threads, screen=True)
         if screens is not None:
             screens[k] = screen
-        out[k] = O.resolve(screen, w, h, subsample, threads=threads)
-    return np.stack([out[k] for k in pick])
+        out.append(frame)
+    return np.stack(out)
