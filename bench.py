@@ -2,8 +2,8 @@
 """
 bench.py — frames/s of the music-visualizer export path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node N … bench.py --gpus N --steps K --warmup W
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node N … bench.py --gpus N --steps K --warmup W [--full]
 
 Workload (BASELINE.json metric config, `configs[2]`): Visualizer scene, 3840x2160, 2x SSAA, subsample 2, 60 fps,
 synthetic 44.1 kHz stereo sine sweep, synthetic 1920x1080 background; inputs resident in HBM before timing.
@@ -20,18 +20,24 @@ step i+1. `value` = frames of all ranks / max-over-ranks time: frames resident i
 Prints ONE JSON line (rank 0): value = frames/s of the whole job, plus
   roofline     — the dominant kernel (named by the library: sfx_last_kernel). It is bound by VALU issue and LDS bandwidth, not
                  by HBM, so `bound` is "valu": achieved = instruction lanes per second from the launch time measured HERE (HIP
-                 events on the launch stream inside the timed region) x the instructions per supersample rocprofv3 counts IN THIS
-                 RUN (five short children of this script under `rocprofv3 --kernel-trace --pmc`, one per pass: the VALU class
-                 counters, GRBM_GUI_ACTIVE, FETCH_SIZE, WRITE_SIZE, the LDS and wave-state counters; `--no-live-counters` skips
-                 them). Where the profiler is missing or a pass fails the tracked profile of THIS build stands in (profiles/*.json,
-                 checked against the library's source fingerprint — stale counters are dropped, loudly);
-                 `roofline.counters_from` says which it was. The HBM view the contract asks for sits beside it under `hbm`: algorithmic bytes over
-                 the same launch time, and `traffic` = measured FETCH_SIZE + WRITE_SIZE per launch from the same profile.
+                 events on the launch stream inside the timed region) x the instructions per supersample of the tracked profile of
+                 THIS build (profiles/*.json, checked against the library's source fingerprint — stale counters are dropped,
+                 loudly), or with --full the counts rocprofv3 takes IN THIS RUN; `roofline.counters_from` says which it was. The
+                 HBM view the contract asks for sits beside it under `hbm`: algorithmic bytes over the same launch
+                 time, and `traffic` = measured FETCH_SIZE + WRITE_SIZE per launch from the same profile.
+
+A plain run does only what `value` and `ms_per_step` need: set-up, the W + K steps, --dump-outputs, the line. --full adds what
+takes runs or legs of its own (--no-live-counters, --no-cpu-baseline and --no-export leave out a part of it):
+  live counters — five short children of this script under `rocprofv3 --kernel-trace --pmc`, one per pass: the VALU class
+                 counters, GRBM_GUI_ACTIVE, FETCH_SIZE, WRITE_SIZE, the LDS and wave-state counters. Where the profiler is
+                 missing or a pass fails the tracked profile stands.
   cpu_baseline — the oracle (kind "port": plain-C restatement of the reference path) on the host cores of this box, all cores
                  and one thread, over bands of three frames of the same workload; rank 0 at N = 1 only, AFTER the GPU legs.
                  `llvmpipe_container`: the reference itself (numpy FFT + its GLSL on Mesa llvmpipe), measured in the build container.
   export_host  — the same frames through a real export to /dev/null including the read-out to host memory (N = 1: pinned ring
                  + writer thread; N > 1: every rank over its own PCIe link into the shared-memory ring, "host" mode).
+  yuv420p legs — N > 1: every transport once more with planar yuv420p frames (`value_yuv420p`); a plain run times the rgb24 legs
+                 its `value` is the faster of.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes the frames its last timed step rendered as DIR/*.npy (dump_outputs()). The
 inputs are synthetic and seeded, so two builds run with the same arguments can be compared output for output.
@@ -78,11 +84,14 @@ def parse_args():
                    help="visualizer = the metric's scene; bars = MusicBars, waveform = Waveform, basic = Basic (default.glsl): light fragments")
     p.add_argument("--camera-zoom", type=float, default=1.0,
                    help="tier analysis of the light fragments (tools/experiments/basic_tiers.sh): the camera's zoom; the metric's runs leave it at 1")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-export", action="store_true", help="skip the host-inclusive export measurement")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what takes runs or legs of its own: the live counters, the CPU baseline, the host-inclusive export and, "
+                        "N > 1, the yuv420p legs (a plain run times the steps and prints the line)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-export", action="store_true", help="with --full: skip the host-inclusive export measurement")
     p.add_argument("--no-live-counters", action="store_true",
-                   help="do not collect the dominant kernel's instruction counters in this run (two short rocprofv3 children of this script); "
-                        "the roofline then rests on the tracked profile alone")
+                   help="with --full: do not collect the dominant kernel's instruction counters in this run (five short rocprofv3 children of "
+                        "this script); the roofline then rests on the tracked profile alone")
     p.add_argument("--cpu-seconds", type=float, default=18.0, help="budget of the CPU baseline (all cores + one thread)")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write the frames of the last timed step (rank 0's) to DIR/*.npy: float32 / float64, at most 64 MB "
@@ -224,7 +233,7 @@ def live_counters(args, kernel: str | None) -> dict | None:
             command = ["rocprofv3", "--kernel-trace", "--pmc", *names, "-f", "csv", "-d", str(out), "-o", "pmc", "--",
                        sys.executable, str(Path(__file__).resolve()), "--steps", "1", "--warmup", "1", "--frames-per-step", str(frames),
                        "--width", str(args.width), "--height", str(args.height), "--ssaa", str(args.ssaa), "--scene", args.scene,
-                       "--camera-zoom", str(args.camera_zoom), "--no-cpu-baseline", "--no-export", "--no-live-counters"]
+                       "--camera-zoom", str(args.camera_zoom)]     # (a plain run: no counters, baseline or export of its own)
             try:                                                     # (a session of its own: a pass that overruns is ended with its whole process group)
                 child = subprocess.Popen(command, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=dict(os.environ, TMPDIR="/tmp"),
                                          cwd=str(ROOT), start_new_session=True)
@@ -547,7 +556,7 @@ def main() -> None:
     #   "p2p"   grouped point-to-point calls of the process group's backend (RCCL over xGMI: the north star's gather; gloo in tests)
     #   "sdma"  peer copies through IPC windows on SDMA engines NAMED through HSA (shaderflow_amd/parallel.py SdmaTransfer, sfx_peer_*)
     # and two payloads: the rgb24 frames (the reference's byte stream: `value`) and — converted on the rank that rendered them —
-    # planar yuv420p, half the bytes per link (`yuv420p` beside it). SHADERFLOW_SHARD=device|device-sdma pins the transport.
+    # planar yuv420p, half the bytes per link (`yuv420p` beside it, --full only). SHADERFLOW_SHARD=device|device-sdma pins the transport.
     from shaderflow_amd.parallel import DeviceArray
     os.environ.setdefault("SHADERFLOW_COPY_TIMEOUT", "30")          # an engine copy that never completes is reported after 30 s (capi_readout.hip EngineLanes::finish), not waited for
     pinned = os.environ.get("SHADERFLOW_SHARD", "").strip().lower()
@@ -731,7 +740,7 @@ def main() -> None:
     else:
         for transport in transports:
             legs.append(run_leg(transport, False))
-        for transport in transports:
+        for transport in (transports if args.full else []):
             legs.append(run_leg(transport, True))
     if args.dump_outputs and rank == 0:
         # every leg renders the same frame ranges: the last timed step of the last leg is what a caller of step() was handed
@@ -770,9 +779,9 @@ def main() -> None:
     value = frames_total/elapsed if elapsed > 0 else float("nan")
     tape.release()
 
-    # ---- the same frames through a real export, read-out to host memory included (/dev/null sink) ----
+    # ---- --full: the same frames through a real export, read-out to host memory included (/dev/null sink) ----
     export = None
-    if not args.no_export:
+    if args.full and not args.no_export:
         scene2 = build_scene(prepared=False)
         # the whole clip when the default workload is measured (60 s = 3 600 frames: the north star's export), a bounded piece otherwise
         whole_clip = (w, h, s) == (3840, 2160, 2) and args.steps >= 8
@@ -813,7 +822,7 @@ def main() -> None:
 
     # the CPU baseline LAST: the GPU legs above are what the driver's utilisation sampler should see first
     baseline = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and args.scene == "visualizer":
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and args.scene == "visualizer":
         baseline = cpu_baseline(args, pcm, background)
         if (w, h, s) == (3840, 2160, 2):
             baseline["llvmpipe_container"] = REFERENCE_LLVMPIPE
@@ -830,8 +839,8 @@ def main() -> None:
         counters_from = str(PROFILE.relative_to(ROOT)) if counters else None
         profiled = any(key.startswith(("ROCPROF", "ROCP_")) for key in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")   # this run IS a profiler's child
         dominant_share = other_kernels = None
-        if world == 1 and not distributed and not profiled and not args.no_live_counters:
-            # EVERY configuration's run measures its own counters (round 5, missing 3): the dominant kernel by traced
+        if args.full and world == 1 and not distributed and not profiled and not args.no_live_counters:
+            # EVERY configuration's --full run measures its own counters (round 5, missing 3): the dominant kernel by traced
             # GPU time; the tracked profile fills in what a pass did not give (C3 only: it is the profile of C3's kernel)
             live = live_counters(args, kernel)
             if live:

@@ -210,7 +210,7 @@ def test_bench_goes_on_without_a_transport_that_fails_its_preflight():
     env = dict(os.environ, SHADERFLOW_DIST_BACKEND="gloo", SHADERFLOW_BENCH_INJECT="sdma-preflight")
     command = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), str(root/"bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--frames-per-step", "4", "--width", "384", "--height", "216", "--no-export"]
+               "--frames-per-step", "4", "--width", "384", "--height", "216", "--full", "--no-export"]
     out = subprocess.run(command, capture_output=True, text=True, timeout=360, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     record = json.loads([line for line in out.stdout.splitlines() if line.startswith("{")][-1])
@@ -231,7 +231,7 @@ def test_bench_with_two_ranks_prints_one_line_for_the_whole_job():
     env = dict(os.environ, SHADERFLOW_DIST_BACKEND="gloo")
     command = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), str(root/"bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--frames-per-step", "4", "--width", "384", "--height", "216"]
+               "--frames-per-step", "4", "--width", "384", "--height", "216", "--full"]
     out = subprocess.run(command, capture_output=True, text=True, timeout=360, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [line for line in out.stdout.splitlines() if line.startswith("{")]

@@ -41,7 +41,7 @@ def test_bench_over_rccl_on_one_gpu(shard):
     between two device buffers), the all-reduces behind `rccl_ranks` and the max-over-ranks time, all_gather_object, barriers,
     destroy — and ONE JSON line. "device-sdma": the peer-window path (IPC export of rank 0's buffers) under the same group."""
     command = [sys.executable, str(ROOT/"bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames-per-step", "8",
-               "--width", "640", "--height", "360", "--no-cpu-baseline"]
+               "--width", "640", "--height", "360", "--full", "--no-cpu-baseline"]
     out = subprocess.run(command, capture_output=True, text=True, timeout=420, cwd=ROOT, env=_rccl_env(**({"SHADERFLOW_SHARD": shard} if shard else {})))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [line for line in out.stdout.splitlines() if line.startswith("{")]

@@ -375,7 +375,7 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     out = subprocess.run([sys.executable, str(root/"bench.py"), "--steps", "2", "--warmup", "1", "--frames-per-step", "3",
-                          "--width", "384", "--height", "216", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--width", "384", "--height", "216", "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [line for line in out.stdout.splitlines() if line.startswith("{")]
     assert len(lines) == 1
@@ -394,6 +394,26 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert record["cpu_baseline"]["single_thread"]["cores"] == 1 and record["export_host"]["value"] > 0
 
 
+def test_plain_bench_run_measures_the_headline_only():
+    """Without --full the line keeps its headline fields and measures nothing else: no CPU baseline, no export, no counter passes"""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    out = subprocess.run([sys.executable, str(root/"bench.py"), "--steps", "2", "--warmup", "1", "--frames-per-step", "3",
+                          "--width", "384", "--height", "216"], capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [line for line in out.stdout.splitlines() if line.startswith("{")]
+    assert len(lines) == 1
+    record = json.loads(lines[0])
+    assert record["n_gpus"] == 1 and record["steps"] == 2 and record["warmup"] == 1 and record["unit"] == "frames/s" and record["dtype"] == "f32"
+    assert record["value"] > 0 and record["ms_per_step"] > 0 and record["higher_is_better"] is True
+    assert not {"cpu_baseline", "export_host", "value_host", "value_yuv420p"} & set(record), sorted(record)
+    assert not (record["roofline"]["counters_from"] or "").startswith("live"), record["roofline"]["counters_from"]
+    assert record["roofline"]["kernel"].startswith("k_") and record["roofline"]["launch_ms"] > 0
+
+
 def test_bench_measures_the_instruction_counters_of_its_own_run():
     """The benchmark's configuration (C3) as the driver runs it, short: the dominant kernel's VALU counters come from two rocprofv3
     children of the run itself, and they say what the ISA census says (profiles/r05_strip_isa_census.txt) —
@@ -407,7 +427,7 @@ def test_bench_measures_the_instruction_counters_of_its_own_run():
     if shutil.which("rocprofv3") is None:
         pytest.skip("no rocprofv3 on this box")
     root = Path(__file__).resolve().parent.parent
-    out = subprocess.run([sys.executable, str(root/"bench.py"), "--steps", "2", "--warmup", "1", "--frames-per-step", "30", "--no-cpu-baseline", "--no-export"],
+    out = subprocess.run([sys.executable, str(root/"bench.py"), "--steps", "2", "--warmup", "1", "--frames-per-step", "30", "--full", "--no-cpu-baseline", "--no-export"],
                          capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     record = json.loads([line for line in out.stdout.splitlines() if line.startswith("{")][-1])

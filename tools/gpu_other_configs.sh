@@ -11,7 +11,7 @@ OUT=gpurun_out/$TAG/bench_other_configs.jsonl
 for cfg in "--scene basic --width 256 --height 256 --ssaa 1 --frames-per-step 60" "--width 256 --height 256 --ssaa 1 --frames-per-step 60" "--width 1920 --height 1080 --ssaa 1 --frames-per-step 60" "--width 1920 --height 1080 --ssaa 2 --frames-per-step 60" \
            "--width 2560 --height 1440 --ssaa 2 --frames-per-step 60" "--width 7680 --height 4320 --ssaa 4 --frames-per-step 8" \
            "--scene bars --frames-per-step 300" "--scene waveform --frames-per-step 300" "--scene basic --frames-per-step 300" "--scene basic --frames-per-step 300 --camera-zoom 0.2"; do
-  timeout 600 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-export $cfg 2>>gpurun_out/$TAG/bench_other_configs.err | tail -n 1 >> $OUT
+  timeout 600 python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-export $cfg 2>>"${OUT%.jsonl}.err" | tail -n 1 >> $OUT
 done
 python3 - "$OUT" <<'PY'
 import json, sys

@@ -17,7 +17,7 @@ wave follow from a handful of event rates:
 The model's per-class totals are then CHECKED against the hardware's class counters of the same launch (SQ_INSTS_VALU_*): the split of
 "other" is credible to the extent the counted classes agree.
 
-usage: tools/strip_census.py blocks.json [bench.json with roofline.issue_model] [--folds 53.0]
+usage: tools/strip_census.py blocks.json [bench.json with roofline.issue_model: a `bench.py --full` line] [--folds 53.0]
 """
 from __future__ import annotations
 
