@@ -247,6 +247,43 @@ class Bloom(ShaderScene):
         self.shader.fragment = self.FRAGMENT
 
 
+
+class AudioTrails(_AudioScene):
+    """Audio-reactive trails (not one of the reference's): a fragment of its own, translated at run time, with two layers and four
+    frames of history. Layer 0 draws the spectrum as a ring of bars around a disc that breathes with the volume; layer 1 lays it over
+    its own previous frame, zoomed in a little and faded, so every bar leaves a trail — the kind of feedback scene a user of the
+    Visualizer writes next. No python logic between frames: it renders on the device audio tape (shaderflow_amd/tapesequence.py)."""
+    FRAGMENT = """
+        void main() {
+            if (iLayer == 0) {
+                float angle = abs(atan(gluv.y, gluv.x))/PI;
+                vec2 s = texture(iSpectrogram, vec2(0.5, angle)).xy;
+                float bar = 0.5*sqrt(max(0.5*(s.x + s.y), 0.0)/1000.0);
+                float radius = 0.25 + 0.15*iAudioVolume;
+                float r = length(gluv);
+                float ring = smoothstep(radius - 0.01, radius, r)*(1.0 - smoothstep(radius + bar, radius + bar + 0.01, r));
+                vec3 colour = hsv2rgb(vec3(fract(angle*0.5 + 0.1*iTime), 0.7, 1.0))*ring;
+                colour += vec3(0.1, 0.15, 0.3)*(1.0 - smoothstep(0.0, radius, r))*(0.5 + iAudioVolume);
+                fragColor = vec4(colour, 1.0);
+                return;
+            }
+            vec4 now = texture(iScreen0x0, astuv);
+            vec2 inward = 0.5 + (astuv - 0.5)*(0.98 - 0.02*iAudioVolume);
+            vec3 trail = 0.6*iScreenTexture(1, 1, inward).rgb + 0.3*iScreenTexture(3, 1, inward).rgb;
+            fragColor = vec4(max(now.rgb, trail), 1.0);
+        }
+    """
+
+    def build(self):
+        from shaderflow_amd.audio.spectrogram import ShaderSpectrogram
+        from shaderflow_amd.piano import PianoNote
+        self._load_audio()
+        self.spectrogram = ShaderSpectrogram(scene=self, length=0, audio=self.audio, smooth=False)
+        self.spectrogram.from_notes(start=PianoNote.from_frequency(20), end=PianoNote.from_frequency(14000), piano=True)
+        self.shader.texture.temporal = 4
+        self.shader.texture.layers = 2
+        self.shader.fragment = self.FRAGMENT
+
 def make(cls, audio=None, background=None, **fields):
     """Build a scene class with its inputs set before `build()` runs (class attributes, like demo.py's Life)"""
     attrs = {}

@@ -367,6 +367,15 @@ int sfx_tape_destroy(sfx_handle tape);
 int sfx_render_tape(sfx_handle program, sfx_handle tape, int frame0, int nframes,
                     int width, int height, int ssaa_x1000, int subsample, void* device_out);
 
+/* sfx_clock_sequence_run for audio scenes (layered / temporal / several programs, no host logic): frame f of the call is tape frame
+ * frame0 + f of the bank the last sfx_tape_build filled. A pass whose program samples iSpectrogram / iWaveform or reads an audio uniform
+ * (iAudioVolume, iAudioVolumeIntegral, iAudioSTD, iSpectrogramOffset) takes them from that tape frame — a layered pass draws each layer
+ * into row 0 of its matrix, a fused one is sfx_render_tape into the pass' target; every other pass is drawn as by
+ * sfx_clock_sequence_run. The call waits for the bank's build and marks the bank rendered behind its last kernel, as sfx_render_tape. */
+int sfx_tape_sequence_run(sfx_handle ctx, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
+                          const sfx_clock_tick* clock, int nframes, sfx_handle tape, int frame0, sfx_handle ring, int first_slot, int fd,
+                          void* const* planar_slots, int yuv_matrix, int width, int height);
+
 /* Device memory helper for callers without their own allocator */
 int sfx_device_alloc(sfx_handle ctx, size_t nbytes, void** ptr);
 int sfx_device_free(sfx_handle ctx, void* ptr);

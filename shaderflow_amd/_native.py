@@ -173,6 +173,8 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_tape_read": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "sfx_tape_destroy": (C.c_int, [Handle]),
     "sfx_render_tape": (C.c_int, [Handle, Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sfx_tape_sequence_run": (C.c_int, [Handle, P(SequencePass), C.c_int, P(SequenceMatrix), C.c_int, P(ClockTick), C.c_int, Handle, C.c_int, Handle,
+                                        C.c_int, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),
     "sfx_device_free": (C.c_int, [Handle, C.c_void_p]),
     "sfx_device_copy": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_size_t]),

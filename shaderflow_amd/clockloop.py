@@ -13,7 +13,7 @@ Same launches in the same order with the same uniform values as the frame loop, 
 from __future__ import annotations
 
 import ctypes as C
-from typing import TYPE_CHECKING
+from typing import TYPE_CHECKING, Optional
 
 import numpy as np
 
@@ -21,6 +21,7 @@ from shaderflow_amd import _native as N
 from shaderflow_amd.camera import CameraMode, ShaderCamera
 from shaderflow_amd.dynamics import ShaderDynamics
 from shaderflow_amd.module import ShaderModule
+from shaderflow_amd.parallel import shard_batches
 from shaderflow_amd.scheduler import freewheel_clock
 from shaderflow_amd.shader import ShaderProgram
 from shaderflow_amd.texture import ShaderTexture
@@ -28,11 +29,13 @@ from shaderflow_amd.texture import ShaderTexture
 if TYPE_CHECKING:
     from shaderflow_amd.exporting import ExportingHelper
     from shaderflow_amd.scene import ShaderScene
+    from shaderflow_amd.tape import FrameTape
 
 
 class ClockLoop:
     @staticmethod
-    def applicable(scene: "ShaderScene") -> bool:
+    def applicable(scene: "ShaderScene", taped: frozenset = frozenset()) -> bool:
+        """`taped`: ids of the modules an audio tape computes for the caller (tapesequence.py) — left to its own judgement"""
         from shaderflow_amd.scene import ShaderScene
         if type(scene).update is not ShaderModule.update:
             return False
@@ -44,7 +47,7 @@ class ClockLoop:
         if type(scene).pipeline is not ShaderScene.pipeline and not ClockLoop.pipeline_is_static(scene):
             return False
         for module in scene.modules:
-            if module is scene or isinstance(module, ShaderScene):
+            if module is scene or isinstance(module, ShaderScene) or id(module) in taped:
                 continue
             if type(module) not in (ShaderCamera, ShaderDynamics, ShaderProgram, ShaderTexture):
                 return False
@@ -127,7 +130,10 @@ class ClockLoop:
             return False
         return all(program.program is not None for program in self.programs)
 
-    def run_native(self, export: "ExportingHelper", times, dts, rdts, total: int) -> None:
+    def run_native(self, export: "ExportingHelper", times, dts, rdts, total: int, tape: "Optional[FrameTape]" = None, pipe_here: bool = False,
+                   turbo: bool = True) -> None:
+        """With a `tape` (tapesequence.py) the frames go in the tape's batches: each batch is built, then drawn by sfx_tape_sequence_run in
+        chunks that stay inside it. `pipe_here`: one frame per call, read out by export.pipe (a progress relay, no turbo)"""
         scene, lib = self.scene, N.lib()
         runtime, fps = scene.runtime, scene.fps
         # texture matrices: every program's own (its draws go to row 0) — the same objects `rolling` lists when they are temporal
@@ -157,27 +163,41 @@ class ClockLoop:
         planar = None
         if export._yuv_slots:                                           # (staging exists for a planar sink only)
             planar = (C.c_void_p*len(export._yuv_slots))(*export._yuv_slots)
-        piping = export.fileno is not None and export.ring is not None
+        piping = export.fileno is not None and export.ring is not None and not pipe_here
         done = 0
         per_frame = None                                               # seconds per frame of the last native call
         import time as clock
-        while done < total and not scene.quit:
-            count = min(self.chunk_frames(per_frame), total - done)
-            export._check_encoder()
-            started = clock.perf_counter()
-            ticks = (N.ClockTick*count)()
-            for i in range(count):
-                time = times[done + i]
-                ticks[i] = N.ClockTick(time, (time/runtime) % 1.0, dts[done + i], round(time*fps))
-            N.check(lib.sfx_clock_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
-                                               export.ring if piping else N.Handle(), export.frame % max(1, export.slots), export.fileno if piping else -1,
-                                               planar, 1 if export.yuv_matrix == "bt709" else 0, scene.width, scene.height))
-            per_frame = (clock.perf_counter() - started)/count
-            for texture in textures:
-                texture.roll(count)                                   # the native call rolled its own copy of every matrix it drew into
-            export.frame += count
-            done += count
-            keep.clear()
+        for first, size in (shard_batches(0, total, tape.batch) if tape is not None else [(0, total)]):
+            if scene.quit:
+                break
+            if tape is not None:
+                tape.build(first, size)                               # on the tape's stream, beside the previous batch's draws
+            while done < first + size and not scene.quit:
+                count = 1 if pipe_here else min(self.chunk_frames(per_frame), first + size - done)
+                export._check_encoder()
+                started = clock.perf_counter()
+                ticks = (N.ClockTick*count)()
+                for i in range(count):
+                    time = times[done + i]
+                    ticks[i] = N.ClockTick(time, (time/runtime) % 1.0, dts[done + i], round(time*fps))
+                ring, slot, fd = export.ring if piping else N.Handle(), export.frame % max(1, export.slots), export.fileno if piping else -1
+                if tape is None:
+                    N.check(lib.sfx_clock_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
+                                                       ring, slot, fd, planar, 1 if export.yuv_matrix == "bt709" else 0, scene.width, scene.height))
+                else:
+                    N.check(lib.sfx_tape_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
+                                                      tape.handle, done - first, ring, slot, fd, planar, 1 if export.yuv_matrix == "bt709" else 0,
+                                                      scene.width, scene.height))
+                per_frame = (clock.perf_counter() - started)/count
+                for texture in textures:
+                    texture.roll(count)                               # the native call rolled its own copy of every matrix it drew into
+                if pipe_here:
+                    export.pipe(turbo=turbo)
+                    export.update()
+                else:
+                    export.frame += count
+                done += count
+                keep.clear()
         if done:
             scene.time, scene.dt, scene.rdt = times[done - 1], dts[done - 1], rdts[done - 1]
 

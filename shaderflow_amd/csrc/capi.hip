@@ -1001,43 +1001,115 @@ static int resolve_sampler(const Program* p, const char* name) {
     if (p->fragment == FRAG_JIT) { for (const auto& b : p->bindings) if (b.sampler && b.name == name) return b.slot; return -1; }
     return sampler_slot(p->fragment, name);
 }
-extern "C" int sfx_clock_sequence_run(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                                      const sfx_clock_tick* clock, int nframes, sfx_handle hring, int first_slot, int fd,
-                                      void* const* planar_slots, int yuv_matrix, int width, int height) {
+
+// exporting.pipe (exporting.py:151-174) of the frame a sequence just left in `final_target`: ring slot `slot` → fd, through the slot's
+// device staging as yuv420p when `planar_slots` is given
+static int sequence_pipe(sfx_handle hc, sfx_handle hring, int slot, int fd, sfx_handle final_target, void* const* planar_slots, int yuv_matrix,
+                         int width, int height) {
+    int rc;
+    if (planar_slots) {
+        if ((rc = sfx_ring_pipe_sync(hring, slot))) return rc;
+        Texture* final_texture = get<Texture>(final_target, MAGIC_TEX);
+        if (!final_texture) return fail(SFX_E_INVALID, "clock sequence: the last pass has no target to convert");
+        // (the conversion reads width x height RGB8 texels and writes width*height*3/2 bytes: the caller's numbers must be the texture's)
+        if (final_texture->dtype != SFX_U8 || final_texture->components != 3 || final_texture->width != width || final_texture->height != height)
+            return fail(SFX_E_INVALID, "clock sequence: yuv420p of a %d x %d frame was asked for, the last pass' target is %d x %d x %d (dtype %d)",
+                        width, height, final_texture->width, final_texture->height, final_texture->components, final_texture->dtype);
+        if ((rc = sfx_rgb_to_yuv420(hc, final_texture->data, planar_slots[slot], width, height, 1, yuv_matrix))) return rc;
+        rc = sfx_ring_read_device_async(hring, planar_slots[slot], slot);
+    } else {
+        rc = sfx_ring_read_async(hring, final_target, slot);
+    }
+    if (rc) return rc;
+    return sfx_ring_pipe(hring, slot, fd);
+}
+
+// Whether a program's draws read the audio state of a frame: it samples iSpectrogram / iWaveform or reads iAudioVolume,
+// iAudioVolumeIntegral, iAudioSTD or iSpectrogramOffset. The stock fragments by name (check_samplers' table, and demo.py's audio
+// fragment for the uniform), a translated one by its sampler bindings and its code object's flags (sfx_jit_flags bit 1, glsl2hip.py).
+static bool reads_audio(const Program* p) {
+    if (p->fragment == FRAG_JIT) {
+        if (p->flags & 2u) return true;
+        for (const auto& b : p->bindings) if (b.sampler && (b.slot == TEX_SPECTROGRAM || b.slot == TEX_WAVEFORM)) return true;
+        return false;
+    }
+    return p->fragment == FRAG_VISUALIZER || p->fragment == FRAG_BARS || p->fragment == FRAG_WAVEFORM || p->fragment == FRAG_AUDIO;
+}
+
+static int bind_tape(const Program* p, const TapeView* t, RenderArgs& a, int frame0, int nframes);
+// Records the bank's `rendered` event behind the last kernel its scope launched (the build that refills the bank waits for it)
+struct RenderedMark { hipEvent_t event; hipStream_t stream; ~RenderedMark() { if (event) hipEventRecord(event, stream); } };
+
+// sfx_render for tape frame `frame`: the draw of one layer into one box of a texture matrix, its audio state from the tape
+static int render_tape_box(Program* p, const TapeView* t, int frame, Texture* target, int layer) {
+    if (target->dtype != SFX_U8 && target->dtype != SFX_F32 && target->dtype != SFX_F16) return fail(SFX_E_UNSUPPORTED, "render target dtype %d", target->dtype);
+    RenderArgs a;
+    fill_args(p, a);
+    a.u.iLayer = layer;                                             // shader.py:402
+    a.wr = target->width; a.hr = target->height; a.w = target->width; a.h = target->height;
+    a.out = target->data; a.out_components = target->components; a.out_dtype = target->dtype; a.out_frame_stride = 0;
+    set_pixel_centres(a);
+    int rc = bind_tape(p, t, a, frame, 1);
+    if (rc) return rc;
+    if ((rc = launch_render_p(p, a, 1, p->ctx->stream))) return rc;
+    return launch_status();
+}
+
+// The loop of sfx_clock_sequence_run and sfx_tape_sequence_run. With a tape (`ht`), frame f of the call is tape frame frame0 + f of
+// the bank the last build filled: every pass whose program reads audio (reads_audio, decided once per call) takes that frame's
+// audio state from the tape — a layered pass draws through render_tape_box, a fused one through sfx_render_tape into iFinal — and
+// every other pass is drawn exactly as without a tape.
+static int run_sequence(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
+                        const sfx_clock_tick* clock, int nframes, sfx_handle ht, int frame0, sfx_handle hring, int first_slot, int fd,
+                        void* const* planar_slots, int yuv_matrix, int width, int height) {
     CTX_OR_FAIL(c, hc);
     const int ring_slots = hring ? ring_slot_count(hring) : 0;
     if (!passes || npasses < 1 || nmatrices < 0 || (nmatrices && !matrices) || !clock || nframes < 0) return fail(SFX_E_INVALID, "clock sequence: null tables");
     if (ring_slots < 0) return fail(SFX_E_INVALID, "clock sequence: invalid ring handle");
+    TapeView tape, *t = nullptr;
+    if (ht) {
+        if (!tape_view(ht, &tape)) return fail(SFX_E_INVALID, "tape sequence: invalid tape handle");
+        if (tape.ctx != c) return fail(SFX_E_INVALID, "tape sequence: the tape belongs to another context");
+        if (frame0 < 0 || frame0 + nframes > tape.max_frames) return fail(SFX_E_INVALID, "tape sequence: frames [%d, %d) outside the tape", frame0, frame0 + nframes);
+        t = &tape;
+    }
     USE_DEVICE(c);
     // the matrices as this call rolls them: order[m][t] = row of the caller's table that sits at depth t now
     std::vector<std::vector<int>> order(nmatrices);
     for (int m = 0; m < nmatrices; m++) {
         if (matrices[m].temporal < 1 || matrices[m].layers < 1 || !matrices[m].textures) return fail(SFX_E_INVALID, "clock sequence: matrix %d", m);
         order[m].resize(matrices[m].temporal);
-        for (int t = 0; t < matrices[m].temporal; t++) order[m][t] = t;
+        for (int d = 0; d < matrices[m].temporal; d++) order[m][d] = d;
         for (int k = 0; k < matrices[m].temporal*matrices[m].layers; k++) {
             Texture* texture = get<Texture>(matrices[m].textures[k], MAGIC_TEX);
             if (!texture || texture->ctx != c) return fail(SFX_E_INVALID, "clock sequence: matrix %d, box %d is not a texture of this context", m, k);
         }
     }
-    auto box = [&](int m, int t, int l) -> sfx_handle { return matrices[m].textures[order[m][t]*matrices[m].layers + (l < 0 ? matrices[m].layers + l : l)]; };
+    auto box = [&](int m, int d, int l) -> sfx_handle { return matrices[m].textures[order[m][d]*matrices[m].layers + (l < 0 ? matrices[m].layers + l : l)]; };
     // sampler slots of every (program, named box), resolved once: the names never change, only what sits behind them
     struct Bind { Program* p; int slot, m, t, l; };
     std::vector<Bind> binds;
+    std::vector<char> audio(npasses, 0);                             // pass k draws from the tape
     for (int k = 0; k < npasses; k++) {
         if (passes[k].kind == SFX_PASS_RESOLVE) continue;
         Program* p = get<Program>(passes[k].program, MAGIC_PROG);
         if (!p || p->ctx != c) return fail(SFX_E_INVALID, "clock sequence: pass %d has no program of this context", k);
         if (passes[k].matrix < 0 || passes[k].matrix >= nmatrices) return fail(SFX_E_INVALID, "clock sequence: pass %d names matrix %d", k, passes[k].matrix);
+        audio[k] = (t && reads_audio(p)) ? 1 : 0;
+        if (audio[k] && passes[k].kind == SFX_PASS_FUSED && !get<Texture>(passes[k].target, MAGIC_TEX)) return fail(SFX_E_INVALID, "tape sequence: fused pass %d has no target", k);
         for (int m = 0; m < nmatrices; m++) {
             if (!matrices[m].names || matrices[m].temporal < 2) continue;     // (samplers of a matrix that never rolls were bound by the host)
-            for (int t = 0; t < matrices[m].temporal; t++) for (int l = 0; l < matrices[m].layers; l++) {
-                const char* name = matrices[m].names[t*matrices[m].layers + l];
+            for (int d = 0; d < matrices[m].temporal; d++) for (int l = 0; l < matrices[m].layers; l++) {
+                const char* name = matrices[m].names[d*matrices[m].layers + l];
                 const int slot = name ? resolve_sampler(p, name) : -1;
-                if (slot >= 0) binds.push_back({p, slot, m, t, l});
+                if (slot >= 0) binds.push_back({p, slot, m, d, l});
             }
         }
     }
+    // the bank was filled on the tape's stream: the draws wait for its last audio kernel, and the build that refills it waits for
+    // the mark behind the last kernel of this call (as in sfx_render_tape)
+    if (t) HIP_TRY(hipStreamWaitEvent(c->stream, t->built, 0));
+    RenderedMark mark{t ? t->rendered : nullptr, c->stream};
     for (int f = 0; f < nframes; f++) {
         const sfx_clock_tick& now = clock[f];
         bool fused = false;
@@ -1054,65 +1126,54 @@ extern "C" int sfx_clock_sequence_run(sfx_handle hc, const sfx_sequence_pass* pa
             p->u.iTime = now.time; p->u.iTau = now.tau; p->u.iDeltatime = now.deltatime; p->u.iFrame = now.frame;      // sfx_uniform_set_clock
             for (const Bind& b : binds) if (b.p == p) b.p->samplers[b.slot] = get<Texture>(box(b.m, b.t, b.l), MAGIC_TEX);
             if (pass.kind == SFX_PASS_FUSED) {
-                const int rc = sfx_render_resolve(pass.program, pass.target, pass.ssaa, pass.subsample);
+                int rc;
+                if (audio[k]) {
+                    Texture* final_texture = get<Texture>(pass.target, MAGIC_TEX);
+                    rc = sfx_render_tape(pass.program, ht, frame0 + f, 1, final_texture->width, final_texture->height, pass.ssaa*1000, pass.subsample, final_texture->data);
+                } else {
+                    rc = sfx_render_resolve(pass.program, pass.target, pass.ssaa, pass.subsample);
+                }
                 if (rc) return rc;
                 fused = true;
             } else {
                 for (int l = 0; l < matrices[pass.matrix].layers; l++) {
-                    const int rc = sfx_render(pass.program, box(pass.matrix, 0, l), l);      // shader.py:400-403: iLayer = l, into row 0
+                    // shader.py:400-403: iLayer = l, into row 0
+                    const int rc = audio[k] ? render_tape_box(p, t, frame0 + f, get<Texture>(box(pass.matrix, 0, l), MAGIC_TEX), l)
+                                            : sfx_render(pass.program, box(pass.matrix, 0, l), l);
                     if (rc) return rc;
                 }
             }
             std::vector<int>& rows = order[pass.matrix];              // texture.roll(): the oldest row becomes row 0
             std::rotate(rows.begin(), rows.end() - 1, rows.end());
         }
-        if (ring_slots > 0 && fd >= 0) {                            // exporting.pipe (exporting.py:151-174)
-            const int slot = (first_slot + f) % ring_slots;
-            int rc;
-            if (planar_slots) {
-                if ((rc = sfx_ring_pipe_sync(hring, slot))) return rc;
-                Texture* final_texture = get<Texture>(passes[npasses - 1].target, MAGIC_TEX);
-                if (!final_texture) return fail(SFX_E_INVALID, "clock sequence: the last pass has no target to convert");
-                // (the conversion reads width x height RGB8 texels and writes width*height*3/2 bytes: the caller's numbers must be the texture's)
-                if (final_texture->dtype != SFX_U8 || final_texture->components != 3 || final_texture->width != width || final_texture->height != height)
-                    return fail(SFX_E_INVALID, "clock sequence: yuv420p of a %d x %d frame was asked for, the last pass' target is %d x %d x %d (dtype %d)",
-                                width, height, final_texture->width, final_texture->height, final_texture->components, final_texture->dtype);
-                if ((rc = sfx_rgb_to_yuv420(hc, final_texture->data, planar_slots[slot], width, height, 1, yuv_matrix))) return rc;
-                rc = sfx_ring_read_device_async(hring, planar_slots[slot], slot);
-            } else {
-                rc = sfx_ring_read_async(hring, passes[npasses - 1].target, slot);
-            }
+        if (ring_slots > 0 && fd >= 0) {
+            const int rc = sequence_pipe(hc, hring, (first_slot + f) % ring_slots, fd, passes[npasses - 1].target, planar_slots, yuv_matrix, width, height);
             if (rc) return rc;
-            if ((rc = sfx_ring_pipe(hring, slot, fd))) return rc;
         }
     }
     return SFX_OK;
 }
 
+extern "C" int sfx_clock_sequence_run(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
+                                      const sfx_clock_tick* clock, int nframes, sfx_handle hring, int first_slot, int fd,
+                                      void* const* planar_slots, int yuv_matrix, int width, int height) {
+    return run_sequence(hc, passes, npasses, matrices, nmatrices, clock, nframes, 0, 0, hring, first_slot, fd, planar_slots, yuv_matrix, width, height);
+}
 
-extern "C" int sfx_render_tape(sfx_handle hp, sfx_handle ht, int frame0, int nframes, int width, int height,
-                               int ssaa_x1000, int subsample, void* device_out) {
-    Program* p = get<Program>(hp, MAGIC_PROG);
-    TapeView tape, *t = &tape;                                      // the bank the last build filled (capi_audio.hip)
-    if (!p || !tape_view(ht, t) || !device_out) return fail(SFX_E_INVALID, "invalid program/tape handle or output");
-    if (p->ctx != t->ctx) return fail(SFX_E_INVALID, "program and tape belong to different contexts");
-    if (frame0 < 0 || nframes < 1 || frame0 + nframes > t->max_frames) return fail(SFX_E_INVALID, "frames [%d, %d) outside the tape", frame0, frame0 + nframes);
-    if (subsample < 1) subsample = 1;
-    if (ssaa_x1000 < 10) return fail(SFX_E_INVALID, "ssaa %d/1000", ssaa_x1000);
-    const bool fused = (ssaa_x1000 % 1000 == 0) && fused_supported(ssaa_x1000/1000, subsample) && fusable(p, ssaa_x1000/1000);
-    const int ssaa = ssaa_x1000/1000;
-    USE_DEVICE(p->ctx);
-    RenderArgs a;
-    fill_args(p, a);
-    a.w = width; a.h = height; a.subsample = subsample;
-    a.wr = (int)((double)width*ssaa_x1000/1000.0); a.hr = (int)((double)height*ssaa_x1000/1000.0);   // scene.py:372-375
-    set_pixel_centres(a);
-    a.out = device_out; a.out_frame_stride = (long)width*height*3;
+// The same loop for audio scenes (tapesequence.py): the passes that read audio draw tape frames [frame0, frame0 + nframes)
+extern "C" int sfx_tape_sequence_run(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
+                                     const sfx_clock_tick* clock, int nframes, sfx_handle ht, int frame0, sfx_handle hring, int first_slot, int fd,
+                                     void* const* planar_slots, int yuv_matrix, int width, int height) {
+    if (!ht) return fail(SFX_E_INVALID, "tape sequence: null tape handle");
+    return run_sequence(hc, passes, npasses, matrices, nmatrices, clock, nframes, ht, frame0, hring, first_slot, fd, planar_slots, yuv_matrix, width, height);
+}
+
+
+// The tape's half of RenderArgs for tape frames [frame0, frame0 + nframes): the per-frame uniforms, the iSpectrogram / iWaveform
+// redirect and the visualizer's per-frame constants. The caller has filled the rest (fill_args) and ordered its stream after the
+// bank's build. Shared by sfx_render_tape and the tape sequence.
+static int bind_tape(const Program* p, const TapeView* t, RenderArgs& a, int frame0, int nframes) {
     a.dyn = t->dyn; a.frame0 = frame0;
-    // the bank was filled on the tape's stream: this stream waits for its last audio kernel, and leaves a mark behind its own last
-    // kernel that the build refilling the bank will wait for (Tape, above)
-    HIP_TRY(hipStreamWaitEvent(p->ctx->stream, t->built, 0));
-    struct RenderedMark { hipEvent_t event; hipStream_t stream; ~RenderedMark() { hipEventRecord(event, stream); } } mark{t->rendered, p->ctx->stream};
     if (t->audio) {
     // iSpectrogram: width 1 (length=0 scenes), height bins, RG32F (spectrogram.py:298-311); the bound texture's
     // sampler state is kept, only its storage is redirected to the tape column of the frame
@@ -1137,7 +1198,7 @@ extern "C" int sfx_render_tape(sfx_handle hp, sfx_handle ht, int frame0, int nfr
     a.tex[TEX_SPECTROGRAM].data = a.tape_spectrogram;
     if (t->points > 0) a.tex[TEX_WAVEFORM].data = t->rows;
     }
-    int rc = check_samplers(p->fragment, a);
+    const int rc = check_samplers(p->fragment, a);
     if (rc) return rc;
     a.has_vis = 0;                                                  // per-frame audio uniforms live on the device
     if (p->fragment == FRAG_VISUALIZER) {
@@ -1149,6 +1210,33 @@ extern "C" int sfx_render_tape(sfx_handle hp, sfx_handle ht, int frame0, int nfr
             a.tape_bars = t->bars;
         }
     }
+    return SFX_OK;
+}
+
+extern "C" int sfx_render_tape(sfx_handle hp, sfx_handle ht, int frame0, int nframes, int width, int height,
+                               int ssaa_x1000, int subsample, void* device_out) {
+    Program* p = get<Program>(hp, MAGIC_PROG);
+    TapeView tape, *t = &tape;                                      // the bank the last build filled (capi_audio.hip)
+    if (!p || !tape_view(ht, t) || !device_out) return fail(SFX_E_INVALID, "invalid program/tape handle or output");
+    if (p->ctx != t->ctx) return fail(SFX_E_INVALID, "program and tape belong to different contexts");
+    if (frame0 < 0 || nframes < 1 || frame0 + nframes > t->max_frames) return fail(SFX_E_INVALID, "frames [%d, %d) outside the tape", frame0, frame0 + nframes);
+    if (subsample < 1) subsample = 1;
+    if (ssaa_x1000 < 10) return fail(SFX_E_INVALID, "ssaa %d/1000", ssaa_x1000);
+    const bool fused = (ssaa_x1000 % 1000 == 0) && fused_supported(ssaa_x1000/1000, subsample) && fusable(p, ssaa_x1000/1000);
+    const int ssaa = ssaa_x1000/1000;
+    USE_DEVICE(p->ctx);
+    RenderArgs a;
+    fill_args(p, a);
+    a.w = width; a.h = height; a.subsample = subsample;
+    a.wr = (int)((double)width*ssaa_x1000/1000.0); a.hr = (int)((double)height*ssaa_x1000/1000.0);   // scene.py:372-375
+    set_pixel_centres(a);
+    a.out = device_out; a.out_frame_stride = (long)width*height*3;
+    // the bank was filled on the tape's stream: this stream waits for its last audio kernel, and leaves a mark behind its own last
+    // kernel that the build refilling the bank will wait for (Tape, above)
+    HIP_TRY(hipStreamWaitEvent(p->ctx->stream, t->built, 0));
+    RenderedMark mark{t->rendered, p->ctx->stream};
+    int rc = bind_tape(p, t, a, frame0, nframes);
+    if (rc) return rc;
     if (fused) {
         if ((rc = launch_fused_p(p, a, ssaa, nframes, p->ctx->stream))) return rc;
         return launch_status();

@@ -940,10 +940,16 @@ inline void sfx_jit_host_texture(sf::Tex* textures, int slot, const void* data, 
 #endif
 
 // Entry points of a code object (capi: sfx_program_load looks them up by these names)
-// sfx_jit_flags: bit 0 = SF_JIT_DERIVATIVES, bits 8-15 = rows a lane walks in sfx_jit_render / sfx_jit_fused_1 (the launch geometry).
+// sfx_jit_flags: bit 0 = SF_JIT_DERIVATIVES, bit 1 = SF_JIT_AUDIO, bits 8-15 = rows a lane walks in sfx_jit_render / sfx_jit_fused_1
+// (the launch geometry).
 // SF_JIT_DERIVATIVES (0/1, defined by the translator before this macro): the fragment calls dFdx/dFdy/fwidth — the unfused kernel
 // uses the quad layout and the library keeps the program off the fused kernels except at ssaa 2, where the four supersamples of
 // a pixel already are the four lanes of a quad (all valid or all invalid together).
+// SF_JIT_AUDIO (0/1, defined by the translator): the fragment reads a uniform the tape sets per frame (iAudioVolume, iAudioVolumeIntegral,
+// iAudioSTD, iSpectrogramOffset; render_kernels.hpp frame_view) — the tape sequence draws it from the tape (capi.hip reads_audio).
+#ifndef SF_JIT_AUDIO
+#define SF_JIT_AUDIO 0
+#endif
 // SF_JIT_TILED: the translator asked for an LDS tile (SF_JIT_TILE_SLOT) and the fragment takes no derivatives (a probe with
 // two live lanes has no neighbours to difference with).
 #define SF_JIT_TILED ((SF_JIT_TILE_SLOT >= 0) && !(SF_JIT_DERIVATIVES))
@@ -960,7 +966,7 @@ inline void sfx_jit_host_texture(sf::Tex* textures, int slot, const void* data, 
 #define SF_JIT_ENTRY_POINTS(FRAGMENT) \
     SF_JIT_HOST_POINTS(FRAGMENT) \
     extern "C" __device__ __attribute__((used)) const unsigned long long sfx_jit_layout = sf::render_args_layout(); \
-    extern "C" __device__ __attribute__((used)) const unsigned sfx_jit_flags = (SF_JIT_DERIVATIVES ? 1u : 0u) | \
+    extern "C" __device__ __attribute__((used)) const unsigned sfx_jit_flags = (SF_JIT_DERIVATIVES ? 1u : 0u) | (SF_JIT_AUDIO ? 2u : 0u) | \
         ((unsigned)sf::shader_rows_1x<sf::JitShader<FRAGMENT, false, SF_JIT_TILED>>::value << 8); \
     extern "C" __global__ __launch_bounds__(256) void sfx_jit_render(const sf::RenderArgs a) { sf::render_body<sf::JitShader<FRAGMENT, (SF_JIT_DERIVATIVES != 0), SF_JIT_TILED>>(a); } \
     SF_JIT_QUADS_ENTRY(FRAGMENT) \

@@ -42,6 +42,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-ffp-contract=off", "-fh
 USER_SLOTS = 64          # csrc/glsl.hpp USER_SLOTS
 TEX_SLOTS = 16           # csrc/glsl.hpp TEX_SLOTS
 FIXED_SAMPLER_SLOTS = {"iSpectrogram": 1, "iWaveform": 2}      # the slots the tape patches per frame (render_kernels.hpp frame_view)
+AUDIO_UNIFORMS = {"iAudioVolume", "iAudioVolumeIntegral", "iAudioSTD", "iSpectrogramOffset"}   # … and the uniforms it patches (sfx_jit_flags bit 1)
 
 
 class TranslationError(Exception):
@@ -573,6 +574,7 @@ class _Translator:
         code = "".join(self.body)
         undefs = "".join(f"#undef {m}\n" for m in dict.fromkeys(self.macros))
         derivatives = bool(self.identifiers & {'dFdx', 'dFdy', 'fwidth'})
+        audio = bool(self.identifiers & AUDIO_UNIFORMS)
         tiled = None if derivatives else _sampler_worth_a_tile(code, [b for b in bindings if b.type == "sampler2D"])
         cpp = ("// generated by shaderflow_amd/glsl2hip.py from a GLSL fragment\n"
                + (f"#define SF_JIT_TILE_SLOT {tiled.slot}      // {tiled.name}\n" if tiled else "") +
@@ -585,6 +587,7 @@ class _Translator:
                "};\n"
                "}}\n" + undefs +
                f"#define SF_JIT_DERIVATIVES {int(derivatives)}\n"
+               f"#define SF_JIT_AUDIO {int(audio)}\n"
                "SF_JIT_ENTRY_POINTS(sf::rt::Fragment)\n")
         return Translation(cpp, bindings, tiled.name if tiled else None)
 

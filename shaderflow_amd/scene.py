@@ -64,6 +64,7 @@ class ShaderScene(ShaderModule):
     """Scenes in which only the clock moves between frames take clockloop.ClockLoop (same frames, a fifth of the python per frame)"""
 
     tape_loop = None                                          # plain class attribute: the TapeLoop of the last main(), if it took one
+    tape_sequence = None                                      # … and the TapeSequence (tapesequence.py)
     _fused_this_frame: bool = False
     _skip_render: bool = False
     shard_warmup = "auto"                                     # plain class attribute: subclasses override it like `life_period`
@@ -340,6 +341,7 @@ class ShaderScene(ShaderModule):
         self.relay(ShaderMessage.Shader.Compile)
         self.scheduler.clear()
         self.tape_loop = None
+        self.tape_sequence = None
 
         _width, _height = self.resize(width=width, height=height, ratio=ratio, scale=scale)
 
@@ -381,6 +383,11 @@ class ShaderScene(ShaderModule):
         from shaderflow_amd.clockloop import ClockLoop
         if self.freewheel and batch is None and self.clock_loop and ClockLoop.applicable(self):
             return ClockLoop(self).run(export, turbo)
+        # audio-reactive layered / temporal / multi-program scenes without python logic: ClockLoop's native sequence on the tape (tapesequence.py)
+        from shaderflow_amd.tapesequence import TapeSequence
+        if batch is None and TapeSequence.applicable(self):
+            self.tape_sequence = TapeSequence(self)
+            return self.tape_sequence.run(export, turbo)
         # audio scenes with python logic of their own: the audio from the device tape, the user's update() frame by frame (tapeloop.py)
         from shaderflow_amd.tapeloop import TapeLoop
         if batch is None and TapeLoop.applicable(self):

@@ -10,7 +10,9 @@ scalars: the scheduler's float64 clock, the PCM chunk schedule, and the per-fram
 (branch selection, exp/cos — dynamics.py:231-242), rounded to float32 where numpy would round them.
 
 A scene qualifies when it is made only of the stock modules and nothing overrides `update()`/`pipeline()`;
-anything else runs through the frame loop (`ShaderScene.next`), which produces the same frames.
+anything else runs through the frame loop (`ShaderScene.next`), which produces the same frames. Out of scope here: a main texture
+with `temporal` or `layers` != 1 and programs besides the main one and `_final` — audio scenes of that kind without python logic take
+`TapeSequence` (tapesequence.py: this tape, drawn by the native clock sequence), those with python logic `TapeLoop` or the frame loop.
 
 `FrameTape.export` runs one function per delivery mode (`delivery_mode`): `export_single` (one process), `export_host` and
 `export_device` (sharded over a process group, parallel.py); each renders its batches as sink frames (exporting.SinkBatches).

@@ -30,7 +30,8 @@ A scene takes this loop when `main(batch=None)` finds neither FrameTape nor Cloc
 "0". Out of scope, so they keep the frame loop: more than one ShaderProgram, a main texture with temporal or layers != 1, subclasses of
 the audio modules, an overridden `next()` or `handle()`, scheduled tasks of the scene's own, sharded and non-freewheel runs, mono clips,
 an integrating spectrogram and `real` loudness systems (`applicable` says why). Rendering runs of consecutive frames with per-frame
-`user[]` uniforms in one launch is a separate change: here every frame is one launch.
+`user[]` uniforms in one launch is a separate change: here every frame is one launch. Layered, temporal and multi-program audio scenes
+WITHOUT python logic take `TapeSequence` (tapesequence.py) before this loop is asked.
 """
 from __future__ import annotations
 

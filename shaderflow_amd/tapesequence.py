@@ -1,0 +1,123 @@
+"""
+TapeSequence: the frame loop of audio-reactive layered, temporal and multi-program scenes without python logic (no reference equivalent).
+
+Three loops each stopped where the others began: `FrameTape` (tape.py) takes audio scenes of one program with one layer and no history,
+`ClockLoop` (clockloop.py) takes layered / temporal / multi-program scenes in which nothing but the clock moves, `TapeLoop`
+(tapeloop.py) takes audio scenes with python logic of one program. A trails or motion-blur fragment that reads `iSpectrogram`, a
+two-layer multipass driven by the volume, a child program that draws the spectrum for the main one to composite: those fell through
+all three into `ShaderScene.next`, which paid a device STFT, a host round trip, numpy DynamicNumber steps of every bin, the texture
+writes of the spectrogram and the waveform, and the pipeline walk, every frame.
+
+Here the device builds the audio state of a batch of frames exactly as an export's `FrameTape.build` does, and ClockLoop's native
+sequence draws the batch in chunks (`sfx_tape_sequence_run`): the same passes, clock ticks, rolled sampler tables, resolve and read-out
+as `sfx_clock_sequence_run`, except that a pass whose program reads audio (samples iSpectrogram / iWaveform, or reads iAudioVolume,
+iAudioVolumeIntegral, iAudioSTD, iSpectrogramOffset) takes frame k's audio state from tape frame k — a layered pass draws every layer
+into row 0 of its matrix, a fused one renders into iFinal through `sfx_render_tape`. Passes that read no audio are drawn as by
+ClockLoop. The next batch's build is queued right behind the last chunk of the current one and runs beside its draws.
+
+A scene takes this loop when `main(batch=None)` finds neither FrameTape nor ClockLoop applicable (before TapeLoop) and
+`SHADERFLOW_TAPE_SEQUENCE` is not "0". Out of scope, so they keep their loop: python `update()` logic (TapeLoop for one program, the frame
+loop otherwise), sharded runs, a main camera away from the identity pose (`TapeLoop.camera_at_identity` says why), several audio clips
+or spectrograms, and several frames per launch.
+"""
+from __future__ import annotations
+
+import os
+from typing import TYPE_CHECKING
+
+import numpy as np
+
+from shaderflow_amd.audio.module import ShaderAudio
+from shaderflow_amd.audio.spectrogram import ShaderSpectrogram
+from shaderflow_amd.audio.waveform import ShaderWaveform
+from shaderflow_amd.clockloop import ClockLoop
+from shaderflow_amd.parallel import is_sharded
+from shaderflow_amd.scheduler import freewheel_clock
+from shaderflow_amd.tape import FrameTape
+from shaderflow_amd.tapeloop import TapeLoop
+
+if TYPE_CHECKING:
+    from shaderflow_amd.exporting import ExportingHelper
+    from shaderflow_amd.scene import ShaderScene
+
+_AUDIO = (ShaderAudio, ShaderSpectrogram, ShaderWaveform)
+
+
+class TapeSequence:
+    @staticmethod
+    def applicable(scene: "ShaderScene") -> bool:
+        if os.environ.get("SHADERFLOW_TAPE_SEQUENCE", "1") == "0":
+            return False
+        if not scene.freewheel or is_sharded():
+            return False
+        # the audio modules of exact stock types (a subclass may update() differently from what the tape computes), and the two loudness
+        # systems they own: the tape computes them; everything else must be what ClockLoop takes
+        audios = [m for m in scene.modules if type(m) is ShaderAudio]
+        spectrograms = [m for m in scene.modules if type(m) is ShaderSpectrogram]
+        waveforms = [m for m in scene.modules if type(m) is ShaderWaveform]
+        if not audios:
+            return False
+        taped = frozenset(id(m) for m in (*audios, *spectrograms, *waveforms, *(s for a in audios for s in (a.volume, a.std))))
+        if not ClockLoop.applicable(scene, taped=taped):
+            return False
+        if not FrameTape.audio_fits(audios, spectrograms, waveforms):
+            return False
+        return TapeSequence.camera_at_identity(scene)
+
+    @staticmethod
+    def camera_at_identity(scene: "ShaderScene") -> bool:
+        """Whether the camera uniforms the modules yield are the identity pose's (TapeLoop.IDENTITY, compared as the float32 / int32
+        values a push would send). The camera cannot move here (ClockLoop.applicable), so its pose before the first frame is its pose."""
+        seen = {}
+        for module in scene.modules:
+            if module is scene:
+                continue
+            for variable in module.pipeline() or ():
+                if variable.name in TapeLoop.IDENTITY:
+                    seen[variable.name] = variable.value
+        for name, (dtype, want) in TapeLoop.IDENTITY.items():
+            if name not in seen or seen[name] is None:
+                continue
+            value = seen[name]
+            value = getattr(value, "value", value)                    # (an enum: its number)
+            if not np.array_equal(np.asarray(value, dtype=np.float64).astype(dtype).reshape(-1)[:len(want)], np.asarray(want, dtype)):
+                return False
+        return True
+
+    def __init__(self, scene: "ShaderScene"):
+        self.scene = scene
+        self.clock = ClockLoop(scene)                                  # the pass and matrix tables, the chunk size
+        self.tape = FrameTape(scene)
+        self.frames = 0                                                # frames drawn from the tape (tests, measurements)
+
+    def run(self, export: "ExportingHelper", turbo: bool):
+        scene, tape, clock = self.scene, self.tape, self.clock
+        total = export.total_frames
+        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
+        tape.prepare(total)
+        try:
+            if tape.spectrogram is not None and not tape.private_spectrogram:
+                tape.spectrogram.configure_texture()                  # what its first update() would do (FrameTape.bind_static_uniforms)
+            # frame 0's state through the ordinary pipeline walk: every uniform and sampler of every program is on the device
+            scene.time, scene.dt, scene.rdt = times[0], dts[0], rdts[0]
+            for program in clock.programs:
+                if program.program is None:
+                    program.compile()
+                if not program.texture.final:
+                    program.use_scene_pipeline()
+            from shaderflow_amd import _native as N
+            N.check(N.lib().sfx_tape_reset(tape.handle))
+            native = clock.native_sequence(export, turbo)
+            try:
+                clock.run_native(export, times, dts, rdts, total, tape=tape, pipe_here=not native, turbo=turbo)
+            finally:
+                for program in clock.programs:
+                    program._pushed.clear(); program._pushed_plain.clear(); program._module_tokens.clear()
+            self.frames = export.frame
+            # the clock of the last frame; the audio modules' host state and textures are as the export found them (FrameTape.export)
+            last = max(0, min(total, export.frame) - 1)
+            scene.time, scene.dt, scene.rdt = times[last], dts[last], dts[last]
+            return export.finish()
+        finally:
+            scene.context.synchronize()
+            tape.release()
