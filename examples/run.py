@@ -47,7 +47,15 @@ def main() -> None:
     audio = None
     if issubclass(cls, scenes._AudioScene):
         audio = args.audio if args.audio else (synth.sweep_clip(args.time, 44100), 44100)
-    scene = scenes.make(cls, audio=audio, device=local_rank)
+    if issubclass(cls, scenes.PianoRoll):
+        # the built-in score, through a MIDI file as a user's would come; the scene reads it while it is built
+        import tempfile
+        from shaderflow_amd.piano.midi import write_midi
+        with tempfile.TemporaryDirectory(prefix="shaderflow-") as folder:
+            scene = scenes.make(cls, score=write_midi(Path(folder)/"score.mid", scenes.demo_score(args.time)), device=local_rank)
+            scene.initialize()
+    else:
+        scene = scenes.make(cls, audio=audio, device=local_rank)
     started = time.perf_counter()
     result = scene.main(width=args.width, height=args.height, fps=args.fps, ssaa=args.ssaa, subsample=args.subsample, time=args.time, output=args.output)
     took = time.perf_counter() - started

@@ -284,9 +284,93 @@ class AudioTrails(_AudioScene):
         self.shader.texture.layers = 2
         self.shader.fragment = self.FRAGMENT
 
-def make(cls, audio=None, background=None, **fields):
+def demo_score(seconds: float = 8.0) -> list:
+    """A few bars for PianoRoll: a bass note per bar on channel 1 under broken chords on channel 0"""
+    from shaderflow_amd.piano import PianoNote
+    chords = ((48, 55, 60, 64, 67), (45, 52, 57, 60, 64), (41, 48, 53, 57, 60), (43, 50, 55, 59, 62))
+    notes, bar = [], 0
+    while 2.0*bar < seconds:
+        start, chord = 2.0*bar, chords[bar % 4]
+        notes.append(PianoNote(note=chord[0] - 12, start=start, end=start + 1.9, channel=1, velocity=70))
+        for k in range(8):
+            pitch = chord[1 + (3*k) % 4] + (12 if k % 4 == 3 else 0)
+            notes.append(PianoNote(note=pitch, start=start + 0.25*k, end=start + 0.25*k + 0.22, channel=0, velocity=60 + 10*(k % 4)))
+        bar += 1
+    return notes
+
+
+class PianoRoll(ShaderScene):
+    """A piano roll (not one of the reference's, which ships the module without a scene): a keyboard strip whose keys light up in the
+    colour of the channel that plays them, and above it the notes of the next `roll_time` seconds falling onto the keys. The fragment
+    reads what ShaderPiano exports: iPianoKeys / iPianoChan per key, iPianoRoll per (slot, pitch), the note range iPianoDynamic.
+    `score`: PianoNotes, or the path of a MIDI file. No python logic between frames: the score lives on the device and the frames come
+    from the native piano sequence (shaderflow_amd/pianosequence.py)."""
+    score = None
+    FRAGMENT = """
+        bool blackKey(int note) {
+            int k = note % 12;
+            return k == 1 || k == 3 || k == 6 || k == 8 || k == 10;
+        }
+        vec3 channelColour(float channel) {
+            return 0.55 + 0.45*cos(TAU*(0.19*channel + vec3(0.0, 0.33, 0.67)));
+        }
+        void main() {
+            // the keys on screen: the note range the module follows, and a margin on both sides
+            float low = iPianoDynamic.x - iPianoExtra;
+            float high = iPianoDynamic.y + iPianoExtra + 1.0;
+            float key = mix(low, high, astuv.x);
+            int note = int(floor(key));
+            float across = fract(key);
+            vec3 colour = vec3(0.05, 0.05, 0.08);
+            if (note < 0 || note > 127) {
+                fragColor = vec4(colour, 1.0);
+                return;
+            }
+            bool black = blackKey(note);
+            float gap = smoothstep(0.0, 0.08, across)*smoothstep(0.0, 0.08, 1.0 - across);
+            if (astuv.y < iPianoHeight) {
+                // the keyboard strip: a black key covers the upper part of its column
+                float up = astuv.y/iPianoHeight;
+                float pressed = clamp(texelFetch(iPianoKeys, ivec2(note, 0), 0).x/100.0, 0.0, 1.0);
+                float channel = texelFetch(iPianoChan, ivec2(note, 0), 0).x;
+                bool dark = black && up > 1.0 - iPianoBlackRatio;
+                vec3 rest = dark ? vec3(0.07) : vec3(0.9);
+                vec3 lit = channel < 0.0 ? rest : channelColour(channel);
+                colour = mix(rest, lit, pressed)*mix(0.55, 1.0, gap)*(0.8 + 0.2*up);
+            } else {
+                // the roll: height above the strip is time ahead of now
+                float when = iTime + iPianoRollTime*(astuv.y - iPianoHeight)/(1.0 - iPianoHeight);
+                colour += black ? vec3(0.0) : vec3(0.025);
+                for (int slot = 0; slot < iPianoLimit; slot++) {
+                    vec4 entry = texelFetch(iPianoRoll, ivec2(slot, note), 0);
+                    if (entry.y == 0.0 && entry.w == 0.0)
+                        break;
+                    if (when >= entry.x && when <= entry.y)
+                        colour = channelColour(entry.z)*(0.45 + 0.55*entry.w/127.0)*mix(0.3, 1.0, gap);
+                }
+            }
+            fragColor = vec4(colour, 1.0);
+        }
+    """
+
+    def build(self):
+        from shaderflow_amd.piano import ShaderPiano
+        super().build()
+        self.piano = ShaderPiano(scene=self)
+        score = demo_score() if self.score is None else self.score
+        if isinstance(score, (str, Path)):
+            self.piano.load_midi(score)
+        else:
+            for note in score:
+                self.piano.add_note(note)
+        self.shader.fragment = self.FRAGMENT
+
+
+def make(cls, audio=None, background=None, score=None, **fields):
     """Build a scene class with its inputs set before `build()` runs (class attributes, like demo.py's Life)"""
     attrs = {}
+    if score is not None:
+        attrs["score"] = score
     if audio is not None:
         attrs["audio_source"] = audio
     if background is not None:

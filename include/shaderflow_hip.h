@@ -376,6 +376,45 @@ int sfx_tape_sequence_run(sfx_handle ctx, const sfx_sequence_pass* passes, int n
                           const sfx_clock_tick* clock, int nframes, sfx_handle tape, int frame0, sfx_handle ring, int first_slot, int fd,
                           void* const* planar_slots, int yuv_matrix, int width, int height);
 
+/* ------------------------------------------------------------------------------------------------ */
+/* Piano roll — ShaderPiano.update() (reference: shaderflow/piano/module.py:185-277) on the device. The score is uploaded once; one
+ * kernel launch per frame (k_piano_frame, one block per pitch) selects the frame's candidate notes, writes iPianoRoll, iPianoChan and
+ * iPianoKeys straight into the module's three textures, and steps the key-press DynamicNumber, whose state the handle owns. The
+ * note-range DynamicNumber (iPianoDynamic, two values) stays on the host. */
+typedef struct {
+    double time_offset, roll_time, lookahead, release_before_end;       /* the module's fields (module.py:25-60) */
+} sfx_piano_params;
+/* The notes grouped by pitch, insertion order kept inside a pitch: first[128 + 1] are CSR offsets into start / end / channel / velocity
+ * (float64 times: update() compares them with the float64 clock); sorted[count] lists, pitch by pitch, the same indices ordered by
+ * (trunc(start), insertion index). keys / chan (128 x 1 R32F) and roll (256 x 128 RGBA32F) are the textures the frames are written into.
+ * state: [5][128] float32 = value, derivative, previous, acceleration, target of the key-press DynamicNumber (NULL: zeros). */
+int sfx_piano_create(sfx_handle ctx, const int32_t* first, const int32_t* sorted, const double* start, const double* end,
+                     const float* channel, const float* velocity, int count, const sfx_piano_params* params,
+                     sfx_handle keys, sfx_handle chan, sfx_handle roll, const float* state, sfx_handle* piano);
+/* One frame at scene.time = `scene_time` (the module's time_offset is added here), queued on the context's stream. coeff: the python
+ * scalars of DynamicNumber.next for dt = abs(scene.dt), rounded to float32 (dt == 0: no step, reference dynamics.py:210-211). The step assumes
+ * precision == 0 and no integral. previous_is_target: the host object's `previous` IS its `target` array (it is after its first step,
+ * reference dynamics.py:229), so that update()'s refill of the target moves both. */
+int sfx_piano_step(sfx_handle piano, double scene_time, const sfx_dyn_coeff_f32* coeff, int previous_is_target);
+int sfx_piano_state_read(sfx_handle piano, float* state /* [5][128] */);   /* waits for the context's stream */
+int sfx_piano_destroy(sfx_handle piano);
+
+/* What frame f of a piano sequence adds to its clock tick: the frame's scene.time in float64, the key-press coefficients, and
+ * iPianoDynamic — stepped by the host for all frames up front — for every program that declares it. */
+typedef struct {
+    double time;
+    sfx_dyn_coeff_f32 coeff;
+    float dynamic[2];
+    int32_t previous_is_target;
+    int32_t reserved;                /* padding only: the record is 40 bytes, a multiple of the double's alignment */
+} sfx_piano_tick;
+/* sfx_clock_sequence_run for a scene with one ShaderPiano: per frame, in front of the first pass, the piano's frame (sfx_piano_step) and
+ * dynamic[] stored into the uniform `dynamic_name` ("iPianoDynamic") of every pass' program that has one; then the frame as
+ * sfx_clock_sequence_run draws it. */
+int sfx_piano_sequence_run(sfx_handle ctx, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
+                           const sfx_clock_tick* clock, int nframes, sfx_handle piano, const sfx_piano_tick* ticks, const char* dynamic_name,
+                           sfx_handle ring, int first_slot, int fd, void* const* planar_slots, int yuv_matrix, int width, int height);
+
 /* Device memory helper for callers without their own allocator */
 int sfx_device_alloc(sfx_handle ctx, size_t nbytes, void** ptr);
 int sfx_device_free(sfx_handle ctx, void* ptr);

@@ -68,6 +68,14 @@ class ClockTick(C.Structure):
 PASS_LAYERS, PASS_FUSED, PASS_RESOLVE = 0, 1, 2
 
 
+class PianoParams(C.Structure):
+    _fields_ = [("time_offset", C.c_double), ("roll_time", C.c_double), ("lookahead", C.c_double), ("release_before_end", C.c_double)]
+
+
+class PianoTick(C.Structure):
+    _fields_ = [("time", C.c_double), ("coeff", DynCoeffF32), ("dynamic", C.c_float*2), ("previous_is_target", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Binding(C.Structure):
     """sfx_binding (include/shaderflow_hip.h): a uniform or sampler name of a loaded program"""
     _fields_ = [("name", C.c_char_p), ("sampler", C.c_int), ("slot", C.c_int), ("count", C.c_int), ("integer", C.c_int)]
@@ -175,6 +183,13 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_render_tape": (C.c_int, [Handle, Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sfx_tape_sequence_run": (C.c_int, [Handle, P(SequencePass), C.c_int, P(SequenceMatrix), C.c_int, P(ClockTick), C.c_int, Handle, C.c_int, Handle,
                                         C.c_int, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int]),
+    "sfx_piano_create": (C.c_int, [Handle, P(C.c_int32), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_float), P(C.c_float), C.c_int, P(PianoParams),
+                                   Handle, Handle, Handle, P(C.c_float), P(Handle)]),
+    "sfx_piano_step": (C.c_int, [Handle, C.c_double, P(DynCoeffF32), C.c_int]),
+    "sfx_piano_state_read": (C.c_int, [Handle, P(C.c_float)]),
+    "sfx_piano_destroy": (C.c_int, [Handle]),
+    "sfx_piano_sequence_run": (C.c_int, [Handle, P(SequencePass), C.c_int, P(SequenceMatrix), C.c_int, P(ClockTick), C.c_int, Handle, P(PianoTick), C.c_char_p,
+                                         Handle, C.c_int, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),
     "sfx_device_free": (C.c_int, [Handle, C.c_void_p]),
     "sfx_device_copy": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_size_t]),

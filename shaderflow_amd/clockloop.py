@@ -131,9 +131,12 @@ class ClockLoop:
         return all(program.program is not None for program in self.programs)
 
     def run_native(self, export: "ExportingHelper", times, dts, rdts, total: int, tape: "Optional[FrameTape]" = None, pipe_here: bool = False,
-                   turbo: bool = True) -> None:
+                   turbo: bool = True, piano=None) -> None:
         """With a `tape` (tapesequence.py) the frames go in the tape's batches: each batch is built, then drawn by sfx_tape_sequence_run in
-        chunks that stay inside it. `pipe_here`: one frame per call, read out by export.pipe (a progress relay, no turbo)"""
+        chunks that stay inside it. `pipe_here`: one frame per call, read out by export.pipe (a progress relay, no turbo).
+        With a `piano` (pianosequence.py: `.handle`, `.ticks(first, count)` = the frames' sfx_piano_tick table, `.dynamic_name` = the module's
+        `<name>Dynamic` uniform) every chunk is drawn by
+        sfx_piano_sequence_run."""
         scene, lib = self.scene, N.lib()
         runtime, fps = scene.runtime, scene.fps
         # texture matrices: every program's own (its draws go to row 0) — the same objects `rolling` lists when they are temporal
@@ -181,7 +184,11 @@ class ClockLoop:
                     time = times[done + i]
                     ticks[i] = N.ClockTick(time, (time/runtime) % 1.0, dts[done + i], round(time*fps))
                 ring, slot, fd = export.ring if piping else N.Handle(), export.frame % max(1, export.slots), export.fileno if piping else -1
-                if tape is None:
+                if piano is not None:
+                    N.check(lib.sfx_piano_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
+                                                       piano.handle, piano.ticks(done, count), piano.dynamic_name, ring, slot, fd, planar,
+                                                       1 if export.yuv_matrix == "bt709" else 0, scene.width, scene.height))
+                elif tape is None:
                     N.check(lib.sfx_clock_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
                                                        ring, slot, fd, planar, 1 if export.yuv_matrix == "bt709" else 0, scene.width, scene.height))
                 else:

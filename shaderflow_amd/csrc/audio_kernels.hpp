@@ -13,6 +13,7 @@
 #pragma once
 
 #include "glsl.hpp"
+#include "dynamics_step.hpp"
 
 namespace sf {
 
@@ -345,7 +346,7 @@ __global__ __launch_bounds__(256) void k_volume_std(const float* __restrict__ pc
 // The recurrence is sequential in time (an IIR with a data-dependent early-out, dynamics.py:222-225), so one
 // block walks the frames of the batch; the per-frame python scalars (dt, k1, k2, k3) come from the host,
 // already rounded to float32 the way numpy does for a float32 array (NEP 50).
-struct DynCoeffF32 { float dt, k1, k2, k3; };
+// (DynCoeffF32 and the float32 step itself: dynamics_step.hpp — k_piano_frame runs the same step)
 struct DynCoeffF64 { double dt, k1, k2, k3; };
 struct FrameClock { float iTime, iTau, iSpectrogramOffset; int iFrame; };
 struct ScalarState { double value, derivative, previous, integral; };
@@ -453,11 +454,7 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
             if (!skip) {
 #pragma unroll
                 for (int e = 0; e < PER; e++) {
-                    const float velocity = (target[e] - prev[e])/c.dt;
-                    prev[e] = target[e];
-                    value[e] = value[e] + (deriv[e]*c.dt);
-                    const float accel = (((target[e] + (c.k3*velocity)) - value[e]) - (c.k1*deriv[e]))/c.k2;
-                    deriv[e] = deriv[e] + (accel*c.dt);
+                    const float accel = dynamics_step_f32(value[e], deriv[e], prev[e], target[e], c);
                     if constexpr (SNAPSHOT) accel_kept[e] = accel;
                 }
             }

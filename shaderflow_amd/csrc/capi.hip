@@ -1061,8 +1061,10 @@ static int render_tape_box(Program* p, const TapeView* t, int frame, Texture* ta
 // every other pass is drawn exactly as without a tape.
 static int run_sequence(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
                         const sfx_clock_tick* clock, int nframes, sfx_handle ht, int frame0, sfx_handle hring, int first_slot, int fd,
-                        void* const* planar_slots, int yuv_matrix, int width, int height) {
+                        void* const* planar_slots, int yuv_matrix, int width, int height,
+                        sfx_handle hpiano = 0, const sfx_piano_tick* piano_ticks = nullptr, const char* dynamic_name = nullptr) {
     CTX_OR_FAIL(c, hc);
+    if (hpiano && !piano_ticks) return fail(SFX_E_INVALID, "piano sequence: null tick table");
     const int ring_slots = hring ? ring_slot_count(hring) : 0;
     if (!passes || npasses < 1 || nmatrices < 0 || (nmatrices && !matrices) || !clock || nframes < 0) return fail(SFX_E_INVALID, "clock sequence: null tables");
     if (ring_slots < 0) return fail(SFX_E_INVALID, "clock sequence: invalid ring handle");
@@ -1106,6 +1108,18 @@ static int run_sequence(sfx_handle hc, const sfx_sequence_pass* passes, int npas
             }
         }
     }
+    // where iPianoDynamic lives in the user[] block of every program that declares it, resolved once like the sampler slots (the
+    // stock fragments declare none: a translated one by its bindings)
+    struct DynamicSlot { Program* p; int slot; };
+    std::vector<DynamicSlot> dynamic_slots;
+    if (hpiano && dynamic_name) {
+        for (int k = 0; k < npasses; k++) {
+            Program* p = passes[k].kind == SFX_PASS_RESOLVE ? nullptr : get<Program>(passes[k].program, MAGIC_PROG);
+            if (!p) continue;
+            for (const auto& b : p->bindings)
+                if (!b.sampler && !b.integer && b.count >= 2 && b.name == dynamic_name) dynamic_slots.push_back({p, b.slot});
+        }
+    }
     // the bank was filled on the tape's stream: the draws wait for its last audio kernel, and the build that refills it waits for
     // the mark behind the last kernel of this call (as in sfx_render_tape)
     if (t) HIP_TRY(hipStreamWaitEvent(c->stream, t->built, 0));
@@ -1113,6 +1127,14 @@ static int run_sequence(sfx_handle hc, const sfx_sequence_pass* passes, int npas
     for (int f = 0; f < nframes; f++) {
         const sfx_clock_tick& now = clock[f];
         bool fused = false;
+        if (hpiano) {
+            // ShaderPiano.update() of the frame (scene.next updates every module before any program renders): the three textures on the
+            // render stream, in front of the draws that sample them, and iPianoDynamic as the pipeline walk would have pushed it
+            const sfx_piano_tick& tick = piano_ticks[f];
+            const int rc = piano_launch_frame(hpiano, c, tick.time, tick.coeff, tick.previous_is_target);
+            if (rc) return rc;
+            for (const DynamicSlot& d : dynamic_slots) { d.p->u.user[d.slot] = tick.dynamic[0]; d.p->u.user[d.slot + 1] = tick.dynamic[1]; }
+        }
         for (int k = 0; k < npasses; k++) {
             const sfx_sequence_pass& pass = passes[k];
             if (pass.kind == SFX_PASS_RESOLVE) {
@@ -1158,6 +1180,15 @@ extern "C" int sfx_clock_sequence_run(sfx_handle hc, const sfx_sequence_pass* pa
                                       const sfx_clock_tick* clock, int nframes, sfx_handle hring, int first_slot, int fd,
                                       void* const* planar_slots, int yuv_matrix, int width, int height) {
     return run_sequence(hc, passes, npasses, matrices, nmatrices, clock, nframes, 0, 0, hring, first_slot, fd, planar_slots, yuv_matrix, width, height);
+}
+
+// The same loop for a scene with a ShaderPiano (pianosequence.py): k_piano_frame and iPianoDynamic in front of every frame
+extern "C" int sfx_piano_sequence_run(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
+                                      const sfx_clock_tick* clock, int nframes, sfx_handle hpiano, const sfx_piano_tick* ticks, const char* dynamic_name,
+                                      sfx_handle hring, int first_slot, int fd, void* const* planar_slots, int yuv_matrix, int width, int height) {
+    if (!hpiano) return fail(SFX_E_INVALID, "piano sequence: null piano handle");
+    return run_sequence(hc, passes, npasses, matrices, nmatrices, clock, nframes, 0, 0, hring, first_slot, fd, planar_slots, yuv_matrix, width, height,
+                        hpiano, ticks, dynamic_name);
 }
 
 // The same loop for audio scenes (tapesequence.py): the passes that read audio draw tape frames [frame0, frame0 + nframes)

@@ -19,7 +19,7 @@ int launch_status();                              // hipGetLastError() after a l
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(SFX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 enum : uint32_t { MAGIC_CTX = 0x53465843, MAGIC_TEX = 0x53465854, MAGIC_PROG = 0x53465850, MAGIC_RING = 0x53465852,
-                  MAGIC_AUDIO = 0x53465841, MAGIC_PLAN = 0x5346584c, MAGIC_TAPE = 0x53465854 + 0x100, MAGIC_SHM = 0x53465853 };
+                  MAGIC_AUDIO = 0x53465841, MAGIC_PLAN = 0x5346584c, MAGIC_TAPE = 0x53465854 + 0x100, MAGIC_SHM = 0x53465853, MAGIC_PIANO = 0x53465850 + 0x100 };
 
 struct Object { uint32_t magic; };
 
@@ -89,3 +89,5 @@ struct TapeView {
 };
 bool tape_view(sfx_handle tape, TapeView* view);
 int tape_screen_scratch(sfx_handle tape, size_t bytes, hipStream_t stream, void** screen);   // iScreen of the two-pass path, grown on demand
+// capi_piano.hip: k_piano_frame for one frame on the context's render stream (the piano sequence launches it in front of the frame's draws)
+int piano_launch_frame(sfx_handle piano, Context* c, double scene_time, const sfx_dyn_coeff_f32& coeff, int previous_is_target);

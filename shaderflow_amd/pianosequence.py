@@ -1,0 +1,277 @@
+"""
+PianoSequence: the frame loop of piano-roll scenes without python logic (no reference equivalent).
+
+`ShaderPiano.update()` (piano/module.py) runs on the host every frame: a handful of numpy selections over the whole score, two
+`DynamicNumber` steps, and three texture uploads — iPianoRoll alone is 128 x 256 x RGBA32F = 512 KB a frame. No fast loop knew the
+module, so a scene with a piano always took `ShaderScene.next`.
+
+Here the score lives in device memory (`sfx_piano_create`), and ClockLoop's native sequence draws the frames in chunks
+(`sfx_piano_sequence_run`): in front of every frame's passes one launch of `k_piano_frame` (csrc/piano_kernels.hpp) restates that
+frame's `update()` — candidates, rolling slots, channel and target velocity per key, one step of the key-press `DynamicNumber` —
+straight into the module's own three textures, on the render stream, so the draws behind it sample the frame's content. The frames
+are the frame loop's byte for byte.
+
+What stays on the host is `iPianoDynamic`, the note range: two float32 values chasing the lowest and highest candidate pitch. Its
+targets for every frame of the export come from one vectorised pass over frames x notes (`note_range_targets`), its recurrence from
+the module's own `DynamicNumber.next`, before the first frame; the native call stores frame k's pair into the uniform of every
+program that declares it.
+
+A scene takes this loop when `main(batch=None)` finds it applicable (after ClockLoop, before TapeSequence) and
+`SHADERFLOW_PIANO_SEQUENCE` is not "0". Out of scope, so they keep the frame loop: python `update()` logic, a subclass of ShaderPiano,
+several pianos, audio modules beside the piano (joining this hook to `sfx_tape_sequence_run` is the follow-up), sharded runs, and a
+key-press system whose early-out can fire (`precision != 0`) or that integrates.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from copy import deepcopy
+from typing import TYPE_CHECKING
+
+import numpy as np
+
+from shaderflow_amd import _native as N
+from shaderflow_amd.clockloop import ClockLoop
+from shaderflow_amd.parallel import is_sharded
+from shaderflow_amd.piano.module import MAX_NOTE, MAX_ROLLING, ShaderPiano
+from shaderflow_amd.scheduler import freewheel_clock
+from shaderflow_amd.tape import _coefficients_f32
+
+if TYPE_CHECKING:
+    from shaderflow_amd.exporting import ExportingHelper
+    from shaderflow_amd.scene import ShaderScene
+
+# sfx_piano_tick (include/shaderflow_hip.h) as a numpy record: the table of an export is filled without a python loop
+TICK = np.dtype([("time", "f8"), ("coeff", [("dt", "f4"), ("k1", "f4"), ("k2", "f4"), ("k3", "f4")]), ("dynamic", "f4", (2,)),
+                 ("previous_is_target", "i4"), ("reserved", "i4")])
+assert TICK.itemsize == C.sizeof(N.PianoTick)
+
+STATE = ("value", "derivative", "previous", "acceleration", "target")       # the handle's [5][128] float32, in this order
+
+
+def group_by_pitch(pitch: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(first, order): CSR offsets `first[p] … first[p + 1]` into `order`, the note indices grouped by pitch with the insertion order
+    kept inside a pitch (a stable sort)"""
+    pitch = np.asarray(pitch, np.int64)
+    order = np.argsort(pitch, kind="stable")
+    first = np.searchsorted(pitch[order], np.arange(MAX_NOTE + 1)).astype(np.int32)
+    return first, order
+
+
+def start_sorted(first: np.ndarray, start: np.ndarray) -> np.ndarray:
+    """For notes already grouped by pitch: per pitch, their positions ordered by (whole second of the start, insertion index) — the order
+    in which the reference's bucket walk meets the notes that begin after the window's first second"""
+    start = np.asarray(start, np.float64)
+    group = np.repeat(np.arange(MAX_NOTE), np.diff(first))
+    return np.lexsort((np.arange(len(start)), np.trunc(start), group)).astype(np.int32)
+
+
+def note_range_targets(table: dict, times, lookup_time: float, block: int = 1 << 22) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(lowest, highest, any) candidate pitch of every frame: what `update()` calls pitch.min() / pitch.max() of `_candidates(table, time,
+    time + lookup_time)`, for all `times` (already offset by time_offset). The whole-second test of `_candidates` is the same for every
+    frame whose window [int(time), int(time + lookup_time)] is the same, so the frames are taken window by window: one pass over the
+    score picks the window's notes, and only those are compared with each frame's `time + lookup_time`, `block` comparisons at a time."""
+    times = np.asarray(times, np.float64)
+    lowest, highest = np.full(len(times), MAX_NOTE, np.int64), np.full(len(times), -1, np.int64)
+    if len(table["pitch"]) and len(times):
+        pitch, start, first, last = table["pitch"], table["start"], table["first"], table["last"]
+        ends = times + lookup_time
+        windows, member = np.unique(np.stack([np.trunc(times), np.trunc(ends)], axis=1), axis=0, return_inverse=True)
+        by_window = np.argsort(member.ravel(), kind="stable")
+        bounds = np.searchsorted(member.ravel()[by_window], np.arange(len(windows) + 1))
+        for g, (low, high) in enumerate(windows):
+            inside = np.flatnonzero((first <= high) & (last >= low))
+            if not len(inside):
+                continue
+            frames = by_window[bounds[g]:bounds[g + 1]]
+            rows = max(1, block//len(inside))
+            for at in range(0, len(frames), rows):
+                some = frames[at:at + rows]
+                mask = ~(start[inside][None, :] > ends[some, None])
+                lowest[some] = np.where(mask, pitch[inside][None, :], MAX_NOTE).min(axis=1)
+                highest[some] = np.where(mask, pitch[inside][None, :], -1).max(axis=1)
+    return lowest, highest, highest >= 0
+
+
+def step_note_range(piano: ShaderPiano, times, dts) -> np.ndarray:
+    """`update()`'s lines for the note range (module.py:190-197) for every frame: the module's own DynamicNumber stepped through the
+    export; returns the (frames, 2) float32 values `pipeline()` yields as iPianoDynamic frame by frame"""
+    dynamics = piano.note_range_dynamics
+    lowest, highest, found = note_range_targets(piano._table(), [time + piano.time_offset for time in times], piano.lookup_time)
+    out = np.zeros((len(times), 2), np.float32)
+    for k in range(len(times)):
+        dynamics.frequency = 0.5/piano.lookup_time
+        if sum(dynamics.value) == 0:
+            dynamics.value[:] = (piano.global_minimum_note, piano.global_maximum_note)
+        dynamics.target[:] = (lowest[k], highest[k]) if found[k] else (piano.global_minimum_note, piano.global_maximum_note)
+        dynamics.next(dt=abs(dts[k]))
+        out[k] = dynamics.value
+    return out
+
+
+class PianoSequence:
+    @staticmethod
+    def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
+        if os.environ.get("SHADERFLOW_PIANO_SEQUENCE", "1") == "0":
+            return False
+        if not scene.freewheel or is_sharded() or not turbo or (export is not None and export.relay is not None):
+            return False
+        pianos = [m for m in scene.modules if isinstance(m, ShaderPiano)]
+        if len(pianos) != 1 or type(pianos[0]) is not ShaderPiano:     # (a subclass may update() differently from what the kernel computes)
+            return False
+        piano = pianos[0]
+        textures = (piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture)
+        if any(texture is None for texture in textures):
+            return False
+        # everything else must be what ClockLoop takes: no python logic, no audio modules, no other module type
+        if not ClockLoop.applicable(scene, taped=frozenset(id(m) for m in (piano, *textures))):
+            return False
+        from shaderflow_amd.shader import ShaderProgram
+        if not all(m.program is not None for m in scene.modules if isinstance(m, ShaderProgram)):
+            return False
+        if (piano.keys_texture.size, piano.channel_texture.size, piano.roll_texture.size) != ((MAX_NOTE, 1), (MAX_NOTE, 1), (MAX_ROLLING, MAX_NOTE)):
+            return False
+        # the key-press system as the kernel steps it: 128 float32 values, an early-out that cannot fire (its maximum runs over ALL keys:
+        # at precision 0 the blocks are independent), no integral
+        keys = piano.key_press_dynamics
+        if keys.precision != 0 or keys.integrate:
+            return False
+        for name in STATE:
+            field = getattr(keys, name)
+            if not isinstance(field, np.ndarray) or field.dtype != np.float32 or field.shape != (MAX_NOTE,):
+                return False
+        note_range = piano.note_range_dynamics
+        if not all(isinstance(getattr(note_range, name), np.ndarray) and getattr(note_range, name).shape == (2,) for name in ("value", "target")):
+            return False
+        table = piano._table()
+        if len(table["pitch"]):
+            if table["pitch"].min() < 0 or table["pitch"].max() >= MAX_NOTE:
+                return False                                          # (update() would wrap or raise)
+            if not (np.isfinite(table["start"]).all() and np.isfinite(table["end"]).all()):
+                return False
+        return True
+
+    def __init__(self, scene: "ShaderScene"):
+        self.scene = scene
+        self.clock = ClockLoop(scene)                                  # the pass and matrix tables, the chunk size
+        self.piano = next(m for m in scene.modules if type(m) is ShaderPiano)
+        self.handle = None
+        self.frames = 0                                                # frames drawn by the native sequence (tests, measurements)
+        self._ticks = None
+        self._aliased = None                                           # `previous is target` on the host object, as the device has stepped so far
+        self.dynamic_name = f"{self.piano.name}Dynamic".encode()       # the uniform ShaderPiano.pipeline() yields the note range under
+
+    # the device side ----------------------------------------------------------------------------------------------------------------
+
+    def upload(self) -> None:
+        """The score as structure-of-arrays grouped by pitch, the module's parameters and the key-press state → sfx_piano_create"""
+        piano, keys = self.piano, self.piano.key_press_dynamics
+        table = piano._table()
+        first, order = group_by_pitch(table["pitch"])
+        start, end = np.ascontiguousarray(table["start"][order]), np.ascontiguousarray(table["end"][order])
+        # (channel and velocity reach the textures and the target as float32: the same rounding of the table's float64 as update()'s)
+        channel = np.ascontiguousarray(table["channel"][order].astype(np.float32))
+        velocity = np.ascontiguousarray(table["velocity"][order].astype(np.float32))
+        by_start = start_sorted(first, start)
+        params = N.PianoParams(float(piano.time_offset), float(piano.roll_time), float(piano.lookahead), float(piano.release_before_end))
+        state = np.ascontiguousarray(np.stack([np.asarray(getattr(keys, name), np.float32) for name in STATE]))
+        handle = N.Handle()
+        N.check(N.lib().sfx_piano_create(
+            self.scene.context.handle, N.as_ptr(first, C.c_int32), N.as_ptr(by_start, C.c_int32), N.as_ptr(start, C.c_double), N.as_ptr(end, C.c_double),
+            N.as_ptr(channel, C.c_float), N.as_ptr(velocity, C.c_float), len(start), C.byref(params),
+            piano.keys_texture.texture.handle, piano.channel_texture.texture.handle, piano.roll_texture.texture.handle,
+            N.as_ptr(state, C.c_float), C.byref(handle)))
+        self.handle = handle
+
+    def release(self) -> None:
+        if self.handle is not None and self.handle.value:
+            N.lib().sfx_piano_destroy(self.handle)
+        self.handle = None
+
+    def step(self, time: float, dt: float) -> None:
+        """One frame on its own (`sfx_piano_step`): the three textures and the key-press state for scene.time = `time`, scene.dt = `dt`.
+        The host object's state follows with `read_state()`."""
+        keys = self.piano.key_press_dynamics
+        coeff = _coefficients_f32(keys, [dt])
+        aliased = self._aliased if self._aliased is not None else (keys.previous is keys.target)
+        N.check(N.lib().sfx_piano_step(self.handle, float(time), N.as_ptr(coeff, N.DynCoeffF32), int(aliased)))
+        self._aliased = aliased or bool(abs(dt))
+
+    def read_state(self) -> None:
+        """The key-press DynamicNumber as the frame loop would have left it (`sfx_piano_state_read`), and the host copies of the three
+        textures' last full write"""
+        piano, keys = self.piano, self.piano.key_press_dynamics
+        state = np.zeros((len(STATE), MAX_NOTE), np.float32)
+        N.check(N.lib().sfx_piano_state_read(self.handle, N.as_ptr(state, C.c_float)))
+        for name, row in zip(STATE, state):
+            setattr(keys, name, row.copy())
+        if self._aliased:
+            keys.previous = keys.target                                # reference dynamics.py:229 — one array under two names
+        for texture in (piano.keys_texture, piano.channel_texture, piano.roll_texture):
+            box = texture.get_box()
+            box.data, box.empty = box.texture.read().tobytes(), False
+
+    def ticks(self, first: int, count: int):
+        return self._ticks[first:first + count].ctypes.data_as(C.POINTER(N.PianoTick))
+
+    # the export ---------------------------------------------------------------------------------------------------------------------
+
+    def run(self, export: "ExportingHelper", turbo: bool):
+        scene, clock, piano = self.scene, self.clock, self.piano
+        keys, note_range = piano.key_press_dynamics, piano.note_range_dynamics
+        total = export.total_frames
+        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
+        try:
+            # frame 0's state through the ordinary pipeline walk: every uniform and sampler of every program is on the device
+            scene.time, scene.dt, scene.rdt = times[0], dts[0], rdts[0]
+            for program in clock.programs:
+                if program.program is None:
+                    program.compile()
+                if not program.texture.final:
+                    program.use_scene_pipeline()
+            self.upload()
+            # the per-frame table: the clock in float64, the key-press coefficients, iPianoDynamic of every frame
+            before = {name: deepcopy(getattr(note_range, name)) for name in ("value", "target", "previous", "derivative", "acceleration", "frequency")}
+            range_aliased = note_range.previous is note_range.target
+            dynamic = step_note_range(piano, times, dts)
+            coeff = _coefficients_f32(keys, dts)
+            moved = np.asarray([bool(abs(dt)) for dt in dts], bool)         # frames whose step runs (reference dynamics.py:210-211)
+            aliased_after = np.logical_or(keys.previous is keys.target, np.cumsum(moved) > 0)
+            ticks = np.zeros(max(1, total), TICK)
+            ticks["time"][:total], ticks["coeff"][:total], ticks["dynamic"][:total] = times, coeff, dynamic
+            ticks["previous_is_target"][:total] = np.concatenate([[keys.previous is keys.target], aliased_after[:-1]])
+            self._ticks = ticks
+            finished = False
+            try:
+                clock.run_native(export, times, dts, rdts, total, piano=self)
+                finished = True
+            finally:
+                for program in clock.programs:
+                    program._pushed.clear(); program._pushed_plain.clear(); program._module_tokens.clear()
+                # Whatever ended the run — the last frame, scene.quit, an encoder that died, a device error — the host objects are left at
+                # the last frame that was drawn: the note range was stepped through the whole export up front, so it goes back and is
+                # stepped again as far as the frames went; the key-press state and the textures' host copies are read from the device (which a
+                # native call that failed half-way may have left up to a chunk ahead).
+                self.frames = done = min(total, export.frame)
+                if done < total:
+                    for name, value in before.items():
+                        setattr(note_range, name, value)
+                    if range_aliased:
+                        note_range.previous = note_range.target
+                    step_note_range(piano, times[:done], dts[:done])
+                if done:
+                    self._aliased = bool(aliased_after[done - 1])
+                    try:
+                        self.read_state()
+                    except N.NativeError:
+                        if finished:                                   # (behind a failed run the device may not answer: the first error is the one to report)
+                            raise
+                    # the clock as scene.next leaves it behind the last frame (it integrates time AFTER the frame, reference scene.py:475-479):
+                    # what a frame more would have seen
+                    after = freewheel_clock(scene.fps, done + 1, scene.speed)
+                    scene.time, scene.dt, scene.rdt = after[0][done], after[1][done], after[2][done]
+            return export.finish()
+        finally:
+            scene.context.synchronize()
+            self.release()
+            self._ticks = None

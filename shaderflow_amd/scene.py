@@ -65,6 +65,7 @@ class ShaderScene(ShaderModule):
 
     tape_loop = None                                          # plain class attribute: the TapeLoop of the last main(), if it took one
     tape_sequence = None                                      # … and the TapeSequence (tapesequence.py)
+    piano_sequence = None                                     # … and the PianoSequence (pianosequence.py)
     _fused_this_frame: bool = False
     _skip_render: bool = False
     shard_warmup = "auto"                                     # plain class attribute: subclasses override it like `life_period`
@@ -342,6 +343,7 @@ class ShaderScene(ShaderModule):
         self.scheduler.clear()
         self.tape_loop = None
         self.tape_sequence = None
+        self.piano_sequence = None
 
         _width, _height = self.resize(width=width, height=height, ratio=ratio, scale=scale)
 
@@ -383,6 +385,11 @@ class ShaderScene(ShaderModule):
         from shaderflow_amd.clockloop import ClockLoop
         if self.freewheel and batch is None and self.clock_loop and ClockLoop.applicable(self):
             return ClockLoop(self).run(export, turbo)
+        # a ShaderPiano scene without python logic: the score on the device, its textures made in front of every frame's draws (pianosequence.py)
+        from shaderflow_amd.pianosequence import PianoSequence
+        if batch is None and PianoSequence.applicable(self, export, turbo):
+            self.piano_sequence = PianoSequence(self)
+            return self.piano_sequence.run(export, turbo)
         # audio-reactive layered / temporal / multi-program scenes without python logic: ClockLoop's native sequence on the tape (tapesequence.py)
         from shaderflow_amd.tapesequence import TapeSequence
         if batch is None and TapeSequence.applicable(self):
