@@ -199,21 +199,6 @@ int sfx_ring_destroy(sfx_handle ring);
  * capi_readout.hip, restated in the oracle. Half the bytes over PCIe and the pipe: ffmpeg takes `-pix_fmt yuv420p` rawvideo as it is. */
 int sfx_rgb_to_yuv420(sfx_handle ctx, const void* rgb, void* yuv, int width, int height, int frames, int matrix);
 
-/* The frame loop of a scene in which nothing but the clock moves (layered / temporal scenes without host logic: demo.py's Multipass,
- * MotionBlur, Life), `nframes` frames in ONE call: scene.next (scene.py:456-479) = every program's render (shader.py:388-405: a draw per
- * layer into row 0 of its texture matrix, then texture.roll(), texture.py:295-298), iFinal's resolve (shader.py:391-396), exporting.pipe
- * (exporting.py:151-174). `passes` in the order scene.next renders; `matrices[m].textures` is [temporal][layers] in the matrix' CURRENT
- * order (the call rolls its own copy: the host rolls its matrices by `nframes` afterwards), `names` the sampler name of every box or
- * NULL. `clock[f]` = iTime, iTau, iDeltatime, iFrame of frame f. With a ring and fd >= 0 every frame is read out and piped
- * (slot (first_slot + f) % slots; `planar_slots`: device staging per slot for yuv420p, or NULL for rgb24). */
-enum { SFX_PASS_LAYERS = 0, SFX_PASS_FUSED = 1, SFX_PASS_RESOLVE = 2 };
-typedef struct sfx_sequence_pass { sfx_handle program; int kind; int matrix; sfx_handle target; int ssaa; int subsample; } sfx_sequence_pass;
-typedef struct sfx_sequence_matrix { int temporal, layers; const sfx_handle* textures; const char* const* names; } sfx_sequence_matrix;
-typedef struct sfx_clock_tick { float time, tau, deltatime; int32_t frame; } sfx_clock_tick;      /* sfx_uniform_set_clock's arguments */
-int sfx_clock_sequence_run(sfx_handle ctx, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                           const sfx_clock_tick* clock, int nframes, sfx_handle ring, int first_slot, int fd,
-                           void* const* planar_slots, int yuv_matrix, int width, int height);
-
 /* ------------------------------------------------------------------------------------------------ */
 /* Cross-process frame queue of a sharded export (one process per GPU; no reference equivalent). The sink takes
  * one byte stream, so one process owns it (rank 0) — but every rank reads its finished frames out over its OWN PCIe link into a
@@ -367,15 +352,6 @@ int sfx_tape_destroy(sfx_handle tape);
 int sfx_render_tape(sfx_handle program, sfx_handle tape, int frame0, int nframes,
                     int width, int height, int ssaa_x1000, int subsample, void* device_out);
 
-/* sfx_clock_sequence_run for audio scenes (layered / temporal / several programs, no host logic): frame f of the call is tape frame
- * frame0 + f of the bank the last sfx_tape_build filled. A pass whose program samples iSpectrogram / iWaveform or reads an audio uniform
- * (iAudioVolume, iAudioVolumeIntegral, iAudioSTD, iSpectrogramOffset) takes them from that tape frame — a layered pass draws each layer
- * into row 0 of its matrix, a fused one is sfx_render_tape into the pass' target; every other pass is drawn as by
- * sfx_clock_sequence_run. The call waits for the bank's build and marks the bank rendered behind its last kernel, as sfx_render_tape. */
-int sfx_tape_sequence_run(sfx_handle ctx, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                          const sfx_clock_tick* clock, int nframes, sfx_handle tape, int frame0, sfx_handle ring, int first_slot, int fd,
-                          void* const* planar_slots, int yuv_matrix, int width, int height);
-
 /* ------------------------------------------------------------------------------------------------ */
 /* Piano roll — ShaderPiano.update() (reference: shaderflow/piano/module.py:185-277) on the device. The score is uploaded once; one
  * kernel launch per frame (k_piano_frame, one block per pitch) selects the frame's candidate notes, writes iPianoRoll, iPianoChan and
@@ -399,6 +375,28 @@ int sfx_piano_step(sfx_handle piano, double scene_time, const sfx_dyn_coeff_f32*
 int sfx_piano_state_read(sfx_handle piano, float* state /* [5][128] */);   /* waits for the context's stream */
 int sfx_piano_destroy(sfx_handle piano);
 
+/* ------------------------------------------------------------------------------------------------ */
+/* The frame sequence: the frame loop of a scene in which nothing but the clock moves (layered / temporal scenes without host logic:
+ * demo.py's Multipass, MotionBlur, Life), `nframes` frames in ONE call: scene.next (scene.py:456-479) = every program's render
+ * (shader.py:388-405: a draw per layer into row 0 of its texture matrix, then texture.roll(), texture.py:295-298), iFinal's resolve
+ * (shader.py:391-396), exporting.pipe (exporting.py:151-174). `passes` in the order scene.next renders; `matrices[m].textures` is
+ * [temporal][layers] in the matrix' CURRENT order (the call rolls its own copy: the host rolls its matrices by `nframes` afterwards),
+ * `names` the sampler name of every box or NULL. `clock[f]` = iTime, iTau, iDeltatime, iFrame of frame f. With a ring and fd >= 0 every
+ * frame is read out and piped (slot (first_slot + f) % slots; `planar_slots`: device staging per slot for yuv420p, or NULL for rgb24).
+ *
+ * With a tape (audio scenes): frame f of the call is tape frame tape_frame0 + f of the bank the last sfx_tape_build filled. A pass whose
+ * program samples iSpectrogram / iWaveform or reads an audio uniform (iAudioVolume, iAudioVolumeIntegral, iAudioSTD, iSpectrogramOffset)
+ * takes them from that tape frame — a layered pass draws each layer into row 0 of its matrix, a fused one is sfx_render_tape into the
+ * pass' target; every other pass is drawn as without a tape. The call waits for the bank's build and marks the bank rendered behind its
+ * last kernel, as sfx_render_tape.
+ *
+ * With a piano (a scene with one ShaderPiano): per frame, in front of the first pass, the piano's frame (sfx_piano_step with
+ * piano_ticks[f]) and piano_ticks[f].dynamic stored into the uniform `piano_dynamic_name` ("iPianoDynamic") of every pass' program
+ * that has one. A tape and a piano in one call are refused (SFX_E_UNSUPPORTED). */
+enum { SFX_PASS_LAYERS = 0, SFX_PASS_FUSED = 1, SFX_PASS_RESOLVE = 2 };
+typedef struct sfx_sequence_pass { sfx_handle program; int kind; int matrix; sfx_handle target; int ssaa; int subsample; } sfx_sequence_pass;
+typedef struct sfx_sequence_matrix { int temporal, layers; const sfx_handle* textures; const char* const* names; } sfx_sequence_matrix;
+typedef struct sfx_clock_tick { float time, tau, deltatime; int32_t frame; } sfx_clock_tick;      /* sfx_uniform_set_clock's arguments */
 /* What frame f of a piano sequence adds to its clock tick: the frame's scene.time in float64, the key-press coefficients, and
  * iPianoDynamic — stepped by the host for all frames up front — for every program that declares it. */
 typedef struct {
@@ -408,12 +406,18 @@ typedef struct {
     int32_t previous_is_target;
     int32_t reserved;                /* padding only: the record is 40 bytes, a multiple of the double's alignment */
 } sfx_piano_tick;
-/* sfx_clock_sequence_run for a scene with one ShaderPiano: per frame, in front of the first pass, the piano's frame (sfx_piano_step) and
- * dynamic[] stored into the uniform `dynamic_name` ("iPianoDynamic") of every pass' program that has one; then the frame as
- * sfx_clock_sequence_run draws it. */
-int sfx_piano_sequence_run(sfx_handle ctx, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                           const sfx_clock_tick* clock, int nframes, sfx_handle piano, const sfx_piano_tick* ticks, const char* dynamic_name,
-                           sfx_handle ring, int first_slot, int fd, void* const* planar_slots, int yuv_matrix, int width, int height);
+typedef struct sfx_sequence {
+    const sfx_sequence_pass* passes; int npasses;
+    const sfx_sequence_matrix* matrices; int nmatrices;
+    const sfx_clock_tick* clock; int nframes;
+    /* the sink: ring == 0 or fd < 0 draws without reading out */
+    sfx_handle ring; int first_slot, fd; void* const* planar_slots; int yuv_matrix, width, height;
+    /* optional: the audio tape. tape == 0: none */
+    sfx_handle tape; int tape_frame0;
+    /* optional: the piano. piano == 0: none */
+    sfx_handle piano; const sfx_piano_tick* piano_ticks; const char* piano_dynamic_name;
+} sfx_sequence;
+int sfx_sequence_run(sfx_handle ctx, const sfx_sequence* sequence);
 
 /* Device memory helper for callers without their own allocator */
 int sfx_device_alloc(sfx_handle ctx, size_t nbytes, void** ptr);

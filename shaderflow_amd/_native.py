@@ -76,6 +76,16 @@ class PianoTick(C.Structure):
     _fields_ = [("time", C.c_double), ("coeff", DynCoeffF32), ("dynamic", C.c_float*2), ("previous_is_target", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Sequence(C.Structure):
+    """sfx_sequence (include/shaderflow_hip.h), field for field: the tables, the sink, the optional tape, the optional piano"""
+    _fields_ = [("passes", C.POINTER(SequencePass)), ("npasses", C.c_int), ("matrices", C.POINTER(SequenceMatrix)), ("nmatrices", C.c_int),
+                ("clock", C.POINTER(ClockTick)), ("nframes", C.c_int),
+                ("ring", Handle), ("first_slot", C.c_int), ("fd", C.c_int), ("planar_slots", C.POINTER(C.c_void_p)),
+                ("yuv_matrix", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("tape", Handle), ("tape_frame0", C.c_int),
+                ("piano", Handle), ("piano_ticks", C.POINTER(PianoTick)), ("piano_dynamic_name", C.c_char_p)]
+
+
 class Binding(C.Structure):
     """sfx_binding (include/shaderflow_hip.h): a uniform or sampler name of a loaded program"""
     _fields_ = [("name", C.c_char_p), ("sampler", C.c_int), ("slot", C.c_int), ("count", C.c_int), ("integer", C.c_int)]
@@ -175,21 +185,16 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_clock_tape_create": (C.c_int, [Handle, C.c_int, P(Handle)]),
     "sfx_tape_reset": (C.c_int, [Handle]),
     "sfx_tape_snapshot": (C.c_int, [Handle, C.c_int]),
-    "sfx_clock_sequence_run": (C.c_int, [Handle, P(SequencePass), C.c_int, P(SequenceMatrix), C.c_int, P(ClockTick), C.c_int, Handle, C.c_int, C.c_int,
-                                         P(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "sfx_tape_build": (C.c_int, [Handle, C.c_int, P(C.c_int64), P(FrameClock), P(DynCoeffF32), P(DynCoeffF64), P(DynCoeffF64)]),
     "sfx_tape_read": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "sfx_tape_destroy": (C.c_int, [Handle]),
     "sfx_render_tape": (C.c_int, [Handle, Handle, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sfx_tape_sequence_run": (C.c_int, [Handle, P(SequencePass), C.c_int, P(SequenceMatrix), C.c_int, P(ClockTick), C.c_int, Handle, C.c_int, Handle,
-                                        C.c_int, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "sfx_piano_create": (C.c_int, [Handle, P(C.c_int32), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_float), P(C.c_float), C.c_int, P(PianoParams),
                                    Handle, Handle, Handle, P(C.c_float), P(Handle)]),
     "sfx_piano_step": (C.c_int, [Handle, C.c_double, P(DynCoeffF32), C.c_int]),
     "sfx_piano_state_read": (C.c_int, [Handle, P(C.c_float)]),
     "sfx_piano_destroy": (C.c_int, [Handle]),
-    "sfx_piano_sequence_run": (C.c_int, [Handle, P(SequencePass), C.c_int, P(SequenceMatrix), C.c_int, P(ClockTick), C.c_int, Handle, P(PianoTick), C.c_char_p,
-                                         Handle, C.c_int, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int]),
+    "sfx_sequence_run": (C.c_int, [Handle, P(Sequence)]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),
     "sfx_device_free": (C.c_int, [Handle, C.c_void_p]),
     "sfx_device_copy": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_size_t]),

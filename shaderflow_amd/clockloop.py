@@ -108,7 +108,7 @@ class ClockLoop:
             handles = (N.Handle*count)(*[box.texture.handle if box.texture is not None else N.Handle() for (_, _, box) in texture.boxes])
             N.check(N.lib().sfx_sampler_bind_many(program.program, names, handles, count))
 
-    # the same loop without python between the frames (csrc/capi.hip sfx_clock_sequence_run) ---------------------------------------------
+    # the same loop without python between the frames (csrc/capi.hip sfx_sequence_run) ---------------------------------------------------
 
     CHUNK = 240                                                        # most frames per native call: the encoder and `scene.quit` are looked at in between
     CHUNK_SECONDS = 0.25                                               # … and about how long a call may keep the host: the chunk is sized by the measured frame time
@@ -132,11 +132,10 @@ class ClockLoop:
 
     def run_native(self, export: "ExportingHelper", times, dts, rdts, total: int, tape: "Optional[FrameTape]" = None, pipe_here: bool = False,
                    turbo: bool = True, piano=None) -> None:
-        """With a `tape` (tapesequence.py) the frames go in the tape's batches: each batch is built, then drawn by sfx_tape_sequence_run in
-        chunks that stay inside it. `pipe_here`: one frame per call, read out by export.pipe (a progress relay, no turbo).
-        With a `piano` (pianosequence.py: `.handle`, `.ticks(first, count)` = the frames' sfx_piano_tick table, `.dynamic_name` = the module's
-        `<name>Dynamic` uniform) every chunk is drawn by
-        sfx_piano_sequence_run."""
+        """Every chunk of frames is one sfx_sequence_run. With a `tape` (tapesequence.py) the frames go in the tape's batches: each batch is
+        built, then drawn in chunks that stay inside it. `pipe_here`: one frame per call, read out by export.pipe (a progress relay, no
+        turbo). With a `piano` (pianosequence.py: `.handle`, `.ticks(first, count)` = the frames' sfx_piano_tick table, `.dynamic_name` = the
+        module's `<name>Dynamic` uniform) the piano's frame goes in front of every frame's passes."""
         scene, lib = self.scene, N.lib()
         runtime, fps = scene.runtime, scene.fps
         # texture matrices: every program's own (its draws go to row 0) — the same objects `rolling` lists when they are temporal
@@ -167,6 +166,14 @@ class ClockLoop:
         if export._yuv_slots:                                           # (staging exists for a planar sink only)
             planar = (C.c_void_p*len(export._yuv_slots))(*export._yuv_slots)
         piping = export.fileno is not None and export.ring is not None and not pipe_here
+        # what a run keeps: the passes, the sink, the tape and the piano; every chunk sets the clock, the matrices and where it starts
+        sequence = N.Sequence(passes=passes, npasses=len(self.programs), nmatrices=len(textures),
+                              ring=export.ring if piping else N.Handle(), fd=export.fileno if piping else -1, planar_slots=planar,
+                              yuv_matrix=1 if export.yuv_matrix == "bt709" else 0, width=scene.width, height=scene.height)
+        if tape is not None:
+            sequence.tape = tape.handle
+        if piano is not None:
+            sequence.piano, sequence.piano_dynamic_name = piano.handle, piano.dynamic_name
         done = 0
         per_frame = None                                               # seconds per frame of the last native call
         import time as clock
@@ -183,18 +190,11 @@ class ClockLoop:
                 for i in range(count):
                     time = times[done + i]
                     ticks[i] = N.ClockTick(time, (time/runtime) % 1.0, dts[done + i], round(time*fps))
-                ring, slot, fd = export.ring if piping else N.Handle(), export.frame % max(1, export.slots), export.fileno if piping else -1
+                sequence.clock, sequence.nframes, sequence.matrices = ticks, count, matrix_tables()
+                sequence.first_slot, sequence.tape_frame0 = export.frame % max(1, export.slots), done - first
                 if piano is not None:
-                    N.check(lib.sfx_piano_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
-                                                       piano.handle, piano.ticks(done, count), piano.dynamic_name, ring, slot, fd, planar,
-                                                       1 if export.yuv_matrix == "bt709" else 0, scene.width, scene.height))
-                elif tape is None:
-                    N.check(lib.sfx_clock_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
-                                                       ring, slot, fd, planar, 1 if export.yuv_matrix == "bt709" else 0, scene.width, scene.height))
-                else:
-                    N.check(lib.sfx_tape_sequence_run(scene.context.handle, passes, len(self.programs), matrix_tables(), len(textures), ticks, count,
-                                                      tape.handle, done - first, ring, slot, fd, planar, 1 if export.yuv_matrix == "bt709" else 0,
-                                                      scene.width, scene.height))
+                    sequence.piano_ticks = piano.ticks(done, count)
+                N.check(lib.sfx_sequence_run(scene.context.handle, C.byref(sequence)))
                 per_frame = (clock.perf_counter() - started)/count
                 for texture in textures:
                     texture.roll(count)                               # the native call rolled its own copy of every matrix it drew into
@@ -205,46 +205,52 @@ class ClockLoop:
                     export.frame += count
                 done += count
                 keep.clear()
+        # The three loops leave different clocks behind, and tests pin them: here the last frame drawn; TapeSequence.run then takes
+        # rdt = dt of that frame (as FrameTape.export does); PianoSequence.run what scene.next leaves BEHIND the last frame
         if done:
             scene.time, scene.dt, scene.rdt = times[done - 1], dts[done - 1], rdts[done - 1]
 
-    def run(self, export: "ExportingHelper", turbo: bool):
+    def prime(self, times, dts, rdts) -> None:
+        """Frame 0's state through the ordinary pipeline walk: every uniform and sampler of every program is on the device"""
         scene = self.scene
-        total = export.total_frames
-        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
-        lib = N.lib()
-        # frame 0's state through the ordinary pipeline walk: every uniform and sampler of every program is on the device
         scene.time, scene.dt, scene.rdt = times[0], dts[0], rdts[0]
         for program in self.programs:
             if program.program is None:
                 program.compile()
             if not program.texture.final:
                 program.use_scene_pipeline()
-        runtime, fps = scene.runtime, scene.fps
-        if self.native_sequence(export, turbo):
-            try:
-                self.run_native(export, times, dts, rdts, total)
-            finally:
-                for program in self.programs:
-                    program._pushed.clear(); program._pushed_plain.clear(); program._module_tokens.clear()
-            return export.finish()
+
+    def forget_sent(self) -> None:
+        """Behind a run: what the loop sent behind the programs' backs — their caches of sent values say something older"""
+        for program in self.programs:
+            program.forget_sent()
+
+    def run(self, export: "ExportingHelper", turbo: bool):
+        scene = self.scene
+        total = export.total_frames
+        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
+        self.prime(times, dts, rdts)
+        native = self.native_sequence(export, turbo)
         try:
-            for k in range(total):
-                if scene.quit:                                        # ShaderMessage.Window.Close (scene.py:478-480), as the vsync loop honours it
-                    break
-                time = times[k]
-                scene.time, scene.dt, scene.rdt = time, dts[k], rdts[k]
-                scene._fused_this_frame = False
-                for program in self.programs:
-                    if not program.texture.final:
-                        N.check(lib.sfx_uniform_set_clock(program.program, time, (time/runtime) % 1.0, dts[k], round(time*fps)))
-                        self.bind_rolled(program)
-                    program.render(pipeline=False)
-                export.pipe(turbo=turbo)
-                export.update()
+            if native:
+                self.run_native(export, times, dts, rdts, total)
+            else:
+                lib, runtime, fps = N.lib(), scene.runtime, scene.fps
+                for k in range(total):
+                    if scene.quit:                                    # ShaderMessage.Window.Close (scene.py:478-480), as the vsync loop honours it
+                        break
+                    time = times[k]
+                    scene.time, scene.dt, scene.rdt = time, dts[k], rdts[k]
+                    scene._fused_this_frame = False
+                    for program in self.programs:
+                        if not program.texture.final:
+                            N.check(lib.sfx_uniform_set_clock(program.program, time, (time/runtime) % 1.0, dts[k], round(time*fps)))
+                            self.bind_rolled(program)
+                        program.render(pipeline=False)
+                    export.pipe(turbo=turbo)
+                    export.update()
         finally:
-            # what this loop sent behind the programs' backs: their caches of sent values say something older
-            for program in self.programs:
-                program._pushed.clear(); program._pushed_plain.clear(); program._module_tokens.clear()
-        scene.time, scene.dt, scene.rdt = times[-1], dts[-1], rdts[-1]          # the clock of the last frame
+            self.forget_sent()
+        if not native:
+            scene.time, scene.dt, scene.rdt = times[-1], dts[-1], rdts[-1]      # the clock of the last frame
         return export.finish()

@@ -925,23 +925,31 @@ static int launch_fused_p(const Program* p, const RenderArgs& a, int ssaa, int f
     return launch_jit(p->fn_fused[ssaa == 2 ? 1 : 2], a, dim3(blocks_x*row_blocks, 1, frames), dim3(threads), s);
 }
 
+static int bind_tape(const Program* p, const TapeView* t, RenderArgs& a, int frame0, int nframes);
+
+// The draw of one layer into one texture (a box of a texture matrix). With a `tape` the audio state is tape frame `frame`'s
+// (the sequence's passes that read audio), without one the program's own bound samplers and uniforms.
+static int render_box(Program* p, Texture* target, int layer, const TapeView* tape, int frame) {
+    if (target->dtype != SFX_U8 && target->dtype != SFX_F32 && target->dtype != SFX_F16) return fail(SFX_E_UNSUPPORTED, "render target dtype %d", target->dtype);
+    USE_DEVICE(p->ctx);
+    RenderArgs a;
+    fill_args(p, a);
+    a.u.iLayer = layer;                                             // shader.py:402
+    a.wr = target->width; a.hr = target->height; a.w = target->width; a.h = target->height;
+    a.out = target->data; a.out_components = target->components; a.out_dtype = target->dtype; a.out_frame_stride = 0;
+    set_pixel_centres(a);
+    int rc = tape ? bind_tape(p, tape, a, frame, 1) : check_samplers(p->fragment, a);
+    if (rc) return rc;
+    if ((rc = launch_render_p(p, a, 1, p->ctx->stream))) return rc;
+    return launch_status();
+}
+
 extern "C" int sfx_render(sfx_handle h, sfx_handle target, int layer) {
     Program* p = get<Program>(h, MAGIC_PROG);
     Texture* t = get<Texture>(target, MAGIC_TEX);
     if (!p || !t) return fail(SFX_E_INVALID, "invalid program or target handle");
     if (p->fragment == FRAG_FINAL) return fail(SFX_E_INVALID, "the final program is driven by sfx_resolve / sfx_render_resolve");
-    if (t->dtype != SFX_U8 && t->dtype != SFX_F32 && t->dtype != SFX_F16) return fail(SFX_E_UNSUPPORTED, "render target dtype %d", t->dtype);
-    USE_DEVICE(p->ctx);
-    RenderArgs a;
-    fill_args(p, a);
-    a.u.iLayer = layer;                                             // shader.py:402
-    a.wr = t->width; a.hr = t->height; a.w = t->width; a.h = t->height;
-    a.out = t->data; a.out_components = t->components; a.out_dtype = t->dtype; a.out_frame_stride = 0;
-    set_pixel_centres(a);
-    int rc = check_samplers(p->fragment, a);
-    if (rc) return rc;
-    if ((rc = launch_render_p(p, a, 1, p->ctx->stream))) return rc;
-    return launch_status();
+    return render_box(p, t, layer, nullptr, 0);
 }
 
 
@@ -1036,167 +1044,144 @@ static bool reads_audio(const Program* p) {
     return p->fragment == FRAG_VISUALIZER || p->fragment == FRAG_BARS || p->fragment == FRAG_WAVEFORM || p->fragment == FRAG_AUDIO;
 }
 
-static int bind_tape(const Program* p, const TapeView* t, RenderArgs& a, int frame0, int nframes);
 // Records the bank's `rendered` event behind the last kernel its scope launched (the build that refills the bank waits for it)
 struct RenderedMark { hipEvent_t event; hipStream_t stream; ~RenderedMark() { if (event) hipEventRecord(event, stream); } };
 
-// sfx_render for tape frame `frame`: the draw of one layer into one box of a texture matrix, its audio state from the tape
-static int render_tape_box(Program* p, const TapeView* t, int frame, Texture* target, int layer) {
-    if (target->dtype != SFX_U8 && target->dtype != SFX_F32 && target->dtype != SFX_F16) return fail(SFX_E_UNSUPPORTED, "render target dtype %d", target->dtype);
-    RenderArgs a;
-    fill_args(p, a);
-    a.u.iLayer = layer;                                             // shader.py:402
-    a.wr = target->width; a.hr = target->height; a.w = target->width; a.h = target->height;
-    a.out = target->data; a.out_components = target->components; a.out_dtype = target->dtype; a.out_frame_stride = 0;
-    set_pixel_centres(a);
-    int rc = bind_tape(p, t, a, frame, 1);
-    if (rc) return rc;
-    if ((rc = launch_render_p(p, a, 1, p->ctx->stream))) return rc;
-    return launch_status();
-}
+// What a sequence call validates and resolves once, in front of its frames: the names never change, only what sits behind them
+struct SequencePlan {
+    int ring_slots = 0;
+    TapeView tape{}; bool taped = false;
+    std::vector<std::vector<int>> order;                             // the matrices as the call rolls them: order[m][t] = row of the caller's table at depth t now
+    struct Bind { Program* p; int slot, m, t, l; };
+    std::vector<Bind> binds;                                         // sampler slots of every (program, named box of a rolled matrix)
+    std::vector<char> audio;                                         // pass k draws from the tape (reads_audio)
+    struct DynamicSlot { Program* p; int slot; };
+    std::vector<DynamicSlot> dynamic_slots;                          // where the piano's note range lives in user[] of every program that declares it
+};
 
-// The loop of sfx_clock_sequence_run and sfx_tape_sequence_run. With a tape (`ht`), frame f of the call is tape frame frame0 + f of
-// the bank the last build filled: every pass whose program reads audio (reads_audio, decided once per call) takes that frame's
-// audio state from the tape — a layered pass draws through render_tape_box, a fused one through sfx_render_tape into iFinal — and
-// every other pass is drawn exactly as without a tape.
-static int run_sequence(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                        const sfx_clock_tick* clock, int nframes, sfx_handle ht, int frame0, sfx_handle hring, int first_slot, int fd,
-                        void* const* planar_slots, int yuv_matrix, int width, int height,
-                        sfx_handle hpiano = 0, const sfx_piano_tick* piano_ticks = nullptr, const char* dynamic_name = nullptr) {
-    CTX_OR_FAIL(c, hc);
-    if (hpiano && !piano_ticks) return fail(SFX_E_INVALID, "piano sequence: null tick table");
-    const int ring_slots = hring ? ring_slot_count(hring) : 0;
-    if (!passes || npasses < 1 || nmatrices < 0 || (nmatrices && !matrices) || !clock || nframes < 0) return fail(SFX_E_INVALID, "clock sequence: null tables");
-    if (ring_slots < 0) return fail(SFX_E_INVALID, "clock sequence: invalid ring handle");
-    TapeView tape, *t = nullptr;
-    if (ht) {
-        if (!tape_view(ht, &tape)) return fail(SFX_E_INVALID, "tape sequence: invalid tape handle");
-        if (tape.ctx != c) return fail(SFX_E_INVALID, "tape sequence: the tape belongs to another context");
-        if (frame0 < 0 || frame0 + nframes > tape.max_frames) return fail(SFX_E_INVALID, "tape sequence: frames [%d, %d) outside the tape", frame0, frame0 + nframes);
-        t = &tape;
+static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) {
+    if (s.piano && !s.piano_ticks) return fail(SFX_E_INVALID, "piano sequence: null tick table");
+    plan.ring_slots = s.ring ? ring_slot_count(s.ring) : 0;
+    if (!s.passes || s.npasses < 1 || s.nmatrices < 0 || (s.nmatrices && !s.matrices) || !s.clock || s.nframes < 0) return fail(SFX_E_INVALID, "clock sequence: null tables");
+    if (plan.ring_slots < 0) return fail(SFX_E_INVALID, "clock sequence: invalid ring handle");
+    if (s.tape && s.piano) return fail(SFX_E_UNSUPPORTED, "sequence: a tape and a piano in one call are not supported");
+    if (s.tape) {
+        if (!tape_view(s.tape, &plan.tape)) return fail(SFX_E_INVALID, "tape sequence: invalid tape handle");
+        if (plan.tape.ctx != c) return fail(SFX_E_INVALID, "tape sequence: the tape belongs to another context");
+        if (s.tape_frame0 < 0 || s.tape_frame0 + s.nframes > plan.tape.max_frames) return fail(SFX_E_INVALID, "tape sequence: frames [%d, %d) outside the tape", s.tape_frame0, s.tape_frame0 + s.nframes);
+        plan.taped = true;
     }
-    USE_DEVICE(c);
-    // the matrices as this call rolls them: order[m][t] = row of the caller's table that sits at depth t now
-    std::vector<std::vector<int>> order(nmatrices);
-    for (int m = 0; m < nmatrices; m++) {
-        if (matrices[m].temporal < 1 || matrices[m].layers < 1 || !matrices[m].textures) return fail(SFX_E_INVALID, "clock sequence: matrix %d", m);
-        order[m].resize(matrices[m].temporal);
-        for (int d = 0; d < matrices[m].temporal; d++) order[m][d] = d;
-        for (int k = 0; k < matrices[m].temporal*matrices[m].layers; k++) {
-            Texture* texture = get<Texture>(matrices[m].textures[k], MAGIC_TEX);
+    plan.order.resize(s.nmatrices);
+    for (int m = 0; m < s.nmatrices; m++) {
+        const sfx_sequence_matrix& matrix = s.matrices[m];
+        if (matrix.temporal < 1 || matrix.layers < 1 || !matrix.textures) return fail(SFX_E_INVALID, "clock sequence: matrix %d", m);
+        plan.order[m].resize(matrix.temporal);
+        for (int d = 0; d < matrix.temporal; d++) plan.order[m][d] = d;
+        for (int k = 0; k < matrix.temporal*matrix.layers; k++) {
+            Texture* texture = get<Texture>(matrix.textures[k], MAGIC_TEX);
             if (!texture || texture->ctx != c) return fail(SFX_E_INVALID, "clock sequence: matrix %d, box %d is not a texture of this context", m, k);
         }
     }
-    auto box = [&](int m, int d, int l) -> sfx_handle { return matrices[m].textures[order[m][d]*matrices[m].layers + (l < 0 ? matrices[m].layers + l : l)]; };
-    // sampler slots of every (program, named box), resolved once: the names never change, only what sits behind them
-    struct Bind { Program* p; int slot, m, t, l; };
-    std::vector<Bind> binds;
-    std::vector<char> audio(npasses, 0);                             // pass k draws from the tape
-    for (int k = 0; k < npasses; k++) {
-        if (passes[k].kind == SFX_PASS_RESOLVE) continue;
-        Program* p = get<Program>(passes[k].program, MAGIC_PROG);
+    plan.audio.assign(s.npasses, 0);
+    for (int k = 0; k < s.npasses; k++) {
+        const sfx_sequence_pass& pass = s.passes[k];
+        if (pass.kind == SFX_PASS_RESOLVE) continue;
+        Program* p = get<Program>(pass.program, MAGIC_PROG);
         if (!p || p->ctx != c) return fail(SFX_E_INVALID, "clock sequence: pass %d has no program of this context", k);
-        if (passes[k].matrix < 0 || passes[k].matrix >= nmatrices) return fail(SFX_E_INVALID, "clock sequence: pass %d names matrix %d", k, passes[k].matrix);
-        audio[k] = (t && reads_audio(p)) ? 1 : 0;
-        if (audio[k] && passes[k].kind == SFX_PASS_FUSED && !get<Texture>(passes[k].target, MAGIC_TEX)) return fail(SFX_E_INVALID, "tape sequence: fused pass %d has no target", k);
-        for (int m = 0; m < nmatrices; m++) {
-            if (!matrices[m].names || matrices[m].temporal < 2) continue;     // (samplers of a matrix that never rolls were bound by the host)
-            for (int d = 0; d < matrices[m].temporal; d++) for (int l = 0; l < matrices[m].layers; l++) {
-                const char* name = matrices[m].names[d*matrices[m].layers + l];
+        if (pass.matrix < 0 || pass.matrix >= s.nmatrices) return fail(SFX_E_INVALID, "clock sequence: pass %d names matrix %d", k, pass.matrix);
+        plan.audio[k] = (plan.taped && reads_audio(p)) ? 1 : 0;
+        if (plan.audio[k] && pass.kind == SFX_PASS_FUSED && !get<Texture>(pass.target, MAGIC_TEX)) return fail(SFX_E_INVALID, "tape sequence: fused pass %d has no target", k);
+        for (int m = 0; m < s.nmatrices; m++) {
+            const sfx_sequence_matrix& matrix = s.matrices[m];
+            if (!matrix.names || matrix.temporal < 2) continue;      // (samplers of a matrix that never rolls were bound by the host)
+            for (int d = 0; d < matrix.temporal; d++) for (int l = 0; l < matrix.layers; l++) {
+                const char* name = matrix.names[d*matrix.layers + l];
                 const int slot = name ? resolve_sampler(p, name) : -1;
-                if (slot >= 0) binds.push_back({p, slot, m, d, l});
+                if (slot >= 0) plan.binds.push_back({p, slot, m, d, l});
             }
         }
-    }
-    // where iPianoDynamic lives in the user[] block of every program that declares it, resolved once like the sampler slots (the
-    // stock fragments declare none: a translated one by its bindings)
-    struct DynamicSlot { Program* p; int slot; };
-    std::vector<DynamicSlot> dynamic_slots;
-    if (hpiano && dynamic_name) {
-        for (int k = 0; k < npasses; k++) {
-            Program* p = passes[k].kind == SFX_PASS_RESOLVE ? nullptr : get<Program>(passes[k].program, MAGIC_PROG);
-            if (!p) continue;
+        // (the stock fragments declare no note range: a translated one by its bindings)
+        if (s.piano && s.piano_dynamic_name)
             for (const auto& b : p->bindings)
-                if (!b.sampler && !b.integer && b.count >= 2 && b.name == dynamic_name) dynamic_slots.push_back({p, b.slot});
-        }
+                if (!b.sampler && !b.integer && b.count >= 2 && b.name == s.piano_dynamic_name) plan.dynamic_slots.push_back({p, b.slot});
     }
+    return SFX_OK;
+}
+
+// The frames of sfx_sequence_run. With a tape, frame f of the call is tape frame tape_frame0 + f of the bank the last build filled:
+// every pass whose program reads audio takes that frame's audio state from the tape — a layered pass draws through render_box, a fused
+// one through sfx_render_tape into iFinal — and every other pass is drawn exactly as without a tape. With a piano, k_piano_frame and
+// the note range go in front of every frame's first pass (pianosequence.py).
+static int run_sequence(sfx_handle hc, Context* c, const sfx_sequence& s, SequencePlan& plan) {
+    const TapeView* t = plan.taped ? &plan.tape : nullptr;
+    auto box = [&](int m, int d, int l) -> sfx_handle {
+        const sfx_sequence_matrix& matrix = s.matrices[m];
+        return matrix.textures[plan.order[m][d]*matrix.layers + (l < 0 ? matrix.layers + l : l)];
+    };
     // the bank was filled on the tape's stream: the draws wait for its last audio kernel, and the build that refills it waits for
     // the mark behind the last kernel of this call (as in sfx_render_tape)
     if (t) HIP_TRY(hipStreamWaitEvent(c->stream, t->built, 0));
     RenderedMark mark{t ? t->rendered : nullptr, c->stream};
-    for (int f = 0; f < nframes; f++) {
-        const sfx_clock_tick& now = clock[f];
+    for (int f = 0; f < s.nframes; f++) {
+        const sfx_clock_tick& now = s.clock[f];
         bool fused = false;
-        if (hpiano) {
+        if (s.piano) {
             // ShaderPiano.update() of the frame (scene.next updates every module before any program renders): the three textures on the
             // render stream, in front of the draws that sample them, and iPianoDynamic as the pipeline walk would have pushed it
-            const sfx_piano_tick& tick = piano_ticks[f];
-            const int rc = piano_launch_frame(hpiano, c, tick.time, tick.coeff, tick.previous_is_target);
+            const sfx_piano_tick& tick = s.piano_ticks[f];
+            const int rc = piano_launch_frame(s.piano, c, tick.time, tick.coeff, tick.previous_is_target);
             if (rc) return rc;
-            for (const DynamicSlot& d : dynamic_slots) { d.p->u.user[d.slot] = tick.dynamic[0]; d.p->u.user[d.slot + 1] = tick.dynamic[1]; }
+            for (const auto& d : plan.dynamic_slots) { d.p->u.user[d.slot] = tick.dynamic[0]; d.p->u.user[d.slot + 1] = tick.dynamic[1]; }
         }
-        for (int k = 0; k < npasses; k++) {
-            const sfx_sequence_pass& pass = passes[k];
+        for (int k = 0; k < s.npasses; k++) {
+            const sfx_sequence_pass& pass = s.passes[k];
             if (pass.kind == SFX_PASS_RESOLVE) {
                 if (fused) continue;                                // the main pass resolved into iFinal already (shader.py:391-396)
-                if (pass.matrix < 0 || pass.matrix >= nmatrices) return fail(SFX_E_INVALID, "clock sequence: resolve pass %d names matrix %d", k, pass.matrix);
+                if (pass.matrix < 0 || pass.matrix >= s.nmatrices) return fail(SFX_E_INVALID, "clock sequence: resolve pass %d names matrix %d", k, pass.matrix);
                 const int rc = sfx_resolve(hc, box(pass.matrix, 0, -1), pass.target, pass.subsample);
                 if (rc) return rc;
                 continue;
             }
             Program* p = get<Program>(pass.program, MAGIC_PROG);
             p->u.iTime = now.time; p->u.iTau = now.tau; p->u.iDeltatime = now.deltatime; p->u.iFrame = now.frame;      // sfx_uniform_set_clock
-            for (const Bind& b : binds) if (b.p == p) b.p->samplers[b.slot] = get<Texture>(box(b.m, b.t, b.l), MAGIC_TEX);
+            for (const auto& b : plan.binds) if (b.p == p) b.p->samplers[b.slot] = get<Texture>(box(b.m, b.t, b.l), MAGIC_TEX);
             if (pass.kind == SFX_PASS_FUSED) {
                 int rc;
-                if (audio[k]) {
+                if (plan.audio[k]) {
                     Texture* final_texture = get<Texture>(pass.target, MAGIC_TEX);
-                    rc = sfx_render_tape(pass.program, ht, frame0 + f, 1, final_texture->width, final_texture->height, pass.ssaa*1000, pass.subsample, final_texture->data);
+                    rc = sfx_render_tape(pass.program, s.tape, s.tape_frame0 + f, 1, final_texture->width, final_texture->height, pass.ssaa*1000, pass.subsample, final_texture->data);
                 } else {
                     rc = sfx_render_resolve(pass.program, pass.target, pass.ssaa, pass.subsample);
                 }
                 if (rc) return rc;
                 fused = true;
             } else {
-                for (int l = 0; l < matrices[pass.matrix].layers; l++) {
+                for (int l = 0; l < s.matrices[pass.matrix].layers; l++) {
                     // shader.py:400-403: iLayer = l, into row 0
-                    const int rc = audio[k] ? render_tape_box(p, t, frame0 + f, get<Texture>(box(pass.matrix, 0, l), MAGIC_TEX), l)
-                                            : sfx_render(pass.program, box(pass.matrix, 0, l), l);
+                    const int rc = plan.audio[k] ? render_box(p, get<Texture>(box(pass.matrix, 0, l), MAGIC_TEX), l, t, s.tape_frame0 + f)
+                                                 : sfx_render(pass.program, box(pass.matrix, 0, l), l);
                     if (rc) return rc;
                 }
             }
-            std::vector<int>& rows = order[pass.matrix];              // texture.roll(): the oldest row becomes row 0
+            std::vector<int>& rows = plan.order[pass.matrix];         // texture.roll(): the oldest row becomes row 0
             std::rotate(rows.begin(), rows.end() - 1, rows.end());
         }
-        if (ring_slots > 0 && fd >= 0) {
-            const int rc = sequence_pipe(hc, hring, (first_slot + f) % ring_slots, fd, passes[npasses - 1].target, planar_slots, yuv_matrix, width, height);
+        if (plan.ring_slots > 0 && s.fd >= 0) {
+            const int rc = sequence_pipe(hc, s.ring, (s.first_slot + f) % plan.ring_slots, s.fd, s.passes[s.npasses - 1].target, s.planar_slots, s.yuv_matrix, s.width, s.height);
             if (rc) return rc;
         }
     }
     return SFX_OK;
 }
 
-extern "C" int sfx_clock_sequence_run(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                                      const sfx_clock_tick* clock, int nframes, sfx_handle hring, int first_slot, int fd,
-                                      void* const* planar_slots, int yuv_matrix, int width, int height) {
-    return run_sequence(hc, passes, npasses, matrices, nmatrices, clock, nframes, 0, 0, hring, first_slot, fd, planar_slots, yuv_matrix, width, height);
-}
-
-// The same loop for a scene with a ShaderPiano (pianosequence.py): k_piano_frame and iPianoDynamic in front of every frame
-extern "C" int sfx_piano_sequence_run(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                                      const sfx_clock_tick* clock, int nframes, sfx_handle hpiano, const sfx_piano_tick* ticks, const char* dynamic_name,
-                                      sfx_handle hring, int first_slot, int fd, void* const* planar_slots, int yuv_matrix, int width, int height) {
-    if (!hpiano) return fail(SFX_E_INVALID, "piano sequence: null piano handle");
-    return run_sequence(hc, passes, npasses, matrices, nmatrices, clock, nframes, 0, 0, hring, first_slot, fd, planar_slots, yuv_matrix, width, height,
-                        hpiano, ticks, dynamic_name);
-}
-
-// The same loop for audio scenes (tapesequence.py): the passes that read audio draw tape frames [frame0, frame0 + nframes)
-extern "C" int sfx_tape_sequence_run(sfx_handle hc, const sfx_sequence_pass* passes, int npasses, const sfx_sequence_matrix* matrices, int nmatrices,
-                                     const sfx_clock_tick* clock, int nframes, sfx_handle ht, int frame0, sfx_handle hring, int first_slot, int fd,
-                                     void* const* planar_slots, int yuv_matrix, int width, int height) {
-    if (!ht) return fail(SFX_E_INVALID, "tape sequence: null tape handle");
-    return run_sequence(hc, passes, npasses, matrices, nmatrices, clock, nframes, ht, frame0, hring, first_slot, fd, planar_slots, yuv_matrix, width, height);
+extern "C" int sfx_sequence_run(sfx_handle hc, const sfx_sequence* sequence) {
+    CTX_OR_FAIL(c, hc);
+    if (!sequence) return fail(SFX_E_INVALID, "clock sequence: null tables");
+    SequencePlan plan;
+    const int rc = plan_sequence(c, *sequence, plan);
+    if (rc) return rc;
+    USE_DEVICE(c);
+    return run_sequence(hc, c, *sequence, plan);
 }
 
 

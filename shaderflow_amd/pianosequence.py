@@ -6,7 +6,7 @@ PianoSequence: the frame loop of piano-roll scenes without python logic (no refe
 module, so a scene with a piano always took `ShaderScene.next`.
 
 Here the score lives in device memory (`sfx_piano_create`), and ClockLoop's native sequence draws the frames in chunks
-(`sfx_piano_sequence_run`): in front of every frame's passes one launch of `k_piano_frame` (csrc/piano_kernels.hpp) restates that
+(`sfx_sequence_run` with the piano named): in front of every frame's passes one launch of `k_piano_frame` (csrc/piano_kernels.hpp) restates that
 frame's `update()` — candidates, rolling slots, channel and target velocity per key, one step of the key-press `DynamicNumber` —
 straight into the module's own three textures, on the render stream, so the draws behind it sample the frame's content. The frames
 are the frame loop's byte for byte.
@@ -18,7 +18,8 @@ program that declares it.
 
 A scene takes this loop when `main(batch=None)` finds it applicable (after ClockLoop, before TapeSequence) and
 `SHADERFLOW_PIANO_SEQUENCE` is not "0". Out of scope, so they keep the frame loop: python `update()` logic, a subclass of ShaderPiano,
-several pianos, audio modules beside the piano (joining this hook to `sfx_tape_sequence_run` is the follow-up), sharded runs, and a
+several pianos, audio modules beside the piano (`sfx_sequence_run` refuses a tape and a piano in one call: lifting that is the
+follow-up), sharded runs, and a
 key-press system whose early-out can fire (`precision != 0`) or that integrates.
 """
 from __future__ import annotations
@@ -222,13 +223,7 @@ class PianoSequence:
         total = export.total_frames
         times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
         try:
-            # frame 0's state through the ordinary pipeline walk: every uniform and sampler of every program is on the device
-            scene.time, scene.dt, scene.rdt = times[0], dts[0], rdts[0]
-            for program in clock.programs:
-                if program.program is None:
-                    program.compile()
-                if not program.texture.final:
-                    program.use_scene_pipeline()
+            clock.prime(times, dts, rdts)
             self.upload()
             # the per-frame table: the clock in float64, the key-press coefficients, iPianoDynamic of every frame
             before = {name: deepcopy(getattr(note_range, name)) for name in ("value", "target", "previous", "derivative", "acceleration", "frequency")}
@@ -246,8 +241,7 @@ class PianoSequence:
                 clock.run_native(export, times, dts, rdts, total, piano=self)
                 finished = True
             finally:
-                for program in clock.programs:
-                    program._pushed.clear(); program._pushed_plain.clear(); program._module_tokens.clear()
+                clock.forget_sent()
                 # Whatever ended the run — the last frame, scene.quit, an encoder that died, a device error — the host objects are left at
                 # the last frame that was drawn: the note range was stepped through the whole export up front, so it goes back and is
                 # stepped again as far as the frames went; the key-press state and the textures' host copies are read from the device (which a

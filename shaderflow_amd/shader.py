@@ -178,12 +178,17 @@ class ShaderProgram(ShaderModule):
         if self.program is not None and self.program.value:
             N.lib().sfx_program_destroy(self.program)
         self.program = None
-        self._pushed.clear()
-        self._pushed_plain.clear()
-        self._module_tokens.clear()
+        self.forget_sent()
         self._module_names.clear()
         self._shared_names = frozenset()
         self._uniform_arrays = {}
+
+    def forget_sent(self) -> None:
+        """The caches of what the device program holds, emptied: whoever wrote uniforms or samplers behind this object's back (the native
+        loops) calls this, and the next pipeline walk sends everything again"""
+        self._pushed.clear()
+        self._pushed_plain.clear()
+        self._module_tokens.clear()
 
     def compile(self, _vertex: str = None, _fragment: str = None):
         for variable in self.full_pipeline():

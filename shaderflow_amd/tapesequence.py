@@ -9,8 +9,8 @@ all three into `ShaderScene.next`, which paid a device STFT, a host round trip, 
 writes of the spectrogram and the waveform, and the pipeline walk, every frame.
 
 Here the device builds the audio state of a batch of frames exactly as an export's `FrameTape.build` does, and ClockLoop's native
-sequence draws the batch in chunks (`sfx_tape_sequence_run`): the same passes, clock ticks, rolled sampler tables, resolve and read-out
-as `sfx_clock_sequence_run`, except that a pass whose program reads audio (samples iSpectrogram / iWaveform, or reads iAudioVolume,
+sequence draws the batch in chunks (`sfx_sequence_run` with the tape named): the same passes, clock ticks, rolled sampler tables, resolve
+and read-out as without a tape, except that a pass whose program reads audio (samples iSpectrogram / iWaveform, or reads iAudioVolume,
 iAudioVolumeIntegral, iAudioSTD, iSpectrogramOffset) takes frame k's audio state from tape frame k — a layered pass draws every layer
 into row 0 of its matrix, a fused one renders into iFinal through `sfx_render_tape`. Passes that read no audio are drawn as by
 ClockLoop. The next batch's build is queued right behind the last chunk of the current one and runs beside its draws.
@@ -27,6 +27,7 @@ from typing import TYPE_CHECKING
 
 import numpy as np
 
+from shaderflow_amd import _native as N
 from shaderflow_amd.audio.module import ShaderAudio
 from shaderflow_amd.audio.spectrogram import ShaderSpectrogram
 from shaderflow_amd.audio.waveform import ShaderWaveform
@@ -98,21 +99,13 @@ class TapeSequence:
         try:
             if tape.spectrogram is not None and not tape.private_spectrogram:
                 tape.spectrogram.configure_texture()                  # what its first update() would do (FrameTape.bind_static_uniforms)
-            # frame 0's state through the ordinary pipeline walk: every uniform and sampler of every program is on the device
-            scene.time, scene.dt, scene.rdt = times[0], dts[0], rdts[0]
-            for program in clock.programs:
-                if program.program is None:
-                    program.compile()
-                if not program.texture.final:
-                    program.use_scene_pipeline()
-            from shaderflow_amd import _native as N
+            clock.prime(times, dts, rdts)
             N.check(N.lib().sfx_tape_reset(tape.handle))
             native = clock.native_sequence(export, turbo)
             try:
                 clock.run_native(export, times, dts, rdts, total, tape=tape, pipe_here=not native, turbo=turbo)
             finally:
-                for program in clock.programs:
-                    program._pushed.clear(); program._pushed_plain.clear(); program._module_tokens.clear()
+                clock.forget_sent()
             self.frames = export.frame
             # the clock of the last frame; the audio modules' host state and textures are as the export found them (FrameTape.export)
             last = max(0, min(total, export.frame) - 1)
