@@ -175,7 +175,10 @@ class Tetration(ShaderScene):
 
 class Video(ShaderScene):
     """Video as a texture (shaderflow/video.py + examples/basic/shaders/video.frag; demo.py has no scene for it):
-    `clip` = (frames (n, h, w, 3) uint8, fps) or a path"""
+    `clip` = (frames (n, h, w, 3) uint8, fps) or a path: a `.npy` of such frames, a `.y4m` file (YUV4MPEG2, 8-bit progressive 4:2:0, read
+    natively: size and rate come from its header), or any container an ffmpeg binary on PATH decodes. Raw `.rgb` and raw planar `.yuv` /
+    `.i420` files carry no size: give them to a ShaderVideo of your own with `width=`, `height=` and `fps=` (shaderflow_amd/video.py).
+    Without python logic of its own the scene is drawn by the video sequence (shaderflow_amd/videosequence.py)."""
     clip = None
 
     def build(self):

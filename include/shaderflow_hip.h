@@ -376,6 +376,33 @@ int sfx_piano_state_read(sfx_handle piano, float* state /* [5][128] */);   /* wa
 int sfx_piano_destroy(sfx_handle piano);
 
 /* ------------------------------------------------------------------------------------------------ */
+/* Video — ShaderVideo.update() (reference: shaderflow/video.py:57-66: when scene.time passes the next frame's timestamp, the next source
+ * frame is flipped to GL order and written into the texture after its temporal matrix rolled) without a host copy per frame: source
+ * frames are staged in pinned host memory, copied host → device on a copy stream of the handle's own, and k_video_frame
+ * (csrc/video_kernels.hpp) puts each one into the RGB8 video texture on the context's stream — rows flipped, and converted when the
+ * source is planar 4:2:0: BT.601 limited range in integer arithmetic, C = Y - 16, D = U - 128, E = V - 128,
+ * R = clip8((298 C + 409 E + 128) >> 8), G = clip8((298 C - 100 D - 208 E + 128) >> 8), B = clip8((298 C + 516 D + 128) >> 8), chroma
+ * replicated over its 2 x 2 block. The counterpart of sfx_rgb_to_yuv420 and, like it, defined by this project: unpinned against swscale. */
+enum { SFX_VIDEO_RGB24 = 0 /* height x width x 3 bytes, top row first; any extents */,
+       SFX_VIDEO_I420 = 1  /* Y (height x width), U, V (height/2 x width/2), top row first; even extents */ };
+/* video.py:57-66. `boxes`: the `temporal` texture handles of the video's texture matrix in its current order (layers must be 1; RGB8,
+ * width x height). The handle owns `slots` pinned host frames, `slots` device staging frames, one event per slot and one copy stream
+ * beside the context's stream. */
+int sfx_video_create(sfx_handle ctx, const sfx_handle* boxes, int temporal, int width, int height, int format, int slots, sfx_handle* video);
+/* video.py:57-66 (`next(self.frames)`): the pinned frame the host reads a source frame into, and its size. Waits until the kernel that
+ * consumed the slot's previous frame has run; SFX_E_INVALID while a submitted frame that was not consumed occupies the slot. */
+int sfx_video_slot(sfx_handle video, int slot, void** host, size_t* nbytes);
+/* video.py:57-66 (the upload of `texture.write`): queues the slot's host → device copy on the copy stream and records the slot's event;
+ * returns at once. SFX_E_INVALID when a submitted but not yet consumed frame still occupies the slot. */
+int sfx_video_submit(sfx_handle video, int slot);
+/* video.py:57-66 (`texture.roll(); texture.write(frame)`) for one frame outside a sequence, queued on the context's stream: the stream
+ * waits for the slot's event, the handle's own copy of the matrix rolls by one, k_video_frame writes the box now at the front, and the
+ * slot is marked free behind the kernel. SFX_E_INVALID when the slot holds no submitted frame. */
+int sfx_video_step(sfx_handle video, int slot);
+/* video.py:57-66 has no counterpart: stops the copy stream, then frees the staging */
+int sfx_video_destroy(sfx_handle video);
+
+/* ------------------------------------------------------------------------------------------------ */
 /* The frame sequence: the frame loop of a scene in which nothing but the clock moves (layered / temporal scenes without host logic:
  * demo.py's Multipass, MotionBlur, Life), `nframes` frames in ONE call: scene.next (scene.py:456-479) = every program's render
  * (shader.py:388-405: a draw per layer into row 0 of its texture matrix, then texture.roll(), texture.py:295-298), iFinal's resolve
@@ -392,7 +419,13 @@ int sfx_piano_destroy(sfx_handle piano);
  *
  * With a piano (a scene with one ShaderPiano): per frame, in front of the first pass, the piano's frame (sfx_piano_step with
  * piano_ticks[f]) and piano_ticks[f].dynamic stored into the uniform `piano_dynamic_name` ("iPianoDynamic") of every pass' program
- * that has one. A tape and a piano in one call are refused (SFX_E_UNSUPPORTED). */
+ * that has one. A tape and a piano in one call are refused (SFX_E_UNSUPPORTED).
+ *
+ * With a video (a scene with one ShaderVideo): video_slots[f] is the slot whose staged frame lands in front of frame f's first pass
+ * (what sfx_video_step does), or -1 for a scene frame that shows what was there. When the video's matrix is temporal, `video_names`
+ * holds the sampler name of each of its rows (depth 0 first) and every pass' program that declares one gets the row now at that depth
+ * — the mechanism of sfx_sequence_matrix.names, except that this matrix rolls on landing frames only (the host rolls its own by the
+ * number of landings afterwards). A video together with a tape or a piano in one call is refused (SFX_E_UNSUPPORTED). */
 enum { SFX_PASS_LAYERS = 0, SFX_PASS_FUSED = 1, SFX_PASS_RESOLVE = 2 };
 typedef struct sfx_sequence_pass { sfx_handle program; int kind; int matrix; sfx_handle target; int ssaa; int subsample; } sfx_sequence_pass;
 typedef struct sfx_sequence_matrix { int temporal, layers; const sfx_handle* textures; const char* const* names; } sfx_sequence_matrix;
@@ -416,6 +449,8 @@ typedef struct sfx_sequence {
     sfx_handle tape; int tape_frame0;
     /* optional: the piano. piano == 0: none */
     sfx_handle piano; const sfx_piano_tick* piano_ticks; const char* piano_dynamic_name;
+    /* optional: the video. video == 0: none */
+    sfx_handle video; const int32_t* video_slots; const char* const* video_names;
 } sfx_sequence;
 int sfx_sequence_run(sfx_handle ctx, const sfx_sequence* sequence);
 

@@ -66,6 +66,7 @@ class ClockTick(C.Structure):
 
 
 PASS_LAYERS, PASS_FUSED, PASS_RESOLVE = 0, 1, 2
+VIDEO_RGB24, VIDEO_I420 = 0, 1
 
 
 class PianoParams(C.Structure):
@@ -77,13 +78,14 @@ class PianoTick(C.Structure):
 
 
 class Sequence(C.Structure):
-    """sfx_sequence (include/shaderflow_hip.h), field for field: the tables, the sink, the optional tape, the optional piano"""
+    """sfx_sequence (include/shaderflow_hip.h), field for field: the tables, the sink, the optional tape, the optional piano, the optional video"""
     _fields_ = [("passes", C.POINTER(SequencePass)), ("npasses", C.c_int), ("matrices", C.POINTER(SequenceMatrix)), ("nmatrices", C.c_int),
                 ("clock", C.POINTER(ClockTick)), ("nframes", C.c_int),
                 ("ring", Handle), ("first_slot", C.c_int), ("fd", C.c_int), ("planar_slots", C.POINTER(C.c_void_p)),
                 ("yuv_matrix", C.c_int), ("width", C.c_int), ("height", C.c_int),
                 ("tape", Handle), ("tape_frame0", C.c_int),
-                ("piano", Handle), ("piano_ticks", C.POINTER(PianoTick)), ("piano_dynamic_name", C.c_char_p)]
+                ("piano", Handle), ("piano_ticks", C.POINTER(PianoTick)), ("piano_dynamic_name", C.c_char_p),
+                ("video", Handle), ("video_slots", C.POINTER(C.c_int32)), ("video_names", C.POINTER(C.c_char_p))]
 
 
 class Binding(C.Structure):
@@ -194,6 +196,11 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_piano_step": (C.c_int, [Handle, C.c_double, P(DynCoeffF32), C.c_int]),
     "sfx_piano_state_read": (C.c_int, [Handle, P(C.c_float)]),
     "sfx_piano_destroy": (C.c_int, [Handle]),
+    "sfx_video_create": (C.c_int, [Handle, P(Handle), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(Handle)]),
+    "sfx_video_slot": (C.c_int, [Handle, C.c_int, P(C.c_void_p), P(C.c_size_t)]),
+    "sfx_video_submit": (C.c_int, [Handle, C.c_int]),
+    "sfx_video_step": (C.c_int, [Handle, C.c_int]),
+    "sfx_video_destroy": (C.c_int, [Handle]),
     "sfx_sequence_run": (C.c_int, [Handle, P(Sequence)]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),
     "sfx_device_free": (C.c_int, [Handle, C.c_void_p]),

@@ -131,11 +131,13 @@ class ClockLoop:
         return all(program.program is not None for program in self.programs)
 
     def run_native(self, export: "ExportingHelper", times, dts, rdts, total: int, tape: "Optional[FrameTape]" = None, pipe_here: bool = False,
-                   turbo: bool = True, piano=None) -> None:
+                   turbo: bool = True, piano=None, video=None) -> None:
         """Every chunk of frames is one sfx_sequence_run. With a `tape` (tapesequence.py) the frames go in the tape's batches: each batch is
         built, then drawn in chunks that stay inside it. `pipe_here`: one frame per call, read out by export.pipe (a progress relay, no
         turbo). With a `piano` (pianosequence.py: `.handle`, `.ticks(first, count)` = the frames' sfx_piano_tick table, `.dynamic_name` = the
-        module's `<name>Dynamic` uniform) the piano's frame goes in front of every frame's passes."""
+        module's `<name>Dynamic` uniform) the piano's frame goes in front of every frame's passes. With a `video` (videosequence.py: `.handle`,
+        `.names` = the sampler names of a temporal matrix, `.take(first, count)` = how many frames the next call may draw and the slot
+        each of them lands, `.consumed(first, count, slots)` behind the call) a staged source frame goes in front of the frames that land one."""
         scene, lib = self.scene, N.lib()
         runtime, fps = scene.runtime, scene.fps
         # texture matrices: every program's own (its draws go to row 0) — the same objects `rolling` lists when they are temporal
@@ -174,6 +176,9 @@ class ClockLoop:
             sequence.tape = tape.handle
         if piano is not None:
             sequence.piano, sequence.piano_dynamic_name = piano.handle, piano.dynamic_name
+        if video is not None:
+            video_names = video.names
+            sequence.video, sequence.video_names = video.handle, video_names
         done = 0
         per_frame = None                                               # seconds per frame of the last native call
         import time as clock
@@ -185,6 +190,9 @@ class ClockLoop:
             while done < first + size and not scene.quit:
                 count = 1 if pipe_here else min(self.chunk_frames(per_frame), first + size - done)
                 export._check_encoder()
+                if video is not None:
+                    count, landing = video.take(done, count)         # (may wait for the reader: not part of the frames' measured time)
+                    sequence.video_slots = landing.ctypes.data_as(C.POINTER(C.c_int32))
                 started = clock.perf_counter()
                 ticks = (N.ClockTick*count)()
                 for i in range(count):
@@ -196,6 +204,8 @@ class ClockLoop:
                     sequence.piano_ticks = piano.ticks(done, count)
                 N.check(lib.sfx_sequence_run(scene.context.handle, C.byref(sequence)))
                 per_frame = (clock.perf_counter() - started)/count
+                if video is not None:
+                    video.consumed(done, count, landing)
                 for texture in textures:
                     texture.roll(count)                               # the native call rolled its own copy of every matrix it drew into
                 if pipe_here:

@@ -1,7 +1,7 @@
 // capi.hip — implementation of include/shaderflow_hip.h (the C-ABI over the gfx950 kernels): contexts, textures, programs (the fragment
 // registry, uniform / sampler tables), the render dispatch into the launch units (launch.hpp), the clock sequence and the render
 // from a tape. Host-side state only. The read-out rings and peer copies live in capi_readout.hip, the audio plans and the tape in
-// capi_audio.hip; host_state.hpp holds what the three share.
+// capi_audio.hip, the piano roll in capi_piano.hip, the video staging in capi_video.hip; host_state.hpp holds what they share.
 
 #include "launch.hpp"
 #include "launch_geometry.hpp"
@@ -1057,6 +1057,8 @@ struct SequencePlan {
     std::vector<char> audio;                                         // pass k draws from the tape (reads_audio)
     struct DynamicSlot { Program* p; int slot; };
     std::vector<DynamicSlot> dynamic_slots;                          // where the piano's note range lives in user[] of every program that declares it
+    struct VideoBind { Program* p; int slot, depth; };
+    std::vector<VideoBind> video_binds;                              // sampler slots of every (program, named row of the video's temporal matrix)
 };
 
 static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) {
@@ -1065,6 +1067,12 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
     if (!s.passes || s.npasses < 1 || s.nmatrices < 0 || (s.nmatrices && !s.matrices) || !s.clock || s.nframes < 0) return fail(SFX_E_INVALID, "clock sequence: null tables");
     if (plan.ring_slots < 0) return fail(SFX_E_INVALID, "clock sequence: invalid ring handle");
     if (s.tape && s.piano) return fail(SFX_E_UNSUPPORTED, "sequence: a tape and a piano in one call are not supported");
+    if (s.video && (s.tape || s.piano)) return fail(SFX_E_UNSUPPORTED, "sequence: a video together with a tape or a piano in one call is not supported");
+    int video_rows = 0;
+    if (s.video) {
+        if (!s.video_slots) return fail(SFX_E_INVALID, "video sequence: null slot table");
+        if ((video_rows = video_temporal(s.video, c)) < 1) return fail(SFX_E_INVALID, "video sequence: invalid video handle, or one of another context");
+    }
     if (s.tape) {
         if (!tape_view(s.tape, &plan.tape)) return fail(SFX_E_INVALID, "tape sequence: invalid tape handle");
         if (plan.tape.ctx != c) return fail(SFX_E_INVALID, "tape sequence: the tape belongs to another context");
@@ -1100,6 +1108,11 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
                 if (slot >= 0) plan.binds.push_back({p, slot, m, d, l});
             }
         }
+        if (video_rows > 1 && s.video_names)
+            for (int d = 0; d < video_rows; d++) {
+                const int slot = s.video_names[d] ? resolve_sampler(p, s.video_names[d]) : -1;
+                if (slot >= 0) plan.video_binds.push_back({p, slot, d});
+            }
         // (the stock fragments declare no note range: a translated one by its bindings)
         if (s.piano && s.piano_dynamic_name)
             for (const auto& b : p->bindings)
@@ -1111,7 +1124,8 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
 // The frames of sfx_sequence_run. With a tape, frame f of the call is tape frame tape_frame0 + f of the bank the last build filled:
 // every pass whose program reads audio takes that frame's audio state from the tape — a layered pass draws through render_box, a fused
 // one through sfx_render_tape into iFinal — and every other pass is drawn exactly as without a tape. With a piano, k_piano_frame and
-// the note range go in front of every frame's first pass (pianosequence.py).
+// the note range go in front of every frame's first pass (pianosequence.py). With a video, k_video_frame goes in front of the first pass
+// of every frame a source frame lands on (videosequence.py).
 static int run_sequence(sfx_handle hc, Context* c, const sfx_sequence& s, SequencePlan& plan) {
     const TapeView* t = plan.taped ? &plan.tape : nullptr;
     auto box = [&](int m, int d, int l) -> sfx_handle {
@@ -1133,6 +1147,12 @@ static int run_sequence(sfx_handle hc, Context* c, const sfx_sequence& s, Sequen
             if (rc) return rc;
             for (const auto& d : plan.dynamic_slots) { d.p->u.user[d.slot] = tick.dynamic[0]; d.p->u.user[d.slot + 1] = tick.dynamic[1]; }
         }
+        if (s.video && s.video_slots[f] >= 0) {
+            // ShaderVideo.update() of a frame whose time passed the next source frame's timestamp (video.py:57-66): the matrix rolls and the
+            // staged frame is written into its front box on the render stream, in front of the draws that sample it
+            const int rc = video_launch_frame(s.video, c, s.video_slots[f]);
+            if (rc) return rc;
+        }
         for (int k = 0; k < s.npasses; k++) {
             const sfx_sequence_pass& pass = s.passes[k];
             if (pass.kind == SFX_PASS_RESOLVE) {
@@ -1145,6 +1165,7 @@ static int run_sequence(sfx_handle hc, Context* c, const sfx_sequence& s, Sequen
             Program* p = get<Program>(pass.program, MAGIC_PROG);
             p->u.iTime = now.time; p->u.iTau = now.tau; p->u.iDeltatime = now.deltatime; p->u.iFrame = now.frame;      // sfx_uniform_set_clock
             for (const auto& b : plan.binds) if (b.p == p) b.p->samplers[b.slot] = get<Texture>(box(b.m, b.t, b.l), MAGIC_TEX);
+            for (const auto& b : plan.video_binds) if (b.p == p) b.p->samplers[b.slot] = get<Texture>(video_box(s.video, b.depth), MAGIC_TEX);
             if (pass.kind == SFX_PASS_FUSED) {
                 int rc;
                 if (plan.audio[k]) {

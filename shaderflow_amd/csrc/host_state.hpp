@@ -1,5 +1,5 @@
 // host_state.hpp — what the translation units of libshaderflow_hip.so share on the HOST side: error reporting, handles, the context and
-// texture objects, and the few calls the C-ABI units (capi.hip, capi_readout.hip, capi_audio.hip) make into each other. capi.hip owns the
+// texture objects, and the few calls the C-ABI units (capi.hip, capi_readout.hip, capi_audio.hip, capi_piano.hip, capi_video.hip) make into each other. capi.hip owns the
 // definitions of the thread-local state; the launch units (launch_*.hip) only read it.
 #pragma once
 
@@ -19,7 +19,7 @@ int launch_status();                              // hipGetLastError() after a l
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(SFX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 enum : uint32_t { MAGIC_CTX = 0x53465843, MAGIC_TEX = 0x53465854, MAGIC_PROG = 0x53465850, MAGIC_RING = 0x53465852,
-                  MAGIC_AUDIO = 0x53465841, MAGIC_PLAN = 0x5346584c, MAGIC_TAPE = 0x53465854 + 0x100, MAGIC_SHM = 0x53465853, MAGIC_PIANO = 0x53465850 + 0x100 };
+                  MAGIC_AUDIO = 0x53465841, MAGIC_PLAN = 0x5346584c, MAGIC_TAPE = 0x53465854 + 0x100, MAGIC_SHM = 0x53465853, MAGIC_PIANO = 0x53465850 + 0x100, MAGIC_VIDEO = 0x53465856 };
 
 struct Object { uint32_t magic; };
 
@@ -91,3 +91,9 @@ bool tape_view(sfx_handle tape, TapeView* view);
 int tape_screen_scratch(sfx_handle tape, size_t bytes, hipStream_t stream, void** screen);   // iScreen of the two-pass path, grown on demand
 // capi_piano.hip: k_piano_frame for one frame on the context's render stream (the piano sequence launches it in front of the frame's draws)
 int piano_launch_frame(sfx_handle piano, Context* c, double scene_time, const sfx_dyn_coeff_f32& coeff, int previous_is_target);
+// capi_video.hip: one landing frame of a ShaderVideo on the context's render stream — the render stream waits for the slot's copy, the
+// handle's matrix rolls by one, k_video_frame writes the box now at the front, the slot is free behind the kernel (the video sequence
+// launches it in front of the scene frame that first shows the source frame)
+int video_launch_frame(sfx_handle video, Context* c, int slot);
+sfx_handle video_box(sfx_handle video, int depth);    // the box `depth` frames back in the handle's current order; 0: none
+int video_temporal(sfx_handle video, Context* c);     // rows of the handle's matrix; -1: not a video of this context

@@ -66,6 +66,7 @@ class ShaderScene(ShaderModule):
     tape_loop = None                                          # plain class attribute: the TapeLoop of the last main(), if it took one
     tape_sequence = None                                      # … and the TapeSequence (tapesequence.py)
     piano_sequence = None                                     # … and the PianoSequence (pianosequence.py)
+    video_sequence = None                                     # … and the VideoSequence (videosequence.py)
     _fused_this_frame: bool = False
     _skip_render: bool = False
     shard_warmup = "auto"                                     # plain class attribute: subclasses override it like `life_period`
@@ -344,6 +345,7 @@ class ShaderScene(ShaderModule):
         self.tape_loop = None
         self.tape_sequence = None
         self.piano_sequence = None
+        self.video_sequence = None
 
         _width, _height = self.resize(width=width, height=height, ratio=ratio, scale=scale)
 
@@ -385,6 +387,12 @@ class ShaderScene(ShaderModule):
         from shaderflow_amd.clockloop import ClockLoop
         if self.freewheel and batch is None and self.clock_loop and ClockLoop.applicable(self):
             return ClockLoop(self).run(export, turbo)
+        # a ShaderVideo scene without python logic: source frames staged ahead in pinned memory, put into the texture in front of the frame
+        # that first shows them (videosequence.py)
+        from shaderflow_amd.videosequence import VideoSequence
+        if batch is None and VideoSequence.applicable(self, export, turbo):
+            self.video_sequence = VideoSequence(self)
+            return self.video_sequence.run(export, turbo)
         # a ShaderPiano scene without python logic: the score on the device, its textures made in front of every frame's draws (pianosequence.py)
         from shaderflow_amd.pianosequence import PianoSequence
         if batch is None and PianoSequence.applicable(self, export, turbo):

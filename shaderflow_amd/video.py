@@ -7,15 +7,28 @@ rule: a frame is uploaded only when `scene.time > frames_read/fps` (so nothing i
 frame), rows flipped to GL order, after rolling the temporal matrix.
 
 Where frames come from: the reference pipes the file through an `ffmpeg` subprocess (ffmpeg.py:1116-1137). Here:
-  * `frames=` any iterable of (height, width, 3) uint8 arrays, top row first — what that iterator yields;
+  * `frames=` any iterable of (height, width, 3) uint8 arrays, top row first — what that iterator yields; with `format="i420"` the
+    iterable yields 1-D uint8 arrays of width*height*3//2 bytes instead (planar 4:2:0: Y, U, V, top row first);
   * `path=` a `.npy` holding (n, height, width, 3) uint8, or a raw `.rgb` file with `width`/`height` given;
+  * `path=` a `.y4m` file (YUV4MPEG2, the uncompressed interchange format: 1.5 bytes per pixel), read natively: width, height and
+    fps come from its header. 8-bit progressive 4:2:0 only (`C420`, `C420jpeg`, `C420mpeg2`, `C420paldv`, or no `C` tag): another
+    chroma layout, a higher bit depth, interlacing or `XCOLORRANGE=FULL` raise ValueError naming the tag;
+  * `path=` a raw `.yuv` / `.i420` file with `width`, `height` and `fps` given: planar 4:2:0 frames, what this package's own
+    yuv420p export writes (exporting.py);
   * any other `path` is decoded by an `ffmpeg` binary on PATH when there is one (rawvideo rgb24 over a pipe),
     otherwise construction raises — there is no silent fallback.
 A source shorter than the scene keeps its last frame on screen (the reference's generator would raise
 StopIteration out of `update`).
+
+Planar sources are converted on the device by `k_video_frame` (csrc/video_kernels.hpp): BT.601 limited range in integer arithmetic,
+chroma replicated over its 2 x 2 block — this project's own definition, **unpinned against swscale** (no ffmpeg binary to pin it
+against), like the yuv420p output. The frame loop shows them through the same kernel (`VideoStage`: a pinned frame, an asynchronous
+copy, one launch), so the conversion has one definition; rgb sources in the frame loop are flipped and uploaded by the host as ever.
+Scenes that qualify draw whole chunks of frames per native call instead (videosequence.py).
 """
 from __future__ import annotations
 
+import ctypes as C
 import shutil
 import subprocess
 from collections.abc import Iterable, Iterator
@@ -25,8 +38,12 @@ from typing import Optional
 import numpy as np
 from attrs import define
 
+from shaderflow_amd import _native as N
 from shaderflow_amd.module import ShaderModule, logger
 from shaderflow_amd.texture import ShaderTexture
+
+Y4M_CHROMA = ("420", "420jpeg", "420mpeg2", "420paldv")              # all read as the same 8-bit 4:2:0 bytes (the siting is not interpolated)
+PLANAR_SUFFIXES = (".yuv", ".i420")                                   # raw planar frames: the suffixes exporting.py's yuv420p sink writes
 
 
 def _probe(path: Path) -> tuple[int, int, float]:
@@ -50,6 +67,133 @@ def iter_video_frames(path: Path, width: int, height: int) -> Iterator[np.ndarra
         process.kill()
 
 
+def parse_y4m_header(line: bytes) -> tuple[int, int, float]:
+    """(width, height, fps) of a YUV4MPEG2 stream header; ValueError names the tag this reader does not take"""
+    tokens = line.rstrip(b"\n").decode("ascii", "replace").split(" ")
+    if tokens[0] != "YUV4MPEG2":
+        raise ValueError(f"not a YUV4MPEG2 stream: it begins with {tokens[0][:16]!r}")
+    width = height = fps = None
+    for token in filter(None, tokens[1:]):
+        tag, value = token[0], token[1:]
+        if tag == "W":
+            width = int(value)
+        elif tag == "H":
+            height = int(value)
+        elif tag == "F":
+            num, _, den = value.partition(":")
+            fps = float(int(num))/float(int(den or 1))
+        elif tag == "I" and value != "p":
+            raise ValueError(f"y4m tag {token!r}: only progressive frames (Ip) are read")
+        elif tag == "C" and value not in Y4M_CHROMA:
+            raise ValueError(f"y4m tag {token!r}: only 8-bit 4:2:0 ({', '.join('C' + c for c in Y4M_CHROMA)}) is read")
+        elif tag == "X" and value.upper() == "COLORRANGE=FULL":
+            raise ValueError(f"y4m tag {token!r}: only limited-range video is read")
+    if not (width and height and fps) or width < 1 or height < 1 or fps <= 0:
+        raise ValueError(f"y4m header without W, H and F: {line[:80]!r}")
+    if width % 2 or height % 2:
+        raise ValueError(f"y4m W{width} H{height}: 4:2:0 frames need even extents")
+    return width, height, fps
+
+
+class PlanarFile:
+    """Frames of a `.y4m` or raw planar file, in order: an iterator of 1-D uint8 arrays of width*height*3//2 bytes, and `readinto(view)`
+    for a caller with a buffer of its own (the sequence's pinned slots: no intermediate array). A truncated last frame ends the clip,
+    as a short read ends iter_video_frames."""
+
+    def __init__(self, path: Path, width: Optional[int] = None, height: Optional[int] = None, fps: Optional[float] = None):
+        self.path, self.y4m = Path(path), Path(path).suffix.lower() == ".y4m"
+        self.file = open(self.path, "rb", buffering=0)
+        if self.y4m:
+            header = self._line(limit=4096)
+            width, height, fps = parse_y4m_header(header)
+        self.width, self.height, self.fps = width, height, fps
+        self.frame_bytes = width*height*3//2
+
+    def _line(self, limit: int = 256) -> bytes:
+        """Up to and including the next newline (unbuffered file: a few bytes at a time only for these short lines)"""
+        line = bytearray()
+        while len(line) < limit and (byte := self.file.read(1)):
+            line += byte
+            if byte == b"\n":
+                break
+        return bytes(line)
+
+    def readinto(self, view) -> bool:
+        """The next frame into `view` (a writable buffer of frame_bytes bytes); False at the end of the clip"""
+        if self.file is None:
+            return False
+        if self.y4m:
+            line = self._line()
+            if not line:
+                return self._end()
+            if not (line.startswith(b"FRAME") and line.endswith(b"\n")):
+                raise ValueError(f"{self.path}: expected a FRAME line, found {line[:32]!r}")
+            if any(token[:1] == b"I" for token in line[5:].split()):
+                raise ValueError(f"{self.path}: frame tag {line[5:].strip()!r}: per-frame interlacing is not read")
+        target, got = memoryview(view).cast("B"), 0
+        while got < self.frame_bytes:
+            count = self.file.readinto(target[got:])
+            if not count:
+                return self._end()                                    # a truncated last frame ends the clip
+            got += count
+        return True
+
+    def _end(self) -> bool:
+        self.file.close()
+        self.file = None
+        return False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> np.ndarray:
+        frame = np.empty(self.frame_bytes, np.uint8)
+        if not self.readinto(frame):
+            raise StopIteration
+        return frame
+
+
+class VideoStage:
+    """sfx_video_* (include/shaderflow_hip.h) for one ShaderVideo: `slots` pinned frames the host fills (`view`), their asynchronous
+    copies (`submit`) and k_video_frame into the texture matrix (`step`, or a landing frame of the native sequence). The handle holds
+    the matrix' boxes in their order at creation and rolls with every frame it lands: the host rolls its ShaderTexture alike."""
+
+    def __init__(self, video: "ShaderVideo", slots: int):
+        texture = video.texture
+        if texture.layers != 1 or texture.components != 3 or texture.dtype != np.uint8:
+            raise ValueError("a staged video needs an RGB8 texture with layers = 1")
+        boxes = [box.texture for (_, _, box) in texture.boxes]
+        self.serials = tuple(box.serial for box in boxes)              # which device textures the handle writes into
+        self.planar = video.format == "i420"
+        self.slots, self.handle = slots, N.Handle()
+        handles = (N.Handle*len(boxes))(*[box.handle for box in boxes])
+        N.check(N.lib().sfx_video_create(video.scene.context.handle, handles, texture.temporal, video.width, video.height,
+                                         N.VIDEO_I420 if self.planar else N.VIDEO_RGB24, slots, C.byref(self.handle)))
+
+    def view(self, slot: int) -> np.ndarray:
+        """The slot's pinned frame as a 1-D uint8 array (waits until the frame it held before has been consumed)"""
+        pointer, nbytes = C.c_void_p(), C.c_size_t()
+        N.check(N.lib().sfx_video_slot(self.handle, slot, C.byref(pointer), C.byref(nbytes)))
+        return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(C.c_uint8)), shape=(nbytes.value,))
+
+    def submit(self, slot: int) -> None:
+        N.check(N.lib().sfx_video_submit(self.handle, slot))
+
+    def step(self, slot: int) -> None:
+        N.check(N.lib().sfx_video_step(self.handle, slot))
+
+    def release(self) -> None:
+        if self.handle is not None and self.handle.value:
+            N.lib().sfx_video_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 @define(eq=False, slots=False)
 class ShaderVideo(ShaderModule):
     name: str = "iVideo"
@@ -59,21 +203,28 @@ class ShaderVideo(ShaderModule):
     width: Optional[int] = None
     height: Optional[int] = None
     fps: Optional[float] = None
+    format: Optional[str] = None
+    """None: the source yields rgb arrays; "i420": planar 4:2:0 frames of width*height*3//2 bytes (set by the planar file sources)"""
+    _stage: Optional[VideoStage] = None
     _reader: Optional[Iterator] = None
     _read: int = 0
     _exhausted: bool = False
 
     def __attrs_post_init__(self):
         ShaderModule.__attrs_post_init__(self)
+        if self.format not in (None, "i420"):
+            raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays) or 'i420'")
         self._reader = self._open()
         if not all((self.width, self.height, self.fps)):
             raise ValueError("ShaderVideo needs width, height and fps (give them, or a source they can be read from)")
+        if self.format == "i420" and (self.width % 2 or self.height % 2):
+            raise ValueError(f"a 4:2:0 source needs even extents, not {self.width} x {self.height}")
         self.texture = ShaderTexture(scene=self.scene, name=self.name, width=self.width, height=self.height,
                                      dtype=np.uint8, components=3)
 
     def _open(self) -> Iterator[np.ndarray]:
         if self.frames is not None:
-            if isinstance(self.frames, np.ndarray):
+            if isinstance(self.frames, np.ndarray) and self.format is None:
                 self.height, self.width = self.height or self.frames.shape[1], self.width or self.frames.shape[2]
             return iter(self.frames)
         if self.path is None:
@@ -89,6 +240,12 @@ class ShaderVideo(ShaderModule):
                 raise ValueError("raw rgb24 video needs width= and height=")
             clip = np.memmap(self.path, np.uint8, "r").reshape(-1, self.height, self.width, 3)
             return iter(clip)
+        if suffix == ".y4m" or suffix in PLANAR_SUFFIXES:
+            if suffix != ".y4m" and not all((self.width, self.height, self.fps)):
+                raise ValueError("raw planar yuv420p video needs width=, height= and fps=")
+            clip = PlanarFile(self.path, self.width, self.height, self.fps)
+            self.width, self.height, self.fps, self.format = clip.width, clip.height, self.fps or clip.fps, "i420"
+            return clip
         if not (shutil.which("ffmpeg") and shutil.which("ffprobe")):
             raise RuntimeError(f"{self.path}: decoding this container needs the ffmpeg and ffprobe binaries; "
                                "give frames=, a .npy clip or a raw .rgb file instead")
@@ -105,7 +262,34 @@ class ShaderVideo(ShaderModule):
             self._exhausted = True
             logger.warning(f"{self.name}: source ended after {self._read} frames, holding the last one")
             return
-        frame = np.ascontiguousarray(np.flip(np.asarray(frame, np.uint8), axis=0))
-        self.texture.roll()
-        self.texture.write(frame)
+        if self.format == "i420":
+            self._show_planar(frame)
+        else:
+            frame = np.ascontiguousarray(np.flip(np.asarray(frame, np.uint8), axis=0))
+            self.texture.roll()
+            self.texture.write(frame)
         self._read += 1
+
+    def _show_planar(self, frame) -> None:
+        """A planar frame through k_video_frame, the one definition of the conversion: a pinned slot, its copy, the kernel"""
+        boxes = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
+        if self._stage is not None and self._stage.serials != boxes:      # the texture was re-made, or rolled by somebody else
+            self._stage.release()
+            self._stage = None
+        if self._stage is None:
+            self._stage = VideoStage(self, slots=1)
+        frame = np.asarray(frame, np.uint8).reshape(-1)
+        if frame.size != self.width*self.height*3//2:
+            raise ValueError(f"{self.name}: an i420 frame of {self.width} x {self.height} has {self.width*self.height*3//2} bytes, not {frame.size}")
+        np.copyto(self._stage.view(0), frame)
+        self._stage.submit(0)
+        self._stage.step(0)
+        self.texture.roll()
+        self._stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
+        box = self.texture.get_box()
+        box.data, box.empty = box.texture.read().tobytes(), False        # the host copy of the last full write, as texture.write keeps it
+
+    def destroy(self) -> None:
+        if self._stage is not None:
+            self._stage.release()
+            self._stage = None
