@@ -8,7 +8,8 @@ the four clock uniforms (iTime, iTau, iDeltatime, iFrame: scene.py:687-703), `iL
 behind every sampler of a temporal texture after its `roll()` (texture.py:295-298, 351-381). This loop does that and nothing else
 per frame: one `sfx_uniform_set_clock`, one `sfx_sampler_bind_many` per rolled texture matrix, the draws, the resolve, the read-out.
 Same launches in the same order with the same uniform values as the frame loop, so the same frames byte for byte
-(tests/test_gpu_multipass.py); anything it is not sure about takes the frame loop.
+(tests/test_gpu_multipass.py); anything it is not sure about takes the frame loop. The loops that put something in front of the frames'
+passes — an audio tape, a piano, a staged video — run the same native sequence through a `FrameSource`, `run_source` and `sequence_gate`.
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ from shaderflow_amd import _native as N
 from shaderflow_amd.camera import CameraMode, ShaderCamera
 from shaderflow_amd.dynamics import ShaderDynamics
 from shaderflow_amd.module import ShaderModule
-from shaderflow_amd.parallel import shard_batches
+from shaderflow_amd.parallel import is_sharded
 from shaderflow_amd.scheduler import freewheel_clock
 from shaderflow_amd.shader import ShaderProgram
 from shaderflow_amd.texture import ShaderTexture
@@ -29,13 +30,69 @@ from shaderflow_amd.texture import ShaderTexture
 if TYPE_CHECKING:
     from shaderflow_amd.exporting import ExportingHelper
     from shaderflow_amd.scene import ShaderScene
-    from shaderflow_amd.tape import FrameTape
+
+
+def box_handles(texture: ShaderTexture):
+    """The device textures behind a matrix' samplers, in the order of `boxes`, as a C array"""
+    return (N.Handle*(texture.temporal*texture.layers))(*[box.texture.handle if box.texture is not None else N.Handle() for (_, _, box) in texture.boxes])
+
+
+def end_clock(policy: str, fps: float, speed: float, done: int) -> tuple[float, float, float]:
+    """(time, dt, rdt) a loop leaves on the scene behind `done` >= 1 frames; the three loops differ on purpose, and tests pin them.
+    "last": the last frame drawn (ClockLoop); "last_dt": the same with rdt = dt, as FrameTape.export leaves it (TapeSequence); "next": what
+    scene.next leaves behind the last frame — it integrates time AFTER the frame (reference scene.py:475-479), so what a frame more
+    would have seen (PianoSequence, VideoSequence)."""
+    times, dts, rdts = freewheel_clock(fps, done + 1, speed)
+    if policy == "next":
+        return times[done], dts[done], rdts[done]
+    last = done - 1
+    return times[last], dts[last], {"last": rdts, "last_dt": dts}[policy][last]
+
+
+class FrameSource:
+    """What feeds sfx_sequence_run beside the clock: an audio tape, a piano, a staged video (tapesequence.py, pianosequence.py,
+    videosequence.py). `run_native` calls batches … consumed of its source, `run_source` the rest; as they stand here they do nothing,
+    and that is the clock loop's own source."""
+    end = "last"                                                       # the clock behind the run (end_clock)
+    chunked = True                                                     # sequence_gate saw to it that every chunk can be ONE native call; False: native_sequence is asked
+
+    def prepare(self, times, dts, total): pass                        # in front of `prime`: the device objects, what the run needs for every frame
+    def batches(self, total): return [(0, total)]                     # the frame ranges (first, size) the run is cut into; a chunk stays inside one
+    def begin_batch(self, first, size): pass
+    def attach(self, sequence): pass                                  # the descriptor fields that hold for the whole run
+    def take(self, sequence, first, count, batch_first): return count  # … and those of the call that draws `count` frames from `first`; it may shorten the call
+    def consumed(self, first, count): pass                            # behind a native call that succeeded
+    def settle(self, done): pass                                      # behind the run, however it ended: the host objects as the frame loop leaves them after `done` frames
+    def finished(self, done, total): return True                      # whether a run_native that returned ran to its end (else a read-back error in `settle` is dropped)
+    def release(self): pass
+
+
+def sequence_gate(scene: "ShaderScene", flag: str, export: "Optional[ExportingHelper]" = None, turbo: bool = True, kind: Optional[type] = None,
+                  taped=lambda module: (module,), chunked: bool = True):
+    """The shared opening of the sequences' `applicable`: SHADERFLOW_<flag> is not "0"; a freewheel run that is not sharded; exactly one
+    module of `kind` and of no subclass of it (which may update() differently from what the device computes); when the loop is `chunked`
+    (FrameSource.chunked) turbo, no progress relay and every program compiled; everything but the modules `taped(module)` names is what
+    ClockLoop takes: no python logic, no other module type. Returns the module (the scene without a `kind`), else None."""
+    import os
+    if os.environ.get(f"SHADERFLOW_{flag}", "1") == "0" or not scene.freewheel or is_sharded():
+        return None
+    found = [scene] if kind is None else [m for m in scene.modules if isinstance(m, kind)]
+    if len(found) != 1 or type(found[0]) is not (kind or type(scene)):
+        return None
+    module = found[0]
+    if chunked and (not turbo or (export is not None and export.relay is not None)):
+        return None
+    if not ClockLoop.applicable(scene, taped=frozenset(id(m) for m in taped(module))):
+        return None
+    if chunked and not all(m.program is not None for m in scene.modules if isinstance(m, ShaderProgram)):
+        return None
+    return module
 
 
 class ClockLoop:
     @staticmethod
-    def applicable(scene: "ShaderScene", taped: frozenset = frozenset()) -> bool:
-        """`taped`: ids of the modules an audio tape computes for the caller (tapesequence.py) — left to its own judgement"""
+    def applicable(scene: "ShaderScene", export: "Optional[ExportingHelper]" = None, turbo: bool = True, taped: frozenset = frozenset()) -> bool:
+        """`taped`: ids of the modules a sequence computes for the caller (tapesequence.py) — left to its own judgement"""
         from shaderflow_amd.scene import ShaderScene
         if type(scene).update is not ShaderModule.update:
             return False
@@ -96,17 +153,16 @@ class ClockLoop:
     def __init__(self, scene: "ShaderScene"):
         self.scene = scene
         self.programs = [m for m in reversed(scene.modules) if isinstance(m, ShaderProgram)]      # the order scene.next renders them in
-        # texture matrices whose samplers move every frame: (names as a C array, the texture) — the names never change
-        self.rolling = []
-        for module in scene.modules:
-            if isinstance(module, ShaderTexture) and module.name and module.temporal > 1:
-                names = [module._sampler_name(t, l).encode() for (t, l, _) in module.boxes]
-                self.rolling.append((module, (C.c_char_p*len(names))(*names), len(names)))
+        # texture matrices whose samplers move every frame, and their sampler names as a C array in the order of `boxes`, by id(texture):
+        # the names never change
+        self.rolling = [m for m in scene.modules if isinstance(m, ShaderTexture) and m.name and m.temporal > 1]
+        self.sampler_names = {id(texture): (C.c_char_p*(texture.temporal*texture.layers))(*[texture._sampler_name(t, l).encode() for (t, l, _) in texture.boxes])
+                              for texture in self.rolling}
 
     def bind_rolled(self, program: ShaderProgram) -> None:
-        for texture, names, count in self.rolling:
-            handles = (N.Handle*count)(*[box.texture.handle if box.texture is not None else N.Handle() for (_, _, box) in texture.boxes])
-            N.check(N.lib().sfx_sampler_bind_many(program.program, names, handles, count))
+        for texture in self.rolling:
+            names = self.sampler_names[id(texture)]
+            N.check(N.lib().sfx_sampler_bind_many(program.program, names, box_handles(texture), len(names)))
 
     # the same loop without python between the frames (csrc/capi.hip sfx_sequence_run) ---------------------------------------------------
 
@@ -130,15 +186,11 @@ class ClockLoop:
             return False
         return all(program.program is not None for program in self.programs)
 
-    def run_native(self, export: "ExportingHelper", times, dts, rdts, total: int, tape: "Optional[FrameTape]" = None, pipe_here: bool = False,
-                   turbo: bool = True, piano=None, video=None) -> None:
-        """Every chunk of frames is one sfx_sequence_run. With a `tape` (tapesequence.py) the frames go in the tape's batches: each batch is
-        built, then drawn in chunks that stay inside it. `pipe_here`: one frame per call, read out by export.pipe (a progress relay, no
-        turbo). With a `piano` (pianosequence.py: `.handle`, `.ticks(first, count)` = the frames' sfx_piano_tick table, `.dynamic_name` = the
-        module's `<name>Dynamic` uniform) the piano's frame goes in front of every frame's passes. With a `video` (videosequence.py: `.handle`,
-        `.names` = the sampler names of a temporal matrix, `.take(first, count)` = how many frames the next call may draw and the slot
-        each of them lands, `.consumed(first, count, slots)` behind the call) a staged source frame goes in front of the frames that land one."""
-        scene, lib = self.scene, N.lib()
+    def run_native(self, export: "ExportingHelper", times, dts, rdts, total: int, source: "Optional[FrameSource]" = None, pipe_here: bool = False, turbo: bool = True) -> None:
+        """Every chunk of frames is one sfx_sequence_run; what a `source` puts in front of the frames' passes it names in the descriptor
+        itself (FrameSource). The frames go in the source's batches, in chunks that stay inside a batch. `pipe_here`: one frame per
+        call, read out by export.pipe (a progress relay, no turbo)."""
+        scene, lib, source = self.scene, N.lib(), source or FrameSource()
         runtime, fps = scene.runtime, scene.fps
         # texture matrices: every program's own (its draws go to row 0) — the same objects `rolling` lists when they are temporal
         textures = [program.texture for program in self.programs]
@@ -156,56 +208,38 @@ class ClockLoop:
         def matrix_tables():
             tables = (N.SequenceMatrix*len(textures))()
             for m, texture in enumerate(textures):
-                boxes = [box for (_, _, box) in texture.boxes]
-                handles = (N.Handle*len(boxes))(*[box.texture.handle if box.texture is not None else N.Handle() for box in boxes])
-                names = None
-                if texture.name and texture.temporal > 1:
-                    names = (C.c_char_p*len(boxes))(*[texture._sampler_name(t, l).encode() for (t, l, _) in texture.boxes])
-                keep.extend([handles, names])
-                tables[m] = N.SequenceMatrix(texture.temporal, texture.layers, handles, names)
+                handles = box_handles(texture)
+                keep.append(handles)
+                tables[m] = N.SequenceMatrix(texture.temporal, texture.layers, handles, self.sampler_names.get(id(texture)))
             return tables
-        planar = None
-        if export._yuv_slots:                                           # (staging exists for a planar sink only)
-            planar = (C.c_void_p*len(export._yuv_slots))(*export._yuv_slots)
+        planar = (C.c_void_p*len(export._yuv_slots))(*export._yuv_slots) if export._yuv_slots else None      # (staging exists for a planar sink only)
         piping = export.fileno is not None and export.ring is not None and not pipe_here
-        # what a run keeps: the passes, the sink, the tape and the piano; every chunk sets the clock, the matrices and where it starts
+        # what a run keeps: the passes, the sink and what the source attaches; every chunk sets the clock, the matrices and where it starts
         sequence = N.Sequence(passes=passes, npasses=len(self.programs), nmatrices=len(textures),
                               ring=export.ring if piping else N.Handle(), fd=export.fileno if piping else -1, planar_slots=planar,
                               yuv_matrix=1 if export.yuv_matrix == "bt709" else 0, width=scene.width, height=scene.height)
-        if tape is not None:
-            sequence.tape = tape.handle
-        if piano is not None:
-            sequence.piano, sequence.piano_dynamic_name = piano.handle, piano.dynamic_name
-        if video is not None:
-            video_names = video.names
-            sequence.video, sequence.video_names = video.handle, video_names
+        source.attach(sequence)
         done = 0
         per_frame = None                                               # seconds per frame of the last native call
         import time as clock
-        for first, size in (shard_batches(0, total, tape.batch) if tape is not None else [(0, total)]):
+        for first, size in source.batches(total):
             if scene.quit:
                 break
-            if tape is not None:
-                tape.build(first, size)                               # on the tape's stream, beside the previous batch's draws
+            source.begin_batch(first, size)
             while done < first + size and not scene.quit:
                 count = 1 if pipe_here else min(self.chunk_frames(per_frame), first + size - done)
                 export._check_encoder()
-                if video is not None:
-                    count, landing = video.take(done, count)         # (may wait for the reader: not part of the frames' measured time)
-                    sequence.video_slots = landing.ctypes.data_as(C.POINTER(C.c_int32))
+                count = source.take(sequence, done, count, first)      # (may wait: not part of the frames' measured time)
                 started = clock.perf_counter()
                 ticks = (N.ClockTick*count)()
                 for i in range(count):
                     time = times[done + i]
                     ticks[i] = N.ClockTick(time, (time/runtime) % 1.0, dts[done + i], round(time*fps))
                 sequence.clock, sequence.nframes, sequence.matrices = ticks, count, matrix_tables()
-                sequence.first_slot, sequence.tape_frame0 = export.frame % max(1, export.slots), done - first
-                if piano is not None:
-                    sequence.piano_ticks = piano.ticks(done, count)
+                sequence.first_slot = export.frame % max(1, export.slots)
                 N.check(lib.sfx_sequence_run(scene.context.handle, C.byref(sequence)))
                 per_frame = (clock.perf_counter() - started)/count
-                if video is not None:
-                    video.consumed(done, count, landing)
+                source.consumed(done, count)
                 for texture in textures:
                     texture.roll(count)                               # the native call rolled its own copy of every matrix it drew into
                 if pipe_here:
@@ -215,10 +249,34 @@ class ClockLoop:
                     export.frame += count
                 done += count
                 keep.clear()
-        # The three loops leave different clocks behind, and tests pin them: here the last frame drawn; TapeSequence.run then takes
-        # rdt = dt of that frame (as FrameTape.export does); PianoSequence.run what scene.next leaves BEHIND the last frame
-        if done:
-            scene.time, scene.dt, scene.rdt = times[done - 1], dts[done - 1], rdts[done - 1]
+
+    def run_source(self, export: "ExportingHelper", source: "FrameSource", turbo: bool = True):
+        """The export of a loop that feeds the native sequence (tapesequence.py, pianosequence.py, videosequence.py). Whatever ends the
+        run — the last frame, scene.quit, an encoder that died, a device error — the source settles the host objects at the last frame
+        that was drawn, and the clock is the one its loop leaves there (`end_clock`)."""
+        scene, total = self.scene, export.total_frames
+        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
+        try:
+            source.prepare(times, dts, total)
+            self.prime(times, dts, rdts)
+            returned = False
+            try:
+                self.run_native(export, times, dts, rdts, total, source, not (source.chunked or self.native_sequence(export, turbo)), turbo)
+                returned = True
+            finally:
+                self.forget_sent()
+                done = min(total, export.frame)
+                try:
+                    source.settle(done)
+                except N.NativeError:
+                    if returned and source.finished(done, total):      # (behind a failed run the device may not answer: the first error is the one to report)
+                        raise
+                if done:
+                    scene.time, scene.dt, scene.rdt = end_clock(source.end, scene.fps, scene.speed, done)
+            return export.finish()
+        finally:
+            scene.context.synchronize()
+            source.release()
 
     def prime(self, times, dts, rdts) -> None:
         """Frame 0's state through the ordinary pipeline walk: every uniform and sampler of every program is on the device"""
@@ -263,4 +321,6 @@ class ClockLoop:
             self.forget_sent()
         if not native:
             scene.time, scene.dt, scene.rdt = times[-1], dts[-1], rdts[-1]      # the clock of the last frame
+        elif export.frame:
+            scene.time, scene.dt, scene.rdt = end_clock(FrameSource.end, scene.fps, scene.speed, min(total, export.frame))
         return export.finish()

@@ -6,7 +6,7 @@ PianoSequence: the frame loop of piano-roll scenes without python logic (no refe
 module, so a scene with a piano always took `ShaderScene.next`.
 
 Here the score lives in device memory (`sfx_piano_create`), and ClockLoop's native sequence draws the frames in chunks
-(`sfx_sequence_run` with the piano named): in front of every frame's passes one launch of `k_piano_frame` (csrc/piano_kernels.hpp) restates that
+(`sfx_sequence_run` with the piano named, by this class as its `FrameSource`): in front of every frame's passes one launch of `k_piano_frame` (csrc/piano_kernels.hpp) restates that
 frame's `update()` — candidates, rolling slots, channel and target velocity per key, one step of the key-press `DynamicNumber` —
 straight into the module's own three textures, on the render stream, so the draws behind it sample the frame's content. The frames
 are the frame loop's byte for byte.
@@ -25,17 +25,14 @@ key-press system whose early-out can fire (`precision != 0`) or that integrates.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from copy import deepcopy
 from typing import TYPE_CHECKING
 
 import numpy as np
 
 from shaderflow_amd import _native as N
-from shaderflow_amd.clockloop import ClockLoop
-from shaderflow_amd.parallel import is_sharded
+from shaderflow_amd.clockloop import ClockLoop, FrameSource, sequence_gate
 from shaderflow_amd.piano.module import MAX_NOTE, MAX_ROLLING, ShaderPiano
-from shaderflow_amd.scheduler import freewheel_clock
 from shaderflow_amd.tape import _coefficients_f32
 
 if TYPE_CHECKING:
@@ -110,25 +107,17 @@ def step_note_range(piano: ShaderPiano, times, dts) -> np.ndarray:
     return out
 
 
-class PianoSequence:
+class PianoSequence(FrameSource):
+    end = "next"                                                       # the clock as scene.next leaves it behind the last frame
+
     @staticmethod
     def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
-        if os.environ.get("SHADERFLOW_PIANO_SEQUENCE", "1") == "0":
+        # no python logic, no audio modules, no module type beside the piano and its textures that ClockLoop does not take
+        piano = sequence_gate(scene, "PIANO_SEQUENCE", export, turbo, ShaderPiano,
+                              taped=lambda piano: (piano, piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture))
+        if piano is None:
             return False
-        if not scene.freewheel or is_sharded() or not turbo or (export is not None and export.relay is not None):
-            return False
-        pianos = [m for m in scene.modules if isinstance(m, ShaderPiano)]
-        if len(pianos) != 1 or type(pianos[0]) is not ShaderPiano:     # (a subclass may update() differently from what the kernel computes)
-            return False
-        piano = pianos[0]
-        textures = (piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture)
-        if any(texture is None for texture in textures):
-            return False
-        # everything else must be what ClockLoop takes: no python logic, no audio modules, no other module type
-        if not ClockLoop.applicable(scene, taped=frozenset(id(m) for m in (piano, *textures))):
-            return False
-        from shaderflow_amd.shader import ShaderProgram
-        if not all(m.program is not None for m in scene.modules if isinstance(m, ShaderProgram)):
+        if any(texture is None for texture in (piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture)):
             return False
         if (piano.keys_texture.size, piano.channel_texture.size, piano.roll_texture.size) != ((MAX_NOTE, 1), (MAX_NOTE, 1), (MAX_ROLLING, MAX_NOTE)):
             return False
@@ -188,6 +177,7 @@ class PianoSequence:
         if self.handle is not None and self.handle.value:
             N.lib().sfx_piano_destroy(self.handle)
         self.handle = None
+        self._ticks = None
 
     def step(self, time: float, dt: float) -> None:
         """One frame on its own (`sfx_piano_step`): the three textures and the key-press state for scene.time = `time`, scene.dt = `dt`.
@@ -209,63 +199,48 @@ class PianoSequence:
         if self._aliased:
             keys.previous = keys.target                                # reference dynamics.py:229 — one array under two names
         for texture in (piano.keys_texture, piano.channel_texture, piano.roll_texture):
-            box = texture.get_box()
-            box.data, box.empty = box.texture.read().tobytes(), False
+            texture.refresh_host_copy()
 
-    def ticks(self, first: int, count: int):
-        return self._ticks[first:first + count].ctypes.data_as(C.POINTER(N.PianoTick))
-
-    # the export ---------------------------------------------------------------------------------------------------------------------
+    # the export: the native sequence with the piano's frame in front of every frame's passes ---------------------------------------------
 
     def run(self, export: "ExportingHelper", turbo: bool):
-        scene, clock, piano = self.scene, self.clock, self.piano
-        keys, note_range = piano.key_press_dynamics, piano.note_range_dynamics
-        total = export.total_frames
-        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
-        try:
-            clock.prime(times, dts, rdts)
-            self.upload()
-            # the per-frame table: the clock in float64, the key-press coefficients, iPianoDynamic of every frame
-            before = {name: deepcopy(getattr(note_range, name)) for name in ("value", "target", "previous", "derivative", "acceleration", "frequency")}
-            range_aliased = note_range.previous is note_range.target
-            dynamic = step_note_range(piano, times, dts)
-            coeff = _coefficients_f32(keys, dts)
-            moved = np.asarray([bool(abs(dt)) for dt in dts], bool)         # frames whose step runs (reference dynamics.py:210-211)
-            aliased_after = np.logical_or(keys.previous is keys.target, np.cumsum(moved) > 0)
-            ticks = np.zeros(max(1, total), TICK)
-            ticks["time"][:total], ticks["coeff"][:total], ticks["dynamic"][:total] = times, coeff, dynamic
-            ticks["previous_is_target"][:total] = np.concatenate([[keys.previous is keys.target], aliased_after[:-1]])
-            self._ticks = ticks
-            finished = False
-            try:
-                clock.run_native(export, times, dts, rdts, total, piano=self)
-                finished = True
-            finally:
-                clock.forget_sent()
-                # Whatever ended the run — the last frame, scene.quit, an encoder that died, a device error — the host objects are left at
-                # the last frame that was drawn: the note range was stepped through the whole export up front, so it goes back and is
-                # stepped again as far as the frames went; the key-press state and the textures' host copies are read from the device (which a
-                # native call that failed half-way may have left up to a chunk ahead).
-                self.frames = done = min(total, export.frame)
-                if done < total:
-                    for name, value in before.items():
-                        setattr(note_range, name, value)
-                    if range_aliased:
-                        note_range.previous = note_range.target
-                    step_note_range(piano, times[:done], dts[:done])
-                if done:
-                    self._aliased = bool(aliased_after[done - 1])
-                    try:
-                        self.read_state()
-                    except N.NativeError:
-                        if finished:                                   # (behind a failed run the device may not answer: the first error is the one to report)
-                            raise
-                    # the clock as scene.next leaves it behind the last frame (it integrates time AFTER the frame, reference scene.py:475-479):
-                    # what a frame more would have seen
-                    after = freewheel_clock(scene.fps, done + 1, scene.speed)
-                    scene.time, scene.dt, scene.rdt = after[0][done], after[1][done], after[2][done]
-            return export.finish()
-        finally:
-            scene.context.synchronize()
-            self.release()
-            self._ticks = None
+        return self.clock.run_source(export, self, turbo)
+
+    def prepare(self, times, dts, total: int) -> None:
+        """The score on the device and the per-frame table: the clock in float64, the key-press coefficients, iPianoDynamic of every frame"""
+        piano, keys, note_range = self.piano, self.piano.key_press_dynamics, self.piano.note_range_dynamics
+        self.upload()
+        self._before = {name: deepcopy(getattr(note_range, name)) for name in ("value", "target", "previous", "derivative", "acceleration", "frequency")}
+        self._range_aliased = note_range.previous is note_range.target
+        self._times, self._dts = times, dts
+        dynamic = step_note_range(piano, times, dts)
+        coeff = _coefficients_f32(keys, dts)
+        moved = np.asarray([bool(abs(dt)) for dt in dts], bool)         # frames whose step runs (reference dynamics.py:210-211)
+        self._aliased_after = np.logical_or(keys.previous is keys.target, np.cumsum(moved) > 0)
+        ticks = np.zeros(max(1, total), TICK)
+        ticks["time"][:total], ticks["coeff"][:total], ticks["dynamic"][:total] = times, coeff, dynamic
+        ticks["previous_is_target"][:total] = np.concatenate([[keys.previous is keys.target], self._aliased_after[:-1]])
+        self._ticks = ticks
+
+    def attach(self, sequence) -> None:
+        sequence.piano, sequence.piano_dynamic_name = self.handle, self.dynamic_name
+
+    def take(self, sequence, first: int, count: int, batch_first: int) -> int:
+        sequence.piano_ticks = self._ticks[first:first + count].ctypes.data_as(C.POINTER(N.PianoTick))
+        return count
+
+    def settle(self, done: int) -> None:
+        """The note range was stepped through the whole export up front, so it goes back and is stepped again as far as the frames went;
+        the key-press state and the textures' host copies are read from the device (which a native call that failed half-way may have
+        left up to a chunk ahead)"""
+        note_range, times, dts = self.piano.note_range_dynamics, self._times, self._dts
+        self.frames = done
+        if done < len(times):
+            for name, value in self._before.items():
+                setattr(note_range, name, value)
+            if self._range_aliased:
+                note_range.previous = note_range.target
+            step_note_range(self.piano, times[:done], dts[:done])
+        if done:
+            self._aliased = bool(self._aliased_after[done - 1])
+            self.read_state()

@@ -383,31 +383,23 @@ class ShaderScene(ShaderModule):
                                         frameskip=frameskip, precise=True)
         if self.exporting and (is_sharded() or shard is not None):
             return self._sharded_frame_loop(export, turbo, *(shard or rank_world()))
-        # nothing but the clock moves between frames (layered / temporal scenes without python logic): the lean loop, same frames
+        # The loops that spare scene.next, in the order they are asked; the one that ran is kept under its attribute (tests, tools):
+        # nothing but the clock moves between frames (clockloop.py: the lean loop, same frames); a ShaderVideo without python logic, its
+        # frames staged ahead (videosequence.py); a ShaderPiano without python logic, its score on the device (pianosequence.py); audio-
+        # reactive layered / temporal / multi-program scenes on the device tape (tapesequence.py); audio scenes with python logic of
+        # their own, the user's update() frame by frame (tapeloop.py)
         from shaderflow_amd.clockloop import ClockLoop
-        if self.freewheel and batch is None and self.clock_loop and ClockLoop.applicable(self):
-            return ClockLoop(self).run(export, turbo)
-        # a ShaderVideo scene without python logic: source frames staged ahead in pinned memory, put into the texture in front of the frame
-        # that first shows them (videosequence.py)
-        from shaderflow_amd.videosequence import VideoSequence
-        if batch is None and VideoSequence.applicable(self, export, turbo):
-            self.video_sequence = VideoSequence(self)
-            return self.video_sequence.run(export, turbo)
-        # a ShaderPiano scene without python logic: the score on the device, its textures made in front of every frame's draws (pianosequence.py)
         from shaderflow_amd.pianosequence import PianoSequence
-        if batch is None and PianoSequence.applicable(self, export, turbo):
-            self.piano_sequence = PianoSequence(self)
-            return self.piano_sequence.run(export, turbo)
-        # audio-reactive layered / temporal / multi-program scenes without python logic: ClockLoop's native sequence on the tape (tapesequence.py)
-        from shaderflow_amd.tapesequence import TapeSequence
-        if batch is None and TapeSequence.applicable(self):
-            self.tape_sequence = TapeSequence(self)
-            return self.tape_sequence.run(export, turbo)
-        # audio scenes with python logic of their own: the audio from the device tape, the user's update() frame by frame (tapeloop.py)
         from shaderflow_amd.tapeloop import TapeLoop
-        if batch is None and TapeLoop.applicable(self):
-            self.tape_loop = TapeLoop(self)
-            return self.tape_loop.run(export, turbo)
+        from shaderflow_amd.tapesequence import TapeSequence
+        from shaderflow_amd.videosequence import VideoSequence
+        loops = ((None, ClockLoop), ("video_sequence", VideoSequence), ("piano_sequence", PianoSequence), ("tape_sequence", TapeSequence), ("tape_loop", TapeLoop))
+        for attribute, loop in loops[0 if self.freewheel and self.clock_loop else 1:]:
+            if batch is None and loop.applicable(self, export, turbo):
+                runner = loop(self)
+                if attribute:
+                    setattr(self, attribute, runner)
+                return runner.run(export, turbo)
         while (task := self.scheduler.next()):
             if (task is not self.vsync):
                 continue

@@ -68,7 +68,7 @@ def _dynamics_state(system) -> tuple:
 
 class TapeLoop:
     @staticmethod
-    def applicable(scene: "ShaderScene") -> bool:
+    def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
         from shaderflow_amd.scene import ShaderScene
         if os.environ.get("SHADERFLOW_TAPE_LOOP", "1") == "0":
             return False

@@ -9,7 +9,7 @@ all three into `ShaderScene.next`, which paid a device STFT, a host round trip, 
 writes of the spectrogram and the waveform, and the pipeline walk, every frame.
 
 Here the device builds the audio state of a batch of frames exactly as an export's `FrameTape.build` does, and ClockLoop's native
-sequence draws the batch in chunks (`sfx_sequence_run` with the tape named): the same passes, clock ticks, rolled sampler tables, resolve
+sequence draws the batch in chunks (`sfx_sequence_run` with the tape named, by this class as its `FrameSource`): the same passes, clock ticks, rolled sampler tables, resolve
 and read-out as without a tape, except that a pass whose program reads audio (samples iSpectrogram / iWaveform, or reads iAudioVolume,
 iAudioVolumeIntegral, iAudioSTD, iSpectrogramOffset) takes frame k's audio state from tape frame k — a layered pass draws every layer
 into row 0 of its matrix, a fused one renders into iFinal through `sfx_render_tape`. Passes that read no audio are drawn as by
@@ -22,7 +22,6 @@ or spectrograms, and several frames per launch.
 """
 from __future__ import annotations
 
-import os
 from typing import TYPE_CHECKING
 
 import numpy as np
@@ -31,9 +30,8 @@ from shaderflow_amd import _native as N
 from shaderflow_amd.audio.module import ShaderAudio
 from shaderflow_amd.audio.spectrogram import ShaderSpectrogram
 from shaderflow_amd.audio.waveform import ShaderWaveform
-from shaderflow_amd.clockloop import ClockLoop
-from shaderflow_amd.parallel import is_sharded
-from shaderflow_amd.scheduler import freewheel_clock
+from shaderflow_amd.clockloop import ClockLoop, FrameSource, sequence_gate
+from shaderflow_amd.parallel import shard_batches
 from shaderflow_amd.tape import FrameTape
 from shaderflow_amd.tapeloop import TapeLoop
 
@@ -41,29 +39,22 @@ if TYPE_CHECKING:
     from shaderflow_amd.exporting import ExportingHelper
     from shaderflow_amd.scene import ShaderScene
 
-_AUDIO = (ShaderAudio, ShaderSpectrogram, ShaderWaveform)
 
+class TapeSequence(FrameSource):
+    end = "last_dt"                                                    # the clock of the last frame, as FrameTape.export leaves it
+    chunked = False                                                    # (a relay or SHADERFLOW_CLOCK_SEQUENCE=0: frame by frame, read out by export.pipe)
 
-class TapeSequence:
     @staticmethod
-    def applicable(scene: "ShaderScene") -> bool:
-        if os.environ.get("SHADERFLOW_TAPE_SEQUENCE", "1") == "0":
-            return False
-        if not scene.freewheel or is_sharded():
-            return False
+    def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
         # the audio modules of exact stock types (a subclass may update() differently from what the tape computes), and the two loudness
         # systems they own: the tape computes them; everything else must be what ClockLoop takes
         audios = [m for m in scene.modules if type(m) is ShaderAudio]
         spectrograms = [m for m in scene.modules if type(m) is ShaderSpectrogram]
         waveforms = [m for m in scene.modules if type(m) is ShaderWaveform]
-        if not audios:
+        taped = (*audios, *spectrograms, *waveforms, *(s for a in audios for s in (a.volume, a.std)))
+        if not audios or sequence_gate(scene, "TAPE_SEQUENCE", taped=lambda _: taped, chunked=False) is None:
             return False
-        taped = frozenset(id(m) for m in (*audios, *spectrograms, *waveforms, *(s for a in audios for s in (a.volume, a.std))))
-        if not ClockLoop.applicable(scene, taped=taped):
-            return False
-        if not FrameTape.audio_fits(audios, spectrograms, waveforms):
-            return False
-        return TapeSequence.camera_at_identity(scene)
+        return FrameTape.audio_fits(audios, spectrograms, waveforms) and TapeSequence.camera_at_identity(scene)
 
     @staticmethod
     def camera_at_identity(scene: "ShaderScene") -> bool:
@@ -92,25 +83,33 @@ class TapeSequence:
         self.frames = 0                                                # frames drawn from the tape (tests, measurements)
 
     def run(self, export: "ExportingHelper", turbo: bool):
-        scene, tape, clock = self.scene, self.tape, self.clock
-        total = export.total_frames
-        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
+        return self.clock.run_source(export, self, turbo)
+
+    # the frame source: the frames go in the tape's batches, each built (on the tape's stream, beside the previous batch's draws) and then
+    # drawn in chunks. Behind the run the audio modules' host state and textures are as the export found them (FrameTape.export)
+
+    def prepare(self, times, dts, total: int) -> None:
+        tape = self.tape
         tape.prepare(total)
-        try:
-            if tape.spectrogram is not None and not tape.private_spectrogram:
-                tape.spectrogram.configure_texture()                  # what its first update() would do (FrameTape.bind_static_uniforms)
-            clock.prime(times, dts, rdts)
-            N.check(N.lib().sfx_tape_reset(tape.handle))
-            native = clock.native_sequence(export, turbo)
-            try:
-                clock.run_native(export, times, dts, rdts, total, tape=tape, pipe_here=not native, turbo=turbo)
-            finally:
-                clock.forget_sent()
-            self.frames = export.frame
-            # the clock of the last frame; the audio modules' host state and textures are as the export found them (FrameTape.export)
-            last = max(0, min(total, export.frame) - 1)
-            scene.time, scene.dt, scene.rdt = times[last], dts[last], dts[last]
-            return export.finish()
-        finally:
-            scene.context.synchronize()
-            tape.release()
+        if tape.spectrogram is not None and not tape.private_spectrogram:
+            tape.spectrogram.configure_texture()                      # what its first update() would do (FrameTape.bind_static_uniforms)
+        N.check(N.lib().sfx_tape_reset(tape.handle))
+
+    def batches(self, total: int):
+        return shard_batches(0, total, self.tape.batch)
+
+    def begin_batch(self, first: int, size: int) -> None:
+        self.tape.build(first, size)
+
+    def attach(self, sequence) -> None:
+        sequence.tape = self.tape.handle
+
+    def take(self, sequence, first: int, count: int, batch_first: int) -> int:
+        sequence.tape_frame0 = first - batch_first
+        return count
+
+    def settle(self, done: int) -> None:
+        self.frames = done
+
+    def release(self) -> None:
+        self.tape.release()

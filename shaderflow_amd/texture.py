@@ -228,6 +228,11 @@ class ShaderTexture(ShaderModule):
         box.empty = False
         return self
 
+    def refresh_host_copy(self, temporal: int = 0, layer: int = -1) -> None:
+        """Behind a kernel that wrote the whole box on the device: the host copy of the last full write, as `write` keeps it"""
+        box = self.get_box(temporal, layer)
+        box.data, box.empty = box.texture.read().tobytes(), False
+
     def clear(self, temporal: int = 0, layer: int = -1):
         return self.write(self.zeros, temporal=temporal, layer=layer)
 

@@ -286,8 +286,7 @@ class ShaderVideo(ShaderModule):
         self._stage.step(0)
         self.texture.roll()
         self._stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
-        box = self.texture.get_box()
-        box.data, box.empty = box.texture.read().tobytes(), False        # the host copy of the last full write, as texture.write keeps it
+        self.texture.refresh_host_copy()
 
     def destroy(self) -> None:
         if self._stage is not None:

@@ -7,7 +7,8 @@ with a video always took `ShaderScene.next`, frame by frame, nothing overlapping
 
 Here source frames are staged ahead of the draws: a reader thread fills pinned slots in source order (`file.readinto` / a memory-mapped
 copy straight into the slot, both without the GIL) and submits each one's asynchronous host → device copy on the stage's own copy
-stream (`sfx_video_submit`). ClockLoop's native sequence draws the frames in chunks (`sfx_sequence_run` with the video named): in front of
+stream (`sfx_video_submit`). ClockLoop's native sequence draws the frames in chunks (`sfx_sequence_run` with the video named, by this class
+as its `FrameSource`): in front of
 the first pass of every scene frame a source frame lands on, the render stream waits for that slot's copy, the video's texture matrix
 rolls and one launch of `k_video_frame` (csrc/video_kernels.hpp) writes the frame into the front box — rows flipped, and converted from
 4:2:0 when the source is planar. The frames are the frame loop's byte for byte.
@@ -30,17 +31,13 @@ from __future__ import annotations
 
 import ctypes as C
 import itertools
-import os
 import threading
 from typing import TYPE_CHECKING, Optional
 
 import numpy as np
 
-from shaderflow_amd import _native as N
-from shaderflow_amd.clockloop import ClockLoop
+from shaderflow_amd.clockloop import ClockLoop, FrameSource, sequence_gate
 from shaderflow_amd.module import logger
-from shaderflow_amd.parallel import is_sharded
-from shaderflow_amd.scheduler import freewheel_clock
 from shaderflow_amd.video import ShaderVideo, VideoStage
 
 if TYPE_CHECKING:
@@ -73,27 +70,19 @@ def landing_frames(times, fps: float, first_read: int = 0, available: Optional[i
     return out
 
 
-class VideoSequence:
+class VideoSequence(FrameSource):
+    end = "next"                                                       # the clock as scene.next leaves it behind the last frame
+
     @staticmethod
     def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
-        if os.environ.get("SHADERFLOW_VIDEO_SEQUENCE", "1") == "0":
+        # no python logic, no audio modules, no piano, no module type beside the video and its texture that ClockLoop does not take
+        video = sequence_gate(scene, "VIDEO_SEQUENCE", export, turbo, ShaderVideo, taped=lambda video: (video, video.texture))
+        if video is None:
             return False
-        if not scene.freewheel or is_sharded() or not turbo or (export is not None and export.relay is not None):
-            return False
-        videos = [m for m in scene.modules if isinstance(m, ShaderVideo)]
-        if len(videos) != 1 or type(videos[0]) is not ShaderVideo:     # (a subclass may update() differently from what the sequence schedules)
-            return False
-        video = videos[0]
         texture = video.texture
         if texture is None or texture.layers != 1 or texture.components != 3 or texture.dtype != np.uint8:
             return False
-        if texture.track or texture.size != (video.width, video.height) or any(box.texture is None for (_, _, box) in texture.boxes):
-            return False
-        # everything else must be what ClockLoop takes: no python logic, no audio modules, no piano, no other module type
-        if not ClockLoop.applicable(scene, taped=frozenset(id(m) for m in (video, texture))):
-            return False
-        from shaderflow_amd.shader import ShaderProgram
-        return all(m.program is not None for m in scene.modules if isinstance(m, ShaderProgram))
+        return not texture.track and texture.size == (video.width, video.height) and all(box.texture is not None for (_, _, box) in texture.boxes)
 
     def __init__(self, scene: "ShaderScene"):
         self.scene = scene
@@ -105,22 +94,14 @@ class VideoSequence:
         self.lock = threading.Condition()
         self.thread: Optional[threading.Thread] = None
 
-    # what run_native asks of its `video` -----------------------------------------------------------------------------------------------
+    # the frame source: a staged source frame goes in front of the frames that land one ------------------------------------------------
 
-    @property
-    def handle(self):
-        return self.stage.handle
+    def attach(self, sequence) -> None:
+        # the sampler names of the matrix' rows, depth 0 first, when it is temporal (else None: the host's bindings stay)
+        sequence.video, sequence.video_names = self.stage.handle, self.clock.sampler_names.get(id(self.video.texture))
 
-    @property
-    def names(self):
-        """The sampler names of the matrix' rows, depth 0 first, when it is temporal (else None: the host's bindings stay)"""
-        texture = self.video.texture
-        if not texture.name or texture.temporal < 2:
-            return None
-        return (C.c_char_p*texture.temporal)(*[texture._sampler_name(t, 0).encode() for t in range(texture.temporal)])
-
-    def take(self, first: int, count: int):
-        """(frames, slot table) of the native call that starts at scene frame `first`: up to `count` frames, shortened so that its landings
+    def take(self, sequence, first: int, count: int, batch_first: int) -> int:
+        """The slot table of the native call that starts at scene frame `first`: up to `count` frames, shortened so that its landings
         are staged already and fill at most half the slots. Waits for the reader only when the call's first frame needs a frame that is
         not there yet; a reader that failed raises its exception here, once the frames staged before it failed are drawn."""
         slots = np.full(count, -1, np.int32)
@@ -129,17 +110,20 @@ class VideoSequence:
             source = int(self.want[first + i])
             if source < 0:
                 continue
-            if landings >= self.per_chunk:
-                return i, slots[:i]
-            with self.lock:
-                slot = self.await_frame(source, first + i, wait=(i == 0))
+            slot = -1                                                 # (half the slots are taken: as if not staged yet)
+            if landings < self.per_chunk:
+                with self.lock:
+                    slot = self.await_frame(source, first + i, wait=(i == 0))
             if slot is None:                                          # the source ended in front of this frame: it shows what was there
                 continue
             if slot < 0:                                              # not staged yet: the call ends in front of this frame
-                return i, slots[:i]
+                count = i
+                break
             slots[i] = slot
             landings += 1
-        return count, slots
+        self.landing = slots[:count]
+        sequence.video_slots = self.landing.ctypes.data_as(C.POINTER(C.c_int32))
+        return count
 
     def await_frame(self, source: int, frame: int, wait: bool):
         """The slot source frame `source` is staged in; None when the source ended before it; -1 when it is not there yet and the caller
@@ -166,8 +150,9 @@ class VideoSequence:
         if self.exhausted_at is None:
             self.exhausted_at = frame
 
-    def consumed(self, first: int, count: int, slots: np.ndarray) -> None:
+    def consumed(self, first: int, count: int) -> None:
         """The native call has queued these landings: their slots go back to the reader (it waits for each kernel before it refills)"""
+        slots = self.landing
         used = [int(slot) for slot in slots if slot >= 0]
         with self.lock:
             for i in range(count):
@@ -182,8 +167,7 @@ class VideoSequence:
 
     def read_frames(self, source, first: int, needed: int) -> None:
         """The reader thread: source frames first, first + 1, … into free slots, each submitted as soon as it is whole"""
-        stage, video = self.stage, self.video
-        nbytes = video.width*video.height*3//(2 if video.format == "i420" else 1)
+        stage, video, nbytes = self.stage, self.video, self.frame_bytes
         readinto = getattr(source, "readinto", None) if video.format == "i420" else None
         try:
             for index in range(first, first + needed):
@@ -228,67 +212,52 @@ class VideoSequence:
 
     # the export ------------------------------------------------------------------------------------------------------------------------
 
-    def read_state(self, landed: int) -> None:
-        """The host copies of the boxes the run wrote into, as `texture.write` keeps them: read back from the device"""
-        texture = self.video.texture
-        for depth in range(min(landed, texture.temporal)):
-            box = texture.get_box(depth)
-            box.data, box.empty = box.texture.read().tobytes(), False
-
     def run(self, export: "ExportingHelper", turbo: bool):
-        scene, clock, video = self.scene, self.clock, self.video
-        total = export.total_frames
-        times, dts, rdts = freewheel_clock(scene.fps, total, scene.speed)
-        first_read, was_exhausted = video._read, video._exhausted
+        return self.clock.run_source(export, self, turbo)
+
+    def prepare(self, times, dts, total: int) -> None:
+        """The stage and the reader thread"""
+        video = self.video
+        self.first_read, self.was_exhausted, self.source = video._read, video._exhausted, video._reader
         # every landing of the export, were the source endless; where it ends is learnt from the reader
-        self.want = landing_frames(times, video.fps, first_read) if not was_exhausted else np.full(total, -1, np.int64)
-        needed = int((self.want >= 0).sum())
-        frame_bytes = video.width*video.height*3//(2 if video.format == "i420" else 1)
-        slots = slot_count(frame_bytes)
+        self.want = landing_frames(times, video.fps, self.first_read) if not self.was_exhausted else np.full(total, -1, np.int64)
+        self.frame_bytes = video.width*video.height*3//(2 if video.format == "i420" else 1)
+        slots = slot_count(self.frame_bytes)
         self.per_chunk = slots//2
         self.free, self.staged, self.views, self.kept = list(range(slots)), {}, {}, {}
         self.total, self.error, self.stop, self.exhausted_at = None, None, False, None
         self.landed = 0
-        source = video._reader
-        try:
-            clock.prime(times, dts, rdts)
-            self.stage = VideoStage(video, slots)
-            self.thread = threading.Thread(target=self.read_frames, args=(source, first_read, needed), name="shaderflow-video-reader", daemon=True)
-            self.thread.start()
-            try:
-                clock.run_native(export, times, dts, rdts, total, video=self)
-            finally:
-                clock.forget_sent()
-                with self.lock:
-                    self.stop = True
-                    self.lock.notify_all()
-                self.thread.join()
-                # Whatever ended the run — the last frame, scene.quit, an encoder that died, a reader that raised — the host objects are
-                # left at the last frame that was drawn
-                self.frames = done = min(total, export.frame)
-                video._read = first_read + self.landed
-                video._exhausted = was_exhausted or (self.exhausted_at is not None and self.exhausted_at < done)
-                if video._exhausted and not was_exhausted:
-                    logger.warning(f"{video.name}: source ended after {video._read} frames, holding the last one")
-                # frames taken from the source but not drawn go back in front of it, in order, for a later update()
-                ahead = {index: self.views[slot].copy() for index, slot in self.staged.items()}
-                ahead.update(self.kept)
-                if ahead:
-                    shape = (-1,) if video.format == "i420" else (video.height, video.width, 3)
-                    video._reader = itertools.chain([ahead[index].reshape(shape) for index in sorted(ahead)], source)
-                if done:
-                    try:
-                        self.read_state(self.landed)
-                    except N.NativeError:
-                        if self.error is None and not scene.quit and done == total:
-                            raise
-                    # the clock as scene.next leaves it behind the last frame (it integrates time AFTER the frame): what a frame more would have seen
-                    after = freewheel_clock(scene.fps, done + 1, scene.speed)
-                    scene.time, scene.dt, scene.rdt = after[0][done], after[1][done], after[2][done]
-            return export.finish()
-        finally:
-            scene.context.synchronize()
-            if self.stage is not None:
-                self.stage.release()
-                self.stage = None
-            self.views = {}
+        self.stage = VideoStage(video, slots)
+        self.thread = threading.Thread(target=self.read_frames, args=(self.source, self.first_read, int((self.want >= 0).sum())),
+                                       name="shaderflow-video-reader", daemon=True)
+        self.thread.start()
+
+    def settle(self, done: int) -> None:
+        video = self.video
+        with self.lock:
+            self.stop = True
+            self.lock.notify_all()
+        self.thread.join()
+        self.frames = done
+        video._read = self.first_read + self.landed
+        video._exhausted = self.was_exhausted or (self.exhausted_at is not None and self.exhausted_at < done)
+        if video._exhausted and not self.was_exhausted:
+            logger.warning(f"{video.name}: source ended after {video._read} frames, holding the last one")
+        # frames taken from the source but not drawn go back in front of it, in order, for a later update()
+        ahead = {index: self.views[slot].copy() for index, slot in self.staged.items()}
+        ahead.update(self.kept)
+        if ahead:
+            shape = (-1,) if video.format == "i420" else (video.height, video.width, 3)
+            video._reader = itertools.chain([ahead[index].reshape(shape) for index in sorted(ahead)], self.source)
+        # the host copies of the boxes the run wrote into, as `texture.write` keeps them: read back from the device
+        for depth in range(min(self.landed, video.texture.temporal) if done else 0):
+            video.texture.refresh_host_copy(depth)
+
+    def finished(self, done: int, total: int) -> bool:
+        return self.error is None and not self.scene.quit and done == total
+
+    def release(self) -> None:
+        if self.stage is not None:
+            self.stage.release()
+            self.stage = None
+        self.views = {}

@@ -215,6 +215,23 @@ def test_written_out_freewheel_clock_equals_the_scheduler_task():
         assert all(list(g) == list(w) for g, w in zip(got, want)), (fps, frames, speed)
 
 
+def test_end_clock_is_the_clock_each_loop_leaves_behind_its_last_frame():
+    """clockloop.end_clock, the clock behind a run of `done` frames, against the scheduler task's own: "last" is frame done - 1's triple
+    (ClockLoop), "last_dt" that triple with rdt = dt (TapeSequence, as FrameTape.export), "next" frame `done`'s triple of a clock of
+    done + 1 frames (PianoSequence, VideoSequence: what scene.next leaves behind the last frame)"""
+    from shaderflow_amd.clockloop import end_clock
+    from shaderflow_amd.scheduler import freewheel_clock_by_task
+    for fps, speed in ((60.0, 1.0), (59.94, 0.5)):
+        for done in (1, 2, 3, 30, 241, 1000):
+            times, dts, rdts = freewheel_clock_by_task(fps, done + 1, speed)
+            assert (times[:done], dts[:done], rdts[:done]) == freewheel_clock_by_task(fps, done, speed)
+            assert end_clock("last", fps, speed, done) == (times[done - 1], dts[done - 1], rdts[done - 1])
+            assert end_clock("last_dt", fps, speed, done) == (times[done - 1], dts[done - 1], dts[done - 1])
+            assert end_clock("next", fps, speed, done) == (times[done], dts[done], rdts[done])
+            if speed != 1.0 and done > 1:
+                assert end_clock("last", fps, speed, done) != end_clock("last_dt", fps, speed, done)
+
+
 def test_module_skipping_keeps_the_order_in_which_modules_override_each_other():
     """shader.py use_scene_pipeline: a module whose pipeline_token() is unchanged is not walked again — unless a module walked earlier
     in the frame yields one of its names (then the later module has to say its value again: last writer wins, as in a full walk)"""
