@@ -47,7 +47,10 @@ def main() -> None:
     audio = None
     if issubclass(cls, scenes._AudioScene):
         audio = args.audio if args.audio else (synth.sweep_clip(args.time, 44100), 44100)
-    if issubclass(cls, scenes.PianoRoll):
+    if issubclass(cls, scenes.PianoAudio):
+        # the built-in score and, without --audio, its own sound (synth.score_clip)
+        scene = scenes.make(cls, audio=args.audio, score=scenes.demo_score(args.time), device=local_rank)
+    elif issubclass(cls, scenes.PianoRoll):
         # the built-in score, through a MIDI file as a user's would come; the scene reads it while it is built
         import tempfile
         from shaderflow_amd.piano.midi import write_midi

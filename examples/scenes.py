@@ -369,6 +369,90 @@ class PianoRoll(ShaderScene):
         self.shader.fragment = self.FRAGMENT
 
 
+class PianoAudio(_AudioScene):
+    """A piano roll with its sound track (not one of the reference's): PianoRoll's keyboard and falling notes, and under the keyboard
+    a spectrum strip — one bin of iSpectrogram per key, drawn in the key's column — while the keys glow with iAudioVolume. `score` as
+    for PianoRoll; `audio` as for the audio scenes, and without one the score's own sound (synth.score_clip). No python logic between
+    frames: the piano and the audio tape feed one native sequence (shaderflow_amd/pianotape.py)."""
+    score = None
+    SPECTRUM_LOW, SPECTRUM_HIGH = 21, 108                           # A0 … C8: one spectrogram bin per key of an 88-key piano
+    FRAGMENT = """
+        #define SPECTRUM_LOW 21.0
+        #define SPECTRUM_KEYS 88.0
+        bool blackKey(int note) {
+            int k = note % 12;
+            return k == 1 || k == 3 || k == 6 || k == 8 || k == 10;
+        }
+        vec3 channelColour(float channel) {
+            return 0.55 + 0.45*cos(TAU*(0.19*channel + vec3(0.0, 0.33, 0.67)));
+        }
+        void main() {
+            // the keys on screen: the note range the module follows, and a margin on both sides
+            float low = iPianoDynamic.x - iPianoExtra;
+            float high = iPianoDynamic.y + iPianoExtra + 1.0;
+            float key = mix(low, high, astuv.x);
+            int note = int(floor(key));
+            float across = fract(key);
+            vec3 colour = vec3(0.05, 0.05, 0.08);
+            if (note < 0 || note > 127) {
+                fragColor = vec4(colour, 1.0);
+                return;
+            }
+            bool black = blackKey(note);
+            float gap = smoothstep(0.0, 0.08, across)*smoothstep(0.0, 0.08, 1.0 - across);
+            float strip = 0.25*iPianoHeight;
+            if (astuv.y < strip) {
+                // the spectrum strip: the level of the key's own bin, both channels, rising from the bottom edge
+                vec2 s = texture(iSpectrogram, vec2(0.5, (key - SPECTRUM_LOW)/SPECTRUM_KEYS)).xy;
+                float level = clamp(sqrt(max(0.5*(s.x + s.y), 0.0))/30.0, 0.0, 1.0);
+                float up = astuv.y/strip;
+                vec3 bar = hsv2rgb(vec3(0.66 - 0.6*level, 0.8, 1.0))*mix(0.5, 1.0, gap);
+                colour = mix(colour, bar, step(up, level));
+            } else if (astuv.y < iPianoHeight) {
+                // the keyboard: a black key covers the upper part of its column; a key that is down glows with the loudness of the moment
+                float up = (astuv.y - strip)/(iPianoHeight - strip);
+                float pressed = clamp(texelFetch(iPianoKeys, ivec2(note, 0), 0).x/100.0, 0.0, 1.0);
+                float channel = texelFetch(iPianoChan, ivec2(note, 0), 0).x;
+                bool dark = black && up > 1.0 - iPianoBlackRatio;
+                vec3 rest = dark ? vec3(0.07) : vec3(0.9);
+                vec3 lit = channel < 0.0 ? rest : channelColour(channel);
+                colour = mix(rest, lit, pressed)*mix(0.55, 1.0, gap)*(0.8 + 0.2*up);
+                colour += 0.6*lit*pressed*clamp(iAudioVolume, 0.0, 1.0)*up;
+            } else {
+                // the roll: height above the keyboard is time ahead of now
+                float when = iTime + iPianoRollTime*(astuv.y - iPianoHeight)/(1.0 - iPianoHeight);
+                colour += black ? vec3(0.0) : vec3(0.025);
+                for (int slot = 0; slot < iPianoLimit; slot++) {
+                    vec4 entry = texelFetch(iPianoRoll, ivec2(slot, note), 0);
+                    if (entry.y == 0.0 && entry.w == 0.0)
+                        break;
+                    if (when >= entry.x && when <= entry.y)
+                        colour = channelColour(entry.z)*(0.45 + 0.55*entry.w/127.0)*mix(0.3, 1.0, gap);
+                }
+            }
+            fragColor = vec4(colour, 1.0);
+        }
+    """
+
+    def build(self):
+        from shaderflow_amd.audio.spectrogram import ShaderSpectrogram
+        from shaderflow_amd.piano import ShaderPiano
+        super().build()
+        self.piano = ShaderPiano(scene=self)
+        score = demo_score() if self.score is None else self.score
+        if isinstance(score, (str, Path)):
+            self.piano.load_midi(score)
+        else:
+            for note in score:
+                self.piano.add_note(note)
+        if self.audio_source is None:
+            self.audio_source = (synth.score_clip(list(self.piano.notes), self.piano.duration + 1.0), 44100)
+        self._load_audio()
+        self.spectrogram = ShaderSpectrogram(scene=self, length=0, audio=self.audio, smooth=False)
+        self.spectrogram.from_notes(start=self.SPECTRUM_LOW, end=self.SPECTRUM_HIGH, piano=True)
+        self.shader.fragment = self.FRAGMENT
+
+
 def make(cls, audio=None, background=None, score=None, **fields):
     """Build a scene class with its inputs set before `build()` runs (class attributes, like demo.py's Life)"""
     attrs = {}

@@ -419,7 +419,13 @@ int sfx_video_destroy(sfx_handle video);
  *
  * With a piano (a scene with one ShaderPiano): per frame, in front of the first pass, the piano's frame (sfx_piano_step with
  * piano_ticks[f]) and piano_ticks[f].dynamic stored into the uniform `piano_dynamic_name` ("iPianoDynamic") of every pass' program
- * that has one. A tape and a piano in one call are refused (SFX_E_UNSUPPORTED).
+ * that has one.
+ *
+ * With a tape and a piano (a piano roll with its sound track): both of the above in one call. The piano's frame goes first, on the render
+ * stream; a pass that reads audio is drawn from the tape frame and sees the frame's piano_ticks[f].dynamic and the piano's textures as
+ * every other pass does (they are the program's own uniforms and bound samplers, read when the pass is drawn). The call uses the
+ * render stream and the tape's stream, as with a tape alone, and the bank's rendered mark stays behind its last draw. A tape of another
+ * context, a null tick table and frames outside the tape are SFX_E_INVALID as they are for each alone.
  *
  * With a video (a scene with one ShaderVideo): video_slots[f] is the slot whose staged frame lands in front of frame f's first pass
  * (what sfx_video_step does), or -1 for a scene frame that shows what was there. When the video's matrix is temporal, `video_names`

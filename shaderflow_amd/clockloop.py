@@ -51,7 +51,7 @@ def end_clock(policy: str, fps: float, speed: float, done: int) -> tuple[float, 
 
 class FrameSource:
     """What feeds sfx_sequence_run beside the clock: an audio tape, a piano, a staged video (tapesequence.py, pianosequence.py,
-    videosequence.py). `run_native` calls batches … consumed of its source, `run_source` the rest; as they stand here they do nothing,
+    videosequence.py), or several of them joined (JoinedSource). `run_native` calls batches … consumed of its source, `run_source` the rest; as they stand here they do nothing,
     and that is the clock loop's own source."""
     end = "last"                                                       # the clock behind the run (end_clock)
     chunked = True                                                     # sequence_gate saw to it that every chunk can be ONE native call; False: native_sequence is asked
@@ -65,6 +65,66 @@ class FrameSource:
     def settle(self, done): pass                                      # behind the run, however it ended: the host objects as the frame loop leaves them after `done` frames
     def finished(self, done, total): return True                      # whether a run_native that returned ran to its end (else a read-back error in `settle` is dropped)
     def release(self): pass
+
+
+class JoinedSource(FrameSource):
+    """Several frame sources in front of the same frames (pianotape.py: a piano and its sound track), in the order given. Every call
+    goes to every part in that order, `release` in reverse. At most one part may cut the run into batches (the tape), and a part whose
+    `take` shortens a call must be the last: what the parts in front of it set for the call must not have depended on the longer count.
+    `settle` reaches every part even when one raised; the first exception is raised again behind the last. `end` and `chunked` are the
+    owner's to say: they belong to the loop, not to a part."""
+
+    def __init__(self, parts, end: str = FrameSource.end, chunked: bool = FrameSource.chunked):
+        self.parts = list(parts)
+        self.end, self.chunked = end, chunked
+        cutting = [part for part in self.parts if type(part).batches is not FrameSource.batches]
+        if len(cutting) > 1:
+            raise ValueError(f"{len(cutting)} frame sources cut the run into batches of their own: {', '.join(type(part).__name__ for part in cutting)}")
+        self.cutting = cutting[0] if cutting else None
+
+    def prepare(self, times, dts, total):
+        for part in self.parts:
+            part.prepare(times, dts, total)
+
+    def batches(self, total):
+        return self.cutting.batches(total) if self.cutting is not None else FrameSource.batches(self, total)
+
+    def begin_batch(self, first, size):
+        for part in self.parts:
+            part.begin_batch(first, size)
+
+    def attach(self, sequence):
+        for part in self.parts:
+            part.attach(sequence)
+
+    def take(self, sequence, first, count, batch_first):
+        for k, part in enumerate(self.parts):
+            taken = part.take(sequence, first, count, batch_first)
+            assert 0 < taken <= count and (taken == count or k == len(self.parts) - 1), \
+                f"{type(part).__name__}.take shortened the call to {taken} of {count} frames in front of another source"
+            count = taken
+        return count
+
+    def consumed(self, first, count):
+        for part in self.parts:
+            part.consumed(first, count)
+
+    def settle(self, done):
+        failure = None
+        for part in self.parts:
+            try:
+                part.settle(done)
+            except Exception as error:
+                failure = failure or error
+        if failure is not None:
+            raise failure
+
+    def finished(self, done, total):
+        return all(part.finished(done, total) for part in self.parts)
+
+    def release(self):
+        for part in reversed(self.parts):
+            part.release()
 
 
 def sequence_gate(scene: "ShaderScene", flag: str, export: "Optional[ExportingHelper]" = None, turbo: bool = True, kind: Optional[type] = None,

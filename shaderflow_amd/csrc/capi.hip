@@ -1066,7 +1066,6 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
     plan.ring_slots = s.ring ? ring_slot_count(s.ring) : 0;
     if (!s.passes || s.npasses < 1 || s.nmatrices < 0 || (s.nmatrices && !s.matrices) || !s.clock || s.nframes < 0) return fail(SFX_E_INVALID, "clock sequence: null tables");
     if (plan.ring_slots < 0) return fail(SFX_E_INVALID, "clock sequence: invalid ring handle");
-    if (s.tape && s.piano) return fail(SFX_E_UNSUPPORTED, "sequence: a tape and a piano in one call are not supported");
     if (s.video && (s.tape || s.piano)) return fail(SFX_E_UNSUPPORTED, "sequence: a video together with a tape or a piano in one call is not supported");
     int video_rows = 0;
     if (s.video) {
@@ -1126,6 +1125,13 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
 // one through sfx_render_tape into iFinal — and every other pass is drawn exactly as without a tape. With a piano, k_piano_frame and
 // the note range go in front of every frame's first pass (pianosequence.py). With a video, k_video_frame goes in front of the first pass
 // of every frame a source frame lands on (videosequence.py).
+// With a tape AND a piano (pianotape.py) both hold at once, and a pass that reads audio and the piano needs nothing more: the note range
+// is stored into the program's own user[] and the piano's kernel writes into the textures the program's samplers name, in front of the
+// frame's passes; render_box and sfx_render_tape both call fill_args when the pass is drawn, which copies p->u and p->samplers as they
+// are then, and bind_tape replaces the audio half only (slots 1 and 2, the audio uniforms). Streams: the render stream (the piano's
+// kernel, the draws, the resolve, the conversion) and the tape's own (the builds) — as many as the tape sequence uses, no event or
+// allocation beyond its two. The bank's `rendered` mark still sits behind the last kernel of the call: k_piano_frame runs in FRONT of
+// a frame's passes, so the last kernel on the render stream is a draw, a resolve or the read-out's conversion, never the piano's.
 static int run_sequence(sfx_handle hc, Context* c, const sfx_sequence& s, SequencePlan& plan) {
     const TapeView* t = plan.taped ? &plan.tape : nullptr;
     auto box = [&](int m, int d, int l) -> sfx_handle {

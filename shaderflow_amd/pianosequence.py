@@ -18,9 +18,8 @@ program that declares it.
 
 A scene takes this loop when `main(batch=None)` finds it applicable (after ClockLoop, before TapeSequence) and
 `SHADERFLOW_PIANO_SEQUENCE` is not "0". Out of scope, so they keep the frame loop: python `update()` logic, a subclass of ShaderPiano,
-several pianos, audio modules beside the piano (`sfx_sequence_run` refuses a tape and a piano in one call: lifting that is the
-follow-up), sharded runs, and a
-key-press system whose early-out can fire (`precision != 0`) or that integrates.
+several pianos, sharded runs, and a key-press system whose early-out can fire (`precision != 0`) or that integrates. A piano beside
+audio modules is not this loop's either: it takes `PianoTapeSequence` (pianotape.py: this source and the tape's, joined).
 """
 from __future__ import annotations
 
@@ -107,39 +106,47 @@ def step_note_range(piano: ShaderPiano, times, dts) -> np.ndarray:
     return out
 
 
+def piano_textures(piano: ShaderPiano) -> tuple:
+    """The module and its four textures: what a sequence that computes the piano takes out of ClockLoop's judgement (sequence_gate)"""
+    return (piano, piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture)
+
+
+def piano_fits(piano: ShaderPiano) -> bool:
+    """Whether this piano is what k_piano_frame and the host-stepped note range compute (PianoSequence, and PianoTapeSequence beside an
+    audio tape): its textures as build() made them, a key-press system the kernel steps, a score inside the textures"""
+    if any(texture is None for texture in (piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture)):
+        return False
+    if (piano.keys_texture.size, piano.channel_texture.size, piano.roll_texture.size) != ((MAX_NOTE, 1), (MAX_NOTE, 1), (MAX_ROLLING, MAX_NOTE)):
+        return False
+    # the key-press system as the kernel steps it: 128 float32 values, an early-out that cannot fire (its maximum runs over ALL keys:
+    # at precision 0 the blocks are independent), no integral
+    keys = piano.key_press_dynamics
+    if keys.precision != 0 or keys.integrate:
+        return False
+    for name in STATE:
+        field = getattr(keys, name)
+        if not isinstance(field, np.ndarray) or field.dtype != np.float32 or field.shape != (MAX_NOTE,):
+            return False
+    note_range = piano.note_range_dynamics
+    if not all(isinstance(getattr(note_range, name), np.ndarray) and getattr(note_range, name).shape == (2,) for name in ("value", "target")):
+        return False
+    table = piano._table()
+    if len(table["pitch"]):
+        if table["pitch"].min() < 0 or table["pitch"].max() >= MAX_NOTE:
+            return False                                              # (update() would wrap or raise)
+        if not (np.isfinite(table["start"]).all() and np.isfinite(table["end"]).all()):
+            return False
+    return True
+
+
 class PianoSequence(FrameSource):
     end = "next"                                                       # the clock as scene.next leaves it behind the last frame
 
     @staticmethod
     def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
         # no python logic, no audio modules, no module type beside the piano and its textures that ClockLoop does not take
-        piano = sequence_gate(scene, "PIANO_SEQUENCE", export, turbo, ShaderPiano,
-                              taped=lambda piano: (piano, piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture))
-        if piano is None:
-            return False
-        if any(texture is None for texture in (piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture)):
-            return False
-        if (piano.keys_texture.size, piano.channel_texture.size, piano.roll_texture.size) != ((MAX_NOTE, 1), (MAX_NOTE, 1), (MAX_ROLLING, MAX_NOTE)):
-            return False
-        # the key-press system as the kernel steps it: 128 float32 values, an early-out that cannot fire (its maximum runs over ALL keys:
-        # at precision 0 the blocks are independent), no integral
-        keys = piano.key_press_dynamics
-        if keys.precision != 0 or keys.integrate:
-            return False
-        for name in STATE:
-            field = getattr(keys, name)
-            if not isinstance(field, np.ndarray) or field.dtype != np.float32 or field.shape != (MAX_NOTE,):
-                return False
-        note_range = piano.note_range_dynamics
-        if not all(isinstance(getattr(note_range, name), np.ndarray) and getattr(note_range, name).shape == (2,) for name in ("value", "target")):
-            return False
-        table = piano._table()
-        if len(table["pitch"]):
-            if table["pitch"].min() < 0 or table["pitch"].max() >= MAX_NOTE:
-                return False                                          # (update() would wrap or raise)
-            if not (np.isfinite(table["start"]).all() and np.isfinite(table["end"]).all()):
-                return False
-        return True
+        piano = sequence_gate(scene, "PIANO_SEQUENCE", export, turbo, ShaderPiano, taped=piano_textures)
+        return piano is not None and piano_fits(piano)
 
     def __init__(self, scene: "ShaderScene"):
         self.scene = scene

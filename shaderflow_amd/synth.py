@@ -32,3 +32,32 @@ def background_image(width: int = 1920, height: int = 1080, seed: int = 0) -> np
     gradient = np.linspace(0.15, 0.85, width)[None, :, None]*np.array([0.9, 0.6, 1.0])[None, None, :]
     fine = rng.random((height, width, 3))*0.08
     return np.clip((0.55*noise + 0.45*gradient + fine)*255.0, 0, 255).astype(np.uint8)
+
+
+SCORE_RELEASE = 0.05     # seconds a note of score_clip takes to fade to exact silence behind its end
+SCORE_ATTACK = 0.005     # … and to rise in front (no click)
+
+
+def score_clip(score, seconds: float, samplerate: int = 44100) -> np.ndarray:
+    """(samples, 2) float32: the sound of a score (PianoNotes: note, start, end, velocity), so that a piano roll has audio that follows
+    its notes without an asset. One sine per note at the pitch's equal-tempered frequency (A4 = note 69 = 440 Hz) from `start`, decaying
+    as exp(-2 t) while the note is held and linearly to zero over SCORE_RELEASE behind `end`; constant-power panning, note 21 hard left
+    to note 108 hard right; the sum is scaled down only if it would leave [-1, 1]. Silent wherever no note sounds."""
+    n = int(round(seconds*samplerate))
+    out = np.zeros((n, 2), np.float64)
+    for note in score:
+        first = max(0, int(math.ceil(note.start*samplerate)))
+        last = min(n, int(math.floor((note.end + SCORE_RELEASE)*samplerate)) + 1)
+        if last <= first:
+            continue
+        t = np.arange(first, last, dtype=np.float64)/samplerate - note.start
+        held = note.end - note.start
+        envelope = np.exp(-2.0*np.minimum(t, held))*np.clip(1.0 - (t - held)/SCORE_RELEASE, 0.0, 1.0)*np.clip(t/SCORE_ATTACK, 0.0, 1.0)
+        tone = 0.35*(note.velocity/127.0)*envelope*np.sin(2*math.pi*440.0*2.0**((note.note - 69)/12.0)*t)
+        pan = min(1.0, max(0.0, (note.note - 21)/87.0))*math.pi/2
+        out[first:last, 0] += math.cos(pan)*tone
+        out[first:last, 1] += math.sin(pan)*tone
+    peak = float(np.abs(out).max()) if n else 0.0
+    if peak > 1.0:
+        out /= peak
+    return out.astype(np.float32)
