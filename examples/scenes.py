@@ -453,9 +453,66 @@ class PianoAudio(_AudioScene):
         self.shader.fragment = self.FRAGMENT
 
 
-def make(cls, audio=None, background=None, score=None, **fields):
+def drifting_clip(width: int = 320, height: int = 180, step: int = 3):
+    """An endless clip for MusicVideo: synth.background_image drifting to the right by `step` pixels a frame, (height, width, 3) uint8"""
+    import itertools
+    image = synth.background_image(width, height, seed=3)
+    return (np.roll(image, step*k, axis=1) for k in itertools.count())
+
+
+class MusicVideo(_AudioScene):
+    """A clip with its sound track (not one of the reference's): the video fills the frame and glows with iAudioVolume, and along the
+    bottom edge runs a spectrum strip, one bin of iSpectrogram per column. `clip` as for Video — (frames, fps), or a path: a `.npy`, a
+    `.y4m` file, or what an ffmpeg binary decodes — and without one a drifting synthetic picture at 30 frames a second; `audio` as for
+    the audio scenes, and without one a sine sweep. No python logic between frames: the staged video and the audio tape feed one
+    native sequence (shaderflow_amd/videojoin.py)."""
+    clip = None
+    CLIP_SIZE, CLIP_FPS = (320, 180), 30.0
+    FRAGMENT = """
+        #define STRIP 0.2
+        void main() {
+            vec3 colour = texture(iVideo, astuv).rgb;
+            float loud = clamp(iAudioVolume, 0.0, 1.0);
+            // the glow: the picture brightens with the loudness of the moment, most towards the edges
+            colour = colour*(0.75 + 0.5*loud) + vec3(0.25, 0.12, 0.35)*loud*smoothstep(0.4, 1.4, length(gluv));
+            if (astuv.y < STRIP) {
+                // the spectrum strip: the level of the column's bin, both channels, rising from the bottom edge over the dimmed clip
+                vec2 s = texture(iSpectrogram, vec2(0.5, astuv.x)).xy;
+                float level = clamp(sqrt(max(0.5*(s.x + s.y), 0.0))/30.0, 0.0, 1.0);
+                float up = astuv.y/STRIP;
+                vec3 bar = hsv2rgb(vec3(0.66 - 0.6*level, 0.8, 1.0))*(0.6 + 0.4*up);
+                colour = mix(0.45*colour, bar, step(up, level));
+            }
+            fragColor = vec4(colour, 1.0);
+        }
+    """
+
+    def build(self):
+        from shaderflow_amd.audio.spectrogram import ShaderSpectrogram
+        from shaderflow_amd.piano import PianoNote
+        from shaderflow_amd.video import ShaderVideo
+        super().build()
+        if isinstance(self.clip, (str, Path)):
+            self.video = ShaderVideo(scene=self, path=self.clip)
+        elif self.clip is not None:
+            frames, fps = self.clip
+            self.video = ShaderVideo(scene=self, frames=frames, fps=fps)
+        else:
+            (width, height), fps = self.CLIP_SIZE, self.CLIP_FPS
+            self.video = ShaderVideo(scene=self, frames=drifting_clip(width, height), width=width, height=height, fps=fps)
+        if self.audio_source is None:
+            self.audio_source = (synth.sweep_clip(10.0, 44100), 44100)
+        self._load_audio()
+        self.spectrogram = ShaderSpectrogram(scene=self, length=0, audio=self.audio, smooth=False)
+        self.spectrogram.from_notes(start=PianoNote.from_frequency(20), end=PianoNote.from_frequency(14000), piano=True)
+        self.shader.fragment = self.FRAGMENT
+
+
+def make(cls, audio=None, background=None, score=None, clip=None, **fields):
     """Build a scene class with its inputs set before `build()` runs (class attributes, like demo.py's Life)"""
     attrs = {}
+    if clip is not None:
+        attrs["clip"] = clip
     if score is not None:
         attrs["score"] = score
     if audio is not None:

@@ -431,7 +431,20 @@ int sfx_video_destroy(sfx_handle video);
  * (what sfx_video_step does), or -1 for a scene frame that shows what was there. When the video's matrix is temporal, `video_names`
  * holds the sampler name of each of its rows (depth 0 first) and every pass' program that declares one gets the row now at that depth
  * — the mechanism of sfx_sequence_matrix.names, except that this matrix rolls on landing frames only (the host rolls its own by the
- * number of landings afterwards). A video together with a tape or a piano in one call is refused (SFX_E_UNSUPPORTED). */
+ * number of landings afterwards).
+ *
+ * With a video and a tape, a piano, or both (a clip with its sound track, a piano roll over a clip): refused with SFX_E_UNSUPPORTED unless
+ * `video_join` is non-zero — the descriptor's last field, zero in every descriptor written before it existed, so that a caller who
+ * never heard of the combination keeps the answer it was written against. With `video_join` set all of the above hold in one call, per
+ * frame in this order: the piano's frame, the video's landing, the passes. A pass that reads audio is drawn from the tape frame and
+ * samples the video like every other pass: the tape replaces sampler slots 1 (iSpectrogram) and 2 (iWaveform) and the audio uniforms
+ * only, and a video's sampler never sits in those two slots (the stock `video` fragment keeps it at the history slots, a translated
+ * one hands the two out to those two names alone). A descriptor in which one does — a video box bound under iSpectrogram or iWaveform
+ * of a pass that reads audio — is SFX_E_INVALID, named in the message, rather than a draw from the wrong texture. Every other check
+ * stands as for the parts alone (null slot table, a video or a tape of another context, frames outside the tape, null tick table:
+ * SFX_E_INVALID). Streams: the render stream, the tape's build stream and the video's copy stream — what the parts own, nothing more;
+ * the bank's rendered mark stays behind the call's last kernel (k_video_frame, as k_piano_frame, runs in FRONT of a frame's passes),
+ * and a slot is released by the event recorded right behind its k_video_frame, as without a tape. */
 enum { SFX_PASS_LAYERS = 0, SFX_PASS_FUSED = 1, SFX_PASS_RESOLVE = 2 };
 typedef struct sfx_sequence_pass { sfx_handle program; int kind; int matrix; sfx_handle target; int ssaa; int subsample; } sfx_sequence_pass;
 typedef struct sfx_sequence_matrix { int temporal, layers; const sfx_handle* textures; const char* const* names; } sfx_sequence_matrix;
@@ -457,6 +470,8 @@ typedef struct sfx_sequence {
     sfx_handle piano; const sfx_piano_tick* piano_ticks; const char* piano_dynamic_name;
     /* optional: the video. video == 0: none */
     sfx_handle video; const int32_t* video_slots; const char* const* video_names;
+    /* non-zero: a video may stand beside a tape or a piano in this call (above). Zero: that combination is SFX_E_UNSUPPORTED */
+    int32_t video_join;
 } sfx_sequence;
 int sfx_sequence_run(sfx_handle ctx, const sfx_sequence* sequence);
 

@@ -78,14 +78,16 @@ class PianoTick(C.Structure):
 
 
 class Sequence(C.Structure):
-    """sfx_sequence (include/shaderflow_hip.h), field for field: the tables, the sink, the optional tape, the optional piano, the optional video"""
+    """sfx_sequence (include/shaderflow_hip.h), field for field: the tables, the sink, the optional tape, the optional piano, the optional video, and whether
+    the video may stand beside the other two (`video_join`, zero unless a caller sets it)"""
     _fields_ = [("passes", C.POINTER(SequencePass)), ("npasses", C.c_int), ("matrices", C.POINTER(SequenceMatrix)), ("nmatrices", C.c_int),
                 ("clock", C.POINTER(ClockTick)), ("nframes", C.c_int),
                 ("ring", Handle), ("first_slot", C.c_int), ("fd", C.c_int), ("planar_slots", C.POINTER(C.c_void_p)),
                 ("yuv_matrix", C.c_int), ("width", C.c_int), ("height", C.c_int),
                 ("tape", Handle), ("tape_frame0", C.c_int),
                 ("piano", Handle), ("piano_ticks", C.POINTER(PianoTick)), ("piano_dynamic_name", C.c_char_p),
-                ("video", Handle), ("video_slots", C.POINTER(C.c_int32)), ("video_names", C.POINTER(C.c_char_p))]
+                ("video", Handle), ("video_slots", C.POINTER(C.c_int32)), ("video_names", C.POINTER(C.c_char_p)),
+                ("video_join", C.c_int32)]
 
 
 class Binding(C.Structure):

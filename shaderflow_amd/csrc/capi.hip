@@ -1066,7 +1066,7 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
     plan.ring_slots = s.ring ? ring_slot_count(s.ring) : 0;
     if (!s.passes || s.npasses < 1 || s.nmatrices < 0 || (s.nmatrices && !s.matrices) || !s.clock || s.nframes < 0) return fail(SFX_E_INVALID, "clock sequence: null tables");
     if (plan.ring_slots < 0) return fail(SFX_E_INVALID, "clock sequence: invalid ring handle");
-    if (s.video && (s.tape || s.piano)) return fail(SFX_E_UNSUPPORTED, "sequence: a video together with a tape or a piano in one call is not supported");
+    if (s.video && (s.tape || s.piano) && !s.video_join) return fail(SFX_E_UNSUPPORTED, "sequence: a video together with a tape or a piano in one call is not supported");
     int video_rows = 0;
     if (s.video) {
         if (!s.video_slots) return fail(SFX_E_INVALID, "video sequence: null slot table");
@@ -1116,6 +1116,18 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
         if (s.piano && s.piano_dynamic_name)
             for (const auto& b : p->bindings)
                 if (!b.sampler && !b.integer && b.count >= 2 && b.name == s.piano_dynamic_name) plan.dynamic_slots.push_back({p, b.slot});
+        // a video beside the tape: bind_tape replaces slots TEX_SPECTROGRAM and TEX_WAVEFORM of a pass that reads audio, so no box of
+        // the video may sit there — neither bound by the host nor named as a row of the temporal matrix. The stock fragment keeps
+        // the video at TEX_HISTORY + depth and a translated one gives the two slots to iSpectrogram / iWaveform alone (glsl2hip.py
+        // FIXED_SAMPLER_SLOTS): only a video texture that goes by one of those two names gets here
+        if (s.video && plan.audio[k])
+            for (const int slot : {(int)TEX_SPECTROGRAM, (int)TEX_WAVEFORM}) {
+                bool taken = false;
+                for (const auto& b : plan.video_binds) taken = taken || (b.p == p && b.slot == slot);
+                for (int d = 0; d < video_rows && p->samplers[slot]; d++) taken = taken || (p->samplers[slot] == get<Texture>(video_box(s.video, d), MAGIC_TEX));
+                if (taken) return fail(SFX_E_INVALID, "sequence: pass %d reads the video through sampler %s (slot %d), which the tape replaces with its own frame", k,
+                                       slot == TEX_SPECTROGRAM ? "iSpectrogram" : "iWaveform", slot);
+            }
     }
     return SFX_OK;
 }
@@ -1132,6 +1144,11 @@ static int plan_sequence(Context* c, const sfx_sequence& s, SequencePlan& plan) 
 // kernel, the draws, the resolve, the conversion) and the tape's own (the builds) — as many as the tape sequence uses, no event or
 // allocation beyond its two. The bank's `rendered` mark still sits behind the last kernel of the call: k_piano_frame runs in FRONT of
 // a frame's passes, so the last kernel on the render stream is a draw, a resolve or the read-out's conversion, never the piano's.
+// With a video beside them (videojoin.py, `video_join`) the same holds once more: k_video_frame goes between the piano's frame and the
+// passes, so it is never the call's last kernel either; the event that frees its slot is recorded right behind it by
+// video_launch_frame, as without a tape; a pass drawn from the tape samples the video through p->samplers like any other (plan_sequence
+// keeps the video out of the two slots bind_tape replaces). Three streams then — render, the tape's builds, the video's copies — each
+// owned by its part; the call adds no stream, event or allocation.
 static int run_sequence(sfx_handle hc, Context* c, const sfx_sequence& s, SequencePlan& plan) {
     const TapeView* t = plan.taped ? &plan.tape : nullptr;
     auto box = [&](int m, int d, int l) -> sfx_handle {

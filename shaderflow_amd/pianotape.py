@@ -19,7 +19,7 @@ A scene takes this loop when `main(batch=None)` finds it applicable (after Piano
 and none of `SHADERFLOW_PIANO_TAPE`, `SHADERFLOW_PIANO_SEQUENCE`, `SHADERFLOW_TAPE_SEQUENCE` is "0" — who switched a half off for an
 A/B run gets the host's half. Out of scope, so they keep the frame loop: everything either half refuses (python `update()` logic,
 subclassed or several pianos, subclassed audio modules, audio a tape does not compute, a main camera off the identity pose, sharded
-runs), and a video beside them.
+runs). With a video beside them the scene is `VideoJoinedSequence`'s (videojoin.py), asked before this loop.
 """
 from __future__ import annotations
 

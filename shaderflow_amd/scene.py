@@ -68,6 +68,7 @@ class ShaderScene(ShaderModule):
     piano_sequence = None                                     # … and the PianoSequence (pianosequence.py)
     piano_tape = None                                         # … and the PianoTapeSequence (pianotape.py)
     video_sequence = None                                     # … and the VideoSequence (videosequence.py)
+    video_join = None                                         # … and the VideoJoinedSequence (videojoin.py)
     _fused_this_frame: bool = False
     _skip_render: bool = False
     shard_warmup = "auto"                                     # plain class attribute: subclasses override it like `life_period`
@@ -348,6 +349,7 @@ class ShaderScene(ShaderModule):
         self.piano_sequence = None
         self.piano_tape = None
         self.video_sequence = None
+        self.video_join = None
 
         _width, _height = self.resize(width=width, height=height, ratio=ratio, scale=scale)
 
@@ -387,7 +389,8 @@ class ShaderScene(ShaderModule):
             return self._sharded_frame_loop(export, turbo, *(shard or rank_world()))
         # The loops that spare scene.next, in the order they are asked; the one that ran is kept under its attribute (tests, tools):
         # nothing but the clock moves between frames (clockloop.py: the lean loop, same frames); a ShaderVideo without python logic, its
-        # frames staged ahead (videosequence.py); a ShaderPiano without python logic, its score on the device (pianosequence.py); the
+        # frames staged ahead (videosequence.py); the same beside audio modules, a piano or both, the staged video, the device tape and
+        # the piano in one native call (videojoin.py); a ShaderPiano without python logic, its score on the device (pianosequence.py); the
         # same beside audio modules, the piano and the device tape in one native call (pianotape.py); audio-reactive layered / temporal
         # / multi-program scenes on the device tape (tapesequence.py); audio scenes with python logic of their own, the user's update()
         # frame by frame (tapeloop.py)
@@ -396,9 +399,10 @@ class ShaderScene(ShaderModule):
         from shaderflow_amd.pianotape import PianoTapeSequence
         from shaderflow_amd.tapeloop import TapeLoop
         from shaderflow_amd.tapesequence import TapeSequence
+        from shaderflow_amd.videojoin import VideoJoinedSequence
         from shaderflow_amd.videosequence import VideoSequence
-        loops = ((None, ClockLoop), ("video_sequence", VideoSequence), ("piano_sequence", PianoSequence), ("piano_tape", PianoTapeSequence),
-                 ("tape_sequence", TapeSequence), ("tape_loop", TapeLoop))
+        loops = ((None, ClockLoop), ("video_sequence", VideoSequence), ("video_join", VideoJoinedSequence), ("piano_sequence", PianoSequence),
+                 ("piano_tape", PianoTapeSequence), ("tape_sequence", TapeSequence), ("tape_loop", TapeLoop))
         for attribute, loop in loops[0 if self.freewheel and self.clock_loop else 1:]:
             if batch is None and loop.applicable(self, export, turbo):
                 runner = loop(self)

@@ -22,10 +22,10 @@ Behind a run — finished, quit or failed — the host objects are where the fra
 draws go back in front of it for a later `update()`.
 
 A scene takes this loop when `main(batch=None)` finds it applicable (after ClockLoop, before PianoSequence) and
-`SHADERFLOW_VIDEO_SEQUENCE` is not "0". Out of scope, so they keep the frame loop: a video beside audio or piano modules
-(`sfx_sequence_run` refuses the combination), several videos, `layers != 1`, a subclass of ShaderVideo, sharded runs, a scene `update()`
-of its own, and — for the planar sources — bt709 or full-range input, chroma interpolation and 10-bit sources (the reader refuses what
-it can see of them).
+`SHADERFLOW_VIDEO_SEQUENCE` is not "0". A video beside audio modules or a piano is not this loop's: it takes `VideoJoinedSequence`
+(videojoin.py: this source joined with the tape's and the piano's). Out of scope, so they keep the frame loop: several videos,
+`layers != 1`, a subclass of ShaderVideo, sharded runs, a scene `update()` of its own, and — for the planar sources — bt709 or
+full-range input, chroma interpolation and 10-bit sources (the reader refuses what it can see of them).
 """
 from __future__ import annotations
 
@@ -70,6 +70,15 @@ def landing_frames(times, fps: float, first_read: int = 0, available: Optional[i
     return out
 
 
+def video_fits(video: ShaderVideo) -> bool:
+    """Whether this video's texture is what k_video_frame writes (VideoSequence, and VideoJoinedSequence beside a tape or a piano): one
+    layer of RGB8 of the clip's own size that follows no resolution, every box on the device"""
+    texture = video.texture
+    if texture is None or texture.layers != 1 or texture.components != 3 or texture.dtype != np.uint8:
+        return False
+    return not texture.track and texture.size == (video.width, video.height) and all(box.texture is not None for (_, _, box) in texture.boxes)
+
+
 class VideoSequence(FrameSource):
     end = "next"                                                       # the clock as scene.next leaves it behind the last frame
 
@@ -77,12 +86,7 @@ class VideoSequence(FrameSource):
     def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
         # no python logic, no audio modules, no piano, no module type beside the video and its texture that ClockLoop does not take
         video = sequence_gate(scene, "VIDEO_SEQUENCE", export, turbo, ShaderVideo, taped=lambda video: (video, video.texture))
-        if video is None:
-            return False
-        texture = video.texture
-        if texture is None or texture.layers != 1 or texture.components != 3 or texture.dtype != np.uint8:
-            return False
-        return not texture.track and texture.size == (video.width, video.height) and all(box.texture is not None for (_, _, box) in texture.boxes)
+        return video is not None and video_fits(video)
 
     def __init__(self, scene: "ShaderScene"):
         self.scene = scene
