@@ -192,12 +192,38 @@ int sfx_ring_sync(sfx_handle ring, int slot, void** host_ptr);                  
 int sfx_ring_pipe(sfx_handle ring, int slot, int fd);                               /* turbopipe.pipe */
 int sfx_ring_pipe_sync(sfx_handle ring, int slot);                                  /* turbopipe.sync; slot < 0: all */
 int sfx_ring_destroy(sfx_handle ring);
+/* A ring of SINK frames that say how long they are: [64-byte header: magic "SFJP", payload bytes, status, zeros][payload], `capacity`
+ * bytes each at the most. The copier reads a frame's header first and then exactly its payload (no stream, event or queue is added);
+ * the writer writes the payload alone (`framing` 0) or as an AVI chunk (`framing` 1: "00dc", little-endian size, payload, a pad byte
+ * to an even length) and notes its size. A frame whose status is not zero is not written: the next pipe_sync that meets it fails with
+ * SFX_E_TOO_LARGE and the frame's number (counted from the ring's first), once, and the ring goes on working. Every other entry point
+ * of a ring works on a sized one, texture reads excepted. */
+int sfx_ring_create_sized(sfx_handle ctx, size_t capacity, int slots, int framing, sfx_handle* ring);
+/* payload sizes of the frames written so far, in write order (the index of an AVI file); `out` may be null to ask for the count */
+int sfx_ring_sizes(sfx_handle ring, uint32_t* out, size_t capacity, size_t* count);
 
 /* Encoder hand-off, optional half (exporting.py:94-134): `frames` RGB8 frames (consecutive, width*height*3 bytes each) on
  * the device → planar yuv420p (I420: Y, U, V; width*height*3/2 bytes each) on the device, on the context's stream. BT.601 limited
  * range (matrix 0) or BT.709 limited (1) in 8-bit integer arithmetic, chroma from the rounded 2x2 mean of R, G, B — defined in
  * capi_readout.hip, restated in the oracle. Half the bytes over PCIe and the pipe: ffmpeg takes `-pix_fmt yuv420p` rawvideo as it is. */
 int sfx_rgb_to_yuv420(sfx_handle ctx, const void* rgb, void* yuv, int width, int height, int frames, int matrix);
+
+/* Motion-JPEG on the device (csrc/jpeg_kernels.hpp defines the stream): baseline sequential JFIF, 8 bit, 4:2:0, the
+ * standard's Annex K tables scaled by `quality` (1…100) and its Huffman tables, one restart interval per MCU row, top row first.
+ * Colour is full range in 8-bit integers: Y = (77 R + 150 G + 29 B + 128) >> 8, Cb = ((-43 R - 85 G + 128 B + 128) >> 8) + 128,
+ * Cr = ((128 R - 107 G - 21 B + 128) >> 8) + 128, chroma from the rounded 2x2 mean of R, G, B; partial MCUs repeat the last column and
+ * row; f32 DCT, round-half-away quantisation. An encoder belongs to one context and one picture size and is destroyed before it.
+ * encode: `frames` RGB8 frames on the device (consecutive, width*height*3 bytes each; `bottom_up` non-zero: their rows are stored
+ * bottom-up) become sink frames on the device, 64 + Wp*Hp*3 bytes apart (Wp, Hp: the extents rounded up to 16), laid out as a sized
+ * ring reads them; on the context's stream, three launches per batch. A frame that does not fit its capacity gets status 1 and no
+ * payload: no fault. header: the constant bytes in front of every frame's entropy-coded data (SOI … SOS); *count is the buffer's size
+ * on entry (ignored when `buffer` is null) and the header's on return. coefficients: the last encoded frame's quantised terms, int16,
+ * mcu rows x mcus per row x 6 (Y0 Y1 Y2 Y3 Cb Cr) x 64 in zigzag order; synchronous, for tests. */
+int sfx_jpeg_create(sfx_handle ctx, int width, int height, int quality, sfx_handle* encoder);
+int sfx_jpeg_destroy(sfx_handle encoder);
+int sfx_jpeg_encode(sfx_handle encoder, const void* rgb, void* sink, int frames, int bottom_up);
+int sfx_jpeg_header(sfx_handle encoder, void* buffer, size_t* count);
+int sfx_jpeg_coefficients(sfx_handle encoder, int16_t* out);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* Cross-process frame queue of a sharded export (one process per GPU; no reference equivalent). The sink takes

@@ -20,6 +20,7 @@ NEAREST, LINEAR = 0, 1
 T_FLOAT, T_INT, T_BOOL, T_VEC2, T_VEC3, T_VEC4, T_MAT2, T_MAT3, T_MAT4 = range(9)
 TAPE_SPECTROGRAM, TAPE_WAVEFORM, TAPE_UNIFORMS, TAPE_TARGETS, TAPE_LOUDNESS, TAPE_SCROLL, TAPE_STATE = range(7)
 E_UNSUPPORTED = -4
+E_TOO_LARGE = -6
 
 Handle = C.c_uint64
 
@@ -150,6 +151,13 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_ring_pipe": (C.c_int, [Handle, C.c_int, C.c_int]),
     "sfx_ring_pipe_sync": (C.c_int, [Handle, C.c_int]),
     "sfx_ring_destroy": (C.c_int, [Handle]),
+    "sfx_ring_create_sized": (C.c_int, [Handle, C.c_size_t, C.c_int, C.c_int, P(Handle)]),
+    "sfx_ring_sizes": (C.c_int, [Handle, P(C.c_uint32), C.c_size_t, P(C.c_size_t)]),
+    "sfx_jpeg_create": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, P(Handle)]),
+    "sfx_jpeg_destroy": (C.c_int, [Handle]),
+    "sfx_jpeg_encode": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "sfx_jpeg_header": (C.c_int, [Handle, C.c_void_p, P(C.c_size_t)]),
+    "sfx_jpeg_coefficients": (C.c_int, [Handle, P(C.c_int16)]),
     "sfx_rgb_to_yuv420": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sfx_peer_export": (C.c_int, [Handle, C.c_void_p, C.c_void_p]),
     "sfx_peer_open": (C.c_int, [Handle, C.c_void_p, P(C.c_void_p)]),
@@ -350,6 +358,37 @@ class Context:
     def destroy(self) -> None:
         if self.handle.value:
             lib().sfx_ctx_destroy(self.handle)
+            self.handle = Handle()
+
+
+class JpegEncoder:
+    """Motion-JPEG encoder of one context and one picture size (sfx_jpeg_*): RGB8 frames on the device → sink frames on the device"""
+    SINK_HEADER = 64
+
+    def __init__(self, context: Context, width: int, height: int, quality: int = 90):
+        self.context, self.width, self.height, self.quality = context, width, height, quality
+        self.handle = Handle()
+        check(lib().sfx_jpeg_create(context.handle, width, height, quality, C.byref(self.handle)))
+        self.mcus_x, self.mcus_y = (width + 15)//16, (height + 15)//16
+        self.sink_bytes = self.SINK_HEADER + self.mcus_x*self.mcus_y*768
+
+    def encode(self, rgb: int, sink: int, frames: int = 1, bottom_up: bool = False) -> None:
+        check(lib().sfx_jpeg_encode(self.handle, C.c_void_p(rgb), C.c_void_p(sink), frames, 1 if bottom_up else 0))
+
+    def header(self) -> bytes:
+        count = C.c_size_t(2048)
+        buffer = C.create_string_buffer(count.value)
+        check(lib().sfx_jpeg_header(self.handle, buffer, C.byref(count)))
+        return buffer.raw[:count.value]
+
+    def coefficients(self) -> np.ndarray:
+        out = np.empty((self.mcus_y, self.mcus_x, 6, 64), np.int16)
+        check(lib().sfx_jpeg_coefficients(self.handle, as_ptr(out, C.c_int16)))
+        return out
+
+    def destroy(self) -> None:
+        if self.handle.value:
+            lib().sfx_jpeg_destroy(self.handle)
             self.handle = Handle()
 
 

@@ -136,6 +136,8 @@ def sequence_gate(scene: "ShaderScene", flag: str, export: "Optional[ExportingHe
     import os
     if os.environ.get(f"SHADERFLOW_{flag}", "1") == "0" or not scene.freewheel or is_sharded():
         return None
+    if export is not None and export.mjpeg:                         # sfx_sequence_run's own sink knows rgb24 and yuv420p: the loop from before the sequences draws
+        return None
     found = [scene] if kind is None else [m for m in scene.modules if isinstance(m, kind)]
     if len(found) != 1 or type(found[0]) is not (kind or type(scene)):
         return None
@@ -242,7 +244,7 @@ class ClockLoop:
         progress relay (a relay wants a python call per frame), every program compiled. SHADERFLOW_CLOCK_SEQUENCE=0 keeps the python loop
         (A/B measurements, and the byte-equality test of the two)."""
         import os
-        if os.environ.get("SHADERFLOW_CLOCK_SEQUENCE", "1") == "0" or not turbo or export.relay is not None:
+        if os.environ.get("SHADERFLOW_CLOCK_SEQUENCE", "1") == "0" or not turbo or export.relay is not None or export.mjpeg:
             return False
         return all(program.program is not None for program in self.programs)
 

@@ -504,7 +504,7 @@ struct Ring : Object {
     std::vector<hipEvent_t> ready;                                  // per slot: recorded on the render stream when the slot's frame is complete
     hipEvent_t fences[2];
     // copier: waits for a frame on the host, copies it on an engine lane (two in flight), marks the slot copied
-    struct CopyJob { int slot; const void* source; hipEvent_t ready; };
+    struct CopyJob { int slot; const void* source; hipEvent_t ready; long frame; };
     std::thread copier;
     std::deque<CopyJob> copy_queue;
     std::vector<int> copying;                       // 1 while the slot's copy is queued or in flight
@@ -519,7 +519,16 @@ struct Ring : Object {
     std::vector<int> pending;                       // writes queued or running per slot
     bool stop = false;
     int io_error = 0;
+    // sized mode (sfx_ring_create_sized): a slot's frame is [64-byte header: magic, payload bytes, status][payload]; the copier reads
+    // the header first and copies exactly the payload, the writer frames it (`framing` 1: an AVI "00dc" chunk) and notes its size
+    bool sized = false;
+    int framing = 0;
+    std::vector<uint32_t> payload;                  // per slot: bytes of the frame that landed (0: a failed frame, nothing is written)
+    std::vector<uint32_t> sizes;                    // payload sizes in write order
+    long frames_queued = 0, unfit_frame = -1;       // unfit_frame: a frame whose status said it did not fit (reported once by the next wait)
 };
+constexpr uint32_t SINK_MAGIC = 0x504a4653u;        // jpeg_kernels.hpp JPEG_SINK_MAGIC
+constexpr size_t SINK_HEADER = 64;
 
 static void ring_copier(Ring* r) {
     hipSetDevice(r->ctx->device);
@@ -557,9 +566,29 @@ static void ring_copier(Ring* r) {
         const auto t2 = std::chrono::steady_clock::now();
         if (trace) fprintf(stderr, "ring copier: slot %d event wait %.0f us, lane finish %.0f us\n", job.slot, std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count());
         r->lanes.resolve(r->ctx, r->host[job.slot], job.source);
-        if (!rendered || !r->lanes.issue(next, r->host[job.slot], job.source, r->frame_bytes)) {
+        char* landing = (char*)r->host[job.slot];
+        const char* source = (const char*)job.source;
+        size_t nbytes = r->frame_bytes;
+        if (r->sized && rendered) {
+            // the header on this lane, to the end; then the payload of exactly the length it names, behind it
+            uint32_t header[3] = {0, 0, 0};
+            const bool read = r->lanes.issue(next, landing, source, SINK_HEADER) && r->lanes.finish(next);
+            if (read) memcpy(header, landing, sizeof header);
+            const bool fits = read && header[0] == SINK_MAGIC && header[2] == 0 && header[1] > 0 && header[1] <= r->frame_bytes - SINK_HEADER;
+            if (!fits) {
+                std::lock_guard<std::mutex> lock(r->mutex);
+                if (!read) r->copy_error = 1; else if (r->unfit_frame < 0) r->unfit_frame = job.frame;
+                r->payload[job.slot] = 0; r->copying[job.slot] = 0;
+                r->idle.notify_all();
+                continue;
+            }
+            { std::lock_guard<std::mutex> lock(r->mutex); r->payload[job.slot] = header[1]; }
+            landing += SINK_HEADER; source += SINK_HEADER; nbytes = header[1];
+        }
+        if (!rendered || !r->lanes.issue(next, landing, source, nbytes)) {
             std::lock_guard<std::mutex> lock(r->mutex);
             r->copy_error = 1; r->copying[job.slot] = 0;
+            if (r->sized) r->payload[job.slot] = 0;
             r->idle.notify_all();
             continue;
         }
@@ -580,6 +609,21 @@ static void ring_writer(Ring* r) {
         }
         const char* p = (const char*)r->host[job.first];
         size_t left = r->frame_bytes;
+        if (r->sized) {
+            // the framing goes into the header's last bytes, right in front of the payload: one run of bytes for write()
+            uint32_t size;
+            { std::lock_guard<std::mutex> lock(r->mutex); size = r->payload[job.first]; if (size) r->sizes.push_back(size); }
+            char* start = (char*)r->host[job.first] + SINK_HEADER;
+            left = size;
+            if (size && r->framing == 1) {
+                start[size] = 0;                                       // the pad byte to an even length
+                left = size + (size & 1) + 8;
+                start -= 8;
+                memcpy(start, "00dc", 4);
+                for (int k = 0; k < 4; k++) start[4 + k] = (char)(size >> 8*k);
+            }
+            p = start;
+        }
         int err = 0;
         while (left > 0) {
             ssize_t n = ::write(job.second, p, left);
@@ -595,18 +639,20 @@ static void ring_writer(Ring* r) {
     }
 }
 
-extern "C" int sfx_ring_create(sfx_handle h, size_t frame_bytes, int slots, sfx_handle* out) {
+static int ring_create(sfx_handle h, size_t frame_bytes, int slots, bool sized, int framing, sfx_handle* out) {
     CTX_OR_FAIL(c, h);
     if (!out || slots < 1 || slots > 64 || frame_bytes == 0) return fail(SFX_E_INVALID, "ring of %d slots x %zu bytes", slots, frame_bytes);
+    if (sized && (frame_bytes <= SINK_HEADER || framing < 0 || framing > 1)) return fail(SFX_E_INVALID, "sized ring of %zu-byte frames, framing %d", frame_bytes, framing);
     USE_DEVICE(c);
     Ring* r = new Ring();
     r->magic = MAGIC_RING; r->ctx = c; r->frame_bytes = frame_bytes; r->slots = slots;
+    r->sized = sized; r->framing = framing; r->payload.assign(slots, 0);
     r->host.resize(slots); r->ready.resize(slots); r->pending.assign(slots, 0); r->copying.assign(slots, 0);
     r->lane_count = std::min(EngineLanes::LANES, std::max(1, slots - 1));                             // (a slot is being filled or written while the others land)
     if (const char* n = getenv("SHADERFLOW_COPY_STREAMS")) r->lane_count = std::min(r->lane_count, std::max(1, atoi(n)));   // A/B switch for measurements
     for (auto& f : r->fences) HIP_TRY(hipEventCreateWithFlags(&f, hipEventDisableTiming));
     for (int k = 0; k < slots; k++) {
-        HIP_TRY(hipHostMalloc(&r->host[k], frame_bytes, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(&r->host[k], frame_bytes + (sized ? 16 : 0), hipHostMallocDefault));   // (sized: room for the pad byte)
         HIP_TRY(hipEventCreateWithFlags(&r->ready[k], hipEventDisableTiming));
     }
     r->copier = std::thread(ring_copier, r);
@@ -619,11 +665,32 @@ extern "C" int sfx_ring_create(sfx_handle h, size_t frame_bytes, int slots, sfx_
     *out = handle_of(r);
     return SFX_OK;
 }
+extern "C" int sfx_ring_create(sfx_handle h, size_t frame_bytes, int slots, sfx_handle* out) { return ring_create(h, frame_bytes, slots, false, 0, out); }
+// A ring of SINK frames that say how long they are (`capacity` bytes each at the most, header included): see Ring::sized
+extern "C" int sfx_ring_create_sized(sfx_handle h, size_t capacity, int slots, int framing, sfx_handle* out) { return ring_create(h, capacity, slots, true, framing, out); }
+
+// payload sizes of the frames written so far, in write order (the AVI index)
+extern "C" int sfx_ring_sizes(sfx_handle h, uint32_t* out, size_t capacity, size_t* count) {
+    Ring* r = get<Ring>(h, MAGIC_RING);
+    if (!r || !r->sized || !count) return fail(SFX_E_INVALID, "invalid ring handle, not a sized ring, or null count");
+    std::lock_guard<std::mutex> lock(r->mutex);
+    *count = r->sizes.size();
+    if (out) memcpy(out, r->sizes.data(), sizeof(uint32_t)*std::min(capacity, r->sizes.size()));
+    return SFX_OK;
+}
+
+// a frame of a sized ring whose status said it did not fit: reported once, by the wait that meets it; the ring goes on working
+static int ring_unfit(Ring* r) {
+    const long frame = r->unfit_frame;
+    r->unfit_frame = -1;
+    return fail(SFX_E_TOO_LARGE, "frame %ld does not fit its sink frame", frame);
+}
 
 // the slot's last frame has been written out (turbopipe.sync(buffer) before reuse) AND any copy into it has landed
 static int ring_wait_slot(Ring* r, int slot) {
     std::unique_lock<std::mutex> lock(r->mutex);
     r->idle.wait(lock, [&] { return r->pending[slot] == 0 && r->copying[slot] == 0; });
+    if (r->unfit_frame >= 0) return ring_unfit(r);
     if (r->copy_error) return fail(SFX_E_HIP, "frame read-out: neither HSA nor HIP accepted the copy");
     return r->io_error ? fail(SFX_E_IO, "pipe write failed: %s", strerror(r->io_error)) : SFX_OK;
 }
@@ -636,7 +703,7 @@ static int ring_queue_copy(Ring* r, const void* dptr, int slot, hipEvent_t ready
     {
         std::lock_guard<std::mutex> lock(r->mutex);
         r->copying[slot] = 1;
-        r->copy_queue.push_back({slot, dptr, ready});
+        r->copy_queue.push_back({slot, dptr, ready, r->frames_queued++});
     }
     r->copy_wake.notify_one();
     return SFX_OK;
@@ -685,6 +752,7 @@ extern "C" int sfx_ring_read_async(sfx_handle h, sfx_handle tex, int slot) {
     Ring* r = get<Ring>(h, MAGIC_RING);
     Texture* t = get<Texture>(tex, MAGIC_TEX);
     if (!r || !t || slot < 0 || slot >= r->slots) return fail(SFX_E_INVALID, "invalid ring or texture handle, or slot");
+    if (r->sized) return fail(SFX_E_INVALID, "a sized ring reads sink frames, not textures");
     if (t->nbytes != r->frame_bytes) return fail(SFX_E_INVALID, "texture holds %zu bytes, ring slots %zu", t->nbytes, r->frame_bytes);
     USE_DEVICE(r->ctx);
     int rc = ring_wait_slot(r, slot);                               // the slot's last frame has left its staging buffer too

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 import tempfile
 import time
@@ -32,6 +33,7 @@ import numpy as np
 from attrs import Factory, define
 
 from shaderflow_amd import _native as N
+from shaderflow_amd import mjpeg
 from shaderflow_amd.module import logger
 
 if TYPE_CHECKING:
@@ -48,7 +50,7 @@ class ExportingHelper:
     took: Optional[float] = None
 
     # sink
-    kind: Optional[str] = None            # "path-raw", "path-ffmpeg", "pipe"
+    kind: Optional[str] = None            # "path-raw", "path-ffmpeg", "path-mjpeg", "pipe"
     path: Optional[Path] = None
     process: Optional[subprocess.Popen] = None
     file: Any = None
@@ -60,6 +62,13 @@ class ExportingHelper:
     `-pix_fmt yuv420p` rawvideo and the codec's own conversion falls away. Opt-in: `scene.main(pixel_format="yuv420p")`."""
     yuv_matrix: str = "bt601"
     _yuv_slots: list = Factory(list)      # device staging of the frame loop's converted frames, one per ring slot
+    jpeg_quality: int = 90
+    """`pixel_format="mjpeg"`: baseline JPEG frames encoded on the device (csrc/jpeg_kernels.hpp; mjpeg.py has the containers). The sink
+    frames are of fixed capacity on the device and say how long they are; a sized ring reads out exactly their payload. No ffmpeg process."""
+    container: Optional[str] = None       # of an mjpeg export to a path: "avi" or "raw" (mjpeg.container_of)
+    _encoder: Optional[N.JpegEncoder] = None
+    _avi: Optional[mjpeg.AviWriter] = None
+    _sizes: list = Factory(list)          # payload sizes of the mjpeg frames written, in order (the AVI index)
 
     # ring
     ring: Optional[N.Handle] = None
@@ -74,10 +83,37 @@ class ExportingHelper:
         return self.pixel_format == "yuv420p"
 
     @property
+    def mjpeg(self) -> bool:
+        return self.pixel_format == "mjpeg"
+
+    @property
+    def staged(self) -> bool:
+        """Sink frames are made from the RGB8 frames by a kernel: into a batch buffer, or a staging frame of the ring slot"""
+        return self.planar or self.mjpeg
+
+    @property
     def frame_bytes(self) -> int:
-        """Bytes of one frame as the sink receives it"""
+        """Bytes of one frame as the sink receives it (mjpeg: the fixed capacity of a sink frame on the device, its 64-byte header included)"""
         pixels = self.scene.width*self.scene.height
+        if self.mjpeg:
+            return N.JpegEncoder.SINK_HEADER + ((self.scene.width + 15)//16)*((self.scene.height + 15)//16)*768
         return pixels*3//2 if self.planar else pixels*3
+
+    @property
+    def encoder(self) -> N.JpegEncoder:
+        if self._encoder is None:
+            self._encoder = N.JpegEncoder(self.scene.context, self.scene.width, self.scene.height, self.jpeg_quality)
+        return self._encoder
+
+    def check(self, code: int) -> None:
+        """N.check of a ring call; a frame the encoder could not fit into its sink frame is said in the export's words"""
+        try:
+            N.check(code)
+        except N.NativeError as error:
+            found = re.search(r"frame (\d+) does not fit", str(error))
+            if self.mjpeg and error.code == N.E_TOO_LARGE and found:
+                raise RuntimeError(f"frame {found.group(1)} does not fit at quality {self.jpeg_quality}") from None
+            raise
 
     def to_yuv(self, rgb: int, yuv: int, frames: int = 1) -> None:
         self.scene.context.rgb_to_yuv420(rgb, yuv, self.scene.width, self.scene.height, frames, 1 if self.yuv_matrix == "bt709" else 0)
@@ -86,6 +122,8 @@ class ExportingHelper:
         """`frames` RGB8 frames on the device → sink frames at `target`, on the context's stream"""
         if self.planar:
             self.to_yuv(rgb, target, frames)
+        elif self.mjpeg:
+            self.encoder.encode(rgb, target, frames, bottom_up=not self.top_down)
         else:
             self.scene.context.copy(target, rgb, frames*self.frame_bytes)
 
@@ -112,8 +150,11 @@ class ExportingHelper:
 
     def ffmpeg_sizes(self, width: int, height: int) -> None:
         self.ffmpeg.time = self.scene.runtime
-        if self.pixel_format not in ("rgb24", "yuv420p"):
-            raise ValueError(f"pixel_format {self.pixel_format!r}: 'rgb24' (the reference's stream) or 'yuv420p' (converted on the device)")
+        if self.pixel_format not in ("rgb24", "yuv420p", "mjpeg"):
+            raise ValueError(f"pixel_format {self.pixel_format!r}: 'rgb24' (the reference's stream), 'yuv420p' (converted on the device) or 'mjpeg' (encoded on the device)")
+        if self.mjpeg:
+            mjpeg.check_quality(self.jpeg_quality)
+            return                                            # no encoder process: nothing to configure
         if self.planar and (self.scene.width % 2 or self.scene.height % 2):
             raise ValueError(f"yuv420p needs even extents, the scene is {self.scene.width}x{self.scene.height}")
         self.ffmpeg.pipe_input(pixel_format=self.pixel_format, width=self.scene.width, height=self.scene.height, framerate=self.scene.fps)
@@ -121,6 +162,17 @@ class ExportingHelper:
         self.ffmpeg.vflip()
 
     def ffmpeg_output(self, output) -> None:
+        if self.mjpeg:
+            if (output in ("pipe", "-", bytes)):
+                self.kind = "pipe"
+            else:
+                self.path = Path(output).expanduser().absolute()
+                self.container = mjpeg.container_of(self.path.suffix)
+                self.path.parent.mkdir(parents=True, exist_ok=True)
+                self.kind = "path-mjpeg"
+            if self.top_down is None:
+                self.top_down = False                         # the encoder reads the rows in the order it needs
+            return
         if (output in ("pipe", "-", bytes)):
             self.kind = "pipe"
             self.ffmpeg.pipe_output()
@@ -159,6 +211,12 @@ class ExportingHelper:
         elif self.kind == "path-raw":
             self.file = open(self.path, "wb")
             self.fileno = self.file.fileno()
+        elif self.kind == "path-mjpeg":
+            self.file = open(self.path, "wb", buffering=0)
+            self.fileno = self.file.fileno()
+            if self.container == "avi":
+                self._avi = mjpeg.AviWriter(self.fileno, self.scene.width, self.scene.height, self.scene.fps)
+                self._avi.begin()
         elif self.kind == "pipe":
             self.file = tempfile.TemporaryFile(mode="w+b")
             self.fileno = self.file.fileno()
@@ -168,19 +226,35 @@ class ExportingHelper:
     def make_buffers(self, n: int = 2) -> None:
         self.release_buffers()
         handle = N.Handle()
-        N.check(N.lib().sfx_ring_create(self.scene.context.handle, self.frame_bytes, max(1, n), C.byref(handle)))
+        if self.mjpeg:
+            N.check(N.lib().sfx_ring_create_sized(self.scene.context.handle, self.frame_bytes, max(1, n), 1 if self.container == "avi" else 0, C.byref(handle)))
+        else:
+            N.check(N.lib().sfx_ring_create(self.scene.context.handle, self.frame_bytes, max(1, n), C.byref(handle)))
         self.ring, self.slots = handle, max(1, n)
-        if self.planar:
+        if self.staged:
             self._yuv_slots = [self.scene.context.alloc(self.frame_bytes) for _ in range(self.slots)]
 
     def release_buffers(self) -> None:
-        if self.ring is not None and self.ring.value:
-            N.check(N.lib().sfx_ring_pipe_sync(self.ring, -1))
-            N.lib().sfx_ring_destroy(self.ring)
-        for pointer in self._yuv_slots:
-            self.scene.context.free(pointer)
-        self._yuv_slots = []
-        self.ring, self.slots = None, 0
+        try:
+            if self.ring is not None and self.ring.value:
+                self.check(N.lib().sfx_ring_pipe_sync(self.ring, -1))
+        finally:
+            if self.ring is not None and self.ring.value:
+                if self.mjpeg:
+                    N.lib().sfx_ring_pipe_sync(self.ring, -1)
+                    count = C.c_size_t()
+                    N.check(N.lib().sfx_ring_sizes(self.ring, None, 0, C.byref(count)))
+                    sizes = (C.c_uint32*max(1, count.value))()
+                    N.check(N.lib().sfx_ring_sizes(self.ring, sizes, count.value, C.byref(count)))
+                    self._sizes += list(sizes[:count.value])
+                N.lib().sfx_ring_destroy(self.ring)
+            for pointer in self._yuv_slots:
+                self.scene.context.free(pointer)
+            self._yuv_slots = []
+            self.ring, self.slots = None, 0
+            if self._encoder is not None:
+                self._encoder.destroy()
+                self._encoder = None
 
     def _check_encoder(self) -> None:
         if (self.process is not None) and (self.process.poll() is not None):
@@ -201,16 +275,16 @@ class ExportingHelper:
             return
         self._check_encoder()
         slot = self.frame % self.slots
-        if self.planar:
+        if self.staged:
             # the slot's last frame has left its staging buffer; then convert (on the render stream, in order with the draws) and read out
-            N.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
-            self.to_yuv(self.scene._final.texture.texture.device_ptr(), self._yuv_slots[slot])
-            N.check(N.lib().sfx_ring_read_device_async(self.ring, C.c_void_p(self._yuv_slots[slot]), slot))
+            self.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
+            self.to_sink(self.scene._final.texture.texture.device_ptr(), self._yuv_slots[slot])
+            self.check(N.lib().sfx_ring_read_device_async(self.ring, C.c_void_p(self._yuv_slots[slot]), slot))
         else:
             N.check(N.lib().sfx_ring_read_async(self.ring, self.scene._final.texture.texture.handle, slot))
         N.check(N.lib().sfx_ring_pipe(self.ring, slot, self.fileno))
         if not turbo:
-            N.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
+            self.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
 
     def fence(self, which: int) -> None:
         """Everything launched on the render stream so far is what frames read against fence `which` depend on"""
@@ -225,7 +299,7 @@ class ExportingHelper:
     def drain(self) -> None:
         """Every queued frame has left its device buffer and reached the sink (gathered buffers are reused right after)"""
         if self.ring is not None and self.ring.value:
-            N.check(N.lib().sfx_ring_pipe_sync(self.ring, -1))
+            self.check(N.lib().sfx_ring_pipe_sync(self.ring, -1))
 
     def pipe_device(self, device_ptr: int, *, rgb: bool, turbo: bool = True, fence: Optional[int] = None) -> None:
         """Same, for a frame in a raw device buffer: an RGB8 frame (`rgb`, converted here for a planar sink) or a sink frame"""
@@ -233,17 +307,17 @@ class ExportingHelper:
             return
         self._check_encoder()
         slot = self.frame % self.slots
-        if rgb and self.planar:
-            N.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
-            self.to_yuv(device_ptr, self._yuv_slots[slot])
+        if rgb and self.staged:
+            self.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
+            self.to_sink(device_ptr, self._yuv_slots[slot])
             device_ptr, fence = self._yuv_slots[slot], None
         if fence is None:
-            N.check(N.lib().sfx_ring_read_device_async(self.ring, C.c_void_p(device_ptr), slot))
+            self.check(N.lib().sfx_ring_read_device_async(self.ring, C.c_void_p(device_ptr), slot))
         else:
-            N.check(N.lib().sfx_ring_read_fenced_async(self.ring, C.c_void_p(device_ptr), slot, fence))
+            self.check(N.lib().sfx_ring_read_fenced_async(self.ring, C.c_void_p(device_ptr), slot, fence))
         N.check(N.lib().sfx_ring_pipe(self.ring, slot, self.fileno))
         if not turbo:
-            N.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
+            self.check(N.lib().sfx_ring_pipe_sync(self.ring, slot))
 
     def pipe_device_frames(self, device_ptr: int, stride: int, count: int, turbo: bool = True, fence: Optional[int] = None) -> None:
         """`count` consecutive SINK frames of a batch in one native call (the per-frame python loop costs more than the frames themselves
@@ -254,7 +328,7 @@ class ExportingHelper:
                 self.update()
             return
         self._check_encoder()
-        N.check(N.lib().sfx_ring_pipe_frames(self.ring, C.c_void_p(device_ptr), stride, count, self.frame % self.slots, -1 if fence is None else fence, self.fileno))
+        self.check(N.lib().sfx_ring_pipe_frames(self.ring, C.c_void_p(device_ptr), stride, count, self.frame % self.slots, -1 if fence is None else fence, self.fileno))
         self.frame += count
 
     # finish ---------------------------------------------------------------------------------------------------------
@@ -262,9 +336,23 @@ class ExportingHelper:
     def finish(self):
         output = None
         self.scene.context.synchronize()
-        self.release_buffers()
-        self.scene.context.output_top_down(False)
-        if self.process is not None:
+        try:
+            self.release_buffers()
+        except BaseException:
+            if self.file is not None:                         # (an mjpeg frame that did not fit: the sink is closed as far as it got)
+                self.file.close()
+            raise
+        finally:
+            self.scene.context.output_top_down(False)
+        if self.kind == "path-mjpeg":
+            output = self.path
+            if self.file is not None:
+                try:
+                    if self._avi is not None:
+                        self._avi.finish(self._sizes)
+                finally:
+                    self.file.close()
+        elif self.process is not None:
             self.process.stdin.close()
             if self.process.wait() != 0:                      # the reference only waits (exporting.py:186-187); say what went wrong
                 logger.error(f"FFmpeg exited with status {self.process.returncode}:\n" + self.encoder_output())
@@ -291,7 +379,7 @@ class ExportingHelper:
 
 class SinkBatches:
     """`count` device buffers of `batch` sink frames, and the rule that fills them: a batch is rendered straight into place as rgb24, or
-    into one RGB8 scratch of a batch and converted right behind as yuv420p — both on the context's stream, so one scratch serves every
+    into one RGB8 scratch of a batch and converted right behind as yuv420p or mjpeg — both on the context's stream, so one scratch serves every
     buffer (allocated by the first batch rendered through it)."""
 
     def __init__(self, export: ExportingHelper, batch: int, count: int = 2):
@@ -305,13 +393,13 @@ class SinkBatches:
         """`draw(count, pointer)` renders `count` RGB8 frames at `pointer`; they end up as sink frames at `target`"""
         assert 0 < count <= self.batch, (count, self.batch)
         rgb = target
-        if self.export.planar:
+        if self.export.staged:
             if self.scratch is None:
                 self.scratch = self.context.alloc(self.rgb_bytes*self.batch)
             rgb = self.scratch
         draw(count, rgb)
         if rgb != target:
-            self.export.to_yuv(rgb, target, count)
+            self.export.to_sink(rgb, target, count)
         self.last_rgb = rgb + (count - 1)*self.rgb_bytes
 
     def close(self) -> None:

@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""The 4K 2xSSAA Visualizer export to /dev/null, 1 800 frames, as rgb24, yuv420p and mjpeg (quality 90 and 75): frames/s, mean bytes per
+frame, and — from `rocprofv3 --kernel-trace --stats` over a short mjpeg export in a process of its own — the three JPEG kernels' times.
+Writes profiles/mjpeg_bench.txt. GPU box only.
+
+    python tools/bench_mjpeg.py [--frames 1800] [--no-profile]
+"""
+import argparse
+import csv
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+W, H, SSAA, FPS = 3840, 2160, 2.0, 60.0
+
+
+def visualizer():
+    from examples.scenes import Visualizer, make
+    from shaderflow_amd import synth
+    return make(Visualizer, audio=(synth.sweep_clip(32.0, 44100), 44100), background=synth.background_image(1920, 1080, seed=0))
+
+
+def export(pixel_format: str, quality: int, frames: int, output) -> tuple[float, object]:
+    started = time.perf_counter()
+    result = visualizer().main(width=W, height=H, ssaa=SSAA, fps=FPS, time=frames/FPS, output=output, pixel_format=pixel_format, jpeg_quality=quality)
+    return time.perf_counter() - started, result
+
+
+def kernel_times(quality: int, frames: int) -> list[str]:
+    """rocprofv3's per-kernel statistics of a short mjpeg export in a fresh process: the lines of the JPEG kernels"""
+    rocprof = shutil.which("rocprofv3")
+    if rocprof is None:
+        return ["rocprofv3 not found: no kernel times"]
+    with tempfile.TemporaryDirectory() as directory:
+        command = [rocprof, "--kernel-trace", "--stats", "-d", directory, "-o", "mjpeg", "--output-format", "csv", "--",
+                   sys.executable, str(Path(__file__).resolve()), "--child", str(quality), "--frames", str(frames)]
+        done = subprocess.run(command, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        if done.returncode != 0:
+            return [f"rocprofv3 run failed ({done.returncode}): {done.stderr.strip()[-300:]}"]
+        lines = []
+        for path in Path(directory).rglob("*kernel_stats.csv"):
+            with open(path, newline="") as file:
+                for row in csv.DictReader(file):
+                    if "k_jpeg_" in row.get("Name", ""):
+                        name = row["Name"].split("(")[0].split("::")[-1]
+                        lines.append(f"  {name:22s} {int(row['Calls']):5d} calls, {float(row['TotalDurationNs'])/1e3/frames:8.1f} us per frame, "
+                                     f"{float(row['AverageNs'])/1e3:9.1f} us per call, {float(row['Percentage']):5.2f} % of the kernel time")
+        return lines or ["no k_jpeg_* rows in rocprofv3's kernel statistics"]
+
+
+def main() -> None:
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--frames", type=int, default=1800)
+    parser.add_argument("--child", type=int, default=None, help="(internal) one mjpeg export at this quality, nothing else")
+    parser.add_argument("--no-profile", action="store_true")
+    args = parser.parse_args()
+    if args.child is not None:
+        with tempfile.TemporaryDirectory() as directory:
+            os.symlink("/dev/null", Path(directory)/"null.mjpeg")
+            export("mjpeg", args.child, args.frames, Path(directory)/"null.mjpeg")
+        return
+    from shaderflow_amd import _native as N
+    lines = [f"4K 2xSSAA Visualizer export to /dev/null, {args.frames} frames (second of two runs each), kernel sources {N.source_fingerprint()}",
+             f"rgb24 frame: {W*H*3} bytes; yuv420p: {W*H*3//2}"]
+    with tempfile.TemporaryDirectory() as directory:
+        null = Path(directory)/"null.mjpeg"
+        os.symlink("/dev/null", null)
+        for pixel_format, quality in (("rgb24", 0), ("yuv420p", 0), ("mjpeg", 90), ("mjpeg", 75)):
+            for attempt in range(2):
+                took, _ = export(pixel_format, quality or 90, args.frames, null if pixel_format == "mjpeg" else "/dev/null")
+            line = f"{pixel_format:8s}{f' q{quality}' if quality else '    '}: {args.frames} frames in {took:7.3f} s = {args.frames/took:7.0f} frames/s"
+            if pixel_format == "mjpeg":
+                _, stream = export(pixel_format, quality, 60, "pipe")
+                line += f", mean {len(stream)/60:9.0f} bytes per frame over the first 60 ({W*H*3/(len(stream)/60):.1f} x smaller than rgb24)"
+            lines.append(line)
+            print(line, flush=True)
+    if not args.no_profile:
+        for quality in (90, 75):
+            lines.append(f"rocprofv3 --kernel-trace --stats, mjpeg q{quality}, 120 frames, a process of its own:")
+            lines += kernel_times(quality, 120)
+    (ROOT/"profiles").mkdir(exist_ok=True)
+    (ROOT/"profiles"/"mjpeg_bench.txt").write_text("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
