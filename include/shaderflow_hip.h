@@ -410,7 +410,8 @@ int sfx_piano_destroy(sfx_handle piano);
  * R = clip8((298 C + 409 E + 128) >> 8), G = clip8((298 C - 100 D - 208 E + 128) >> 8), B = clip8((298 C + 516 D + 128) >> 8), chroma
  * replicated over its 2 x 2 block. The counterpart of sfx_rgb_to_yuv420 and, like it, defined by this project: unpinned against swscale. */
 enum { SFX_VIDEO_RGB24 = 0 /* height x width x 3 bytes, top row first; any extents */,
-       SFX_VIDEO_I420 = 1  /* Y (height x width), U, V (height/2 x width/2), top row first; even extents */ };
+       SFX_VIDEO_I420 = 1  /* Y (height x width), U, V (height/2 x width/2), top row first; even extents */,
+       SFX_VIDEO_MJPEG = 2 /* a staged baseline JPEG frame of its own length (csrc/jpeg_decode_kernels.hpp): sfx_video_create_mjpeg */ };
 /* video.py:57-66. `boxes`: the `temporal` texture handles of the video's texture matrix in its current order (layers must be 1; RGB8,
  * width x height). The handle owns `slots` pinned host frames, `slots` device staging frames, one event per slot and one copy stream
  * beside the context's stream. */
@@ -425,6 +426,30 @@ int sfx_video_submit(sfx_handle video, int slot);
  * waits for the slot's event, the handle's own copy of the matrix rolls by one, k_video_frame writes the box now at the front, and the
  * slot is marked free behind the kernel. SFX_E_INVALID when the slot holds no submitted frame. */
 int sfx_video_step(sfx_handle video, int slot);
+/* Motion-JPEG sources (no reference counterpart: the reference pipes every container through ffmpeg). The frames are decoded where the
+ * texture lives: csrc/jpeg_decode_kernels.hpp defines the decode — baseline, 8 bit, one interleaved scan, YCbCr with luma sampling
+ * `h_sampling` x `v_sampling` of 2x2, 2x1 or 1x1 (or `components` = 1: grey), the triangle filter for subsampled chroma, full-range
+ * 16-bit fixed-point colour — and the layout of a staged frame (tables, the restart intervals' starts, the scan), which the host
+ * builds from a stream's header (shaderflow_amd/mjpegsource.py). A slot holds at most `capacity` bytes. Everything else is
+ * sfx_video_create's; sfx_video_step and a landing frame of sfx_sequence_run launch the decode kernels instead of k_video_frame —
+ * the same event hand-over, the same roll. sfx_video_create itself keeps refusing format 2: the geometry it takes does not say enough. */
+int sfx_video_create_mjpeg(sfx_handle ctx, const sfx_handle* boxes, int temporal, int width, int height, int components, int h_sampling, int v_sampling,
+                           size_t capacity, int slots, sfx_handle* video);
+/* sfx_video_submit for a frame of `nbytes` bytes: only they are copied. A Motion-JPEG frame's words are validated here (magic, interval
+ * count against the geometry, the scan inside the frame, table selectors): SFX_E_INVALID names what is wrong. For the uncompressed
+ * formats `nbytes` must be the frame's size. */
+int sfx_video_submit_bytes(sfx_handle video, int slot, size_t nbytes);
+/* The first landed Motion-JPEG frame since the last call whose entropy-coded data was bad: `frame` = how many frames the handle had
+ * landed before it (-1: none was bad), `status` = its bits: 1 a code that matches nothing, 2 a run past 63, 4 a missing or wrong RSTn,
+ * 8 bits running out, 16 a descriptor the kernels refuse. Such a frame is not drawn: the texture it would have been written into keeps
+ * its content. `wait` non-zero: waits for the context's stream first (else only frames whose kernels have run are seen). */
+int sfx_video_status(sfx_handle video, int wait, int64_t* frame, uint32_t* status);
+/* Test entry, in the spirit of sfx_jpeg_coefficients: one staged frame from host memory through the three decode kernels. Any of the
+ * outputs may be null: `coefficients` mcus x blocks per MCU x 64 int16 in zigzag order (the encoder's layout), `planes` the components'
+ * 8-bit planes before upsampling, padded to whole MCUs (Y: mcus_x*h*8 wide; then Cb, Cr: mcus_x*8 wide), `rgb` height x width x 3,
+ * top row first. Synchronous. */
+int sfx_jpeg_decode(sfx_handle ctx, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling,
+                    int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status);
 /* video.py:57-66 has no counterpart: stops the copy stream, then frees the staging */
 int sfx_video_destroy(sfx_handle video);
 

@@ -67,7 +67,7 @@ class ClockTick(C.Structure):
 
 
 PASS_LAYERS, PASS_FUSED, PASS_RESOLVE = 0, 1, 2
-VIDEO_RGB24, VIDEO_I420 = 0, 1
+VIDEO_RGB24, VIDEO_I420, VIDEO_MJPEG = 0, 1, 2
 
 
 class PianoParams(C.Structure):
@@ -211,6 +211,10 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_video_submit": (C.c_int, [Handle, C.c_int]),
     "sfx_video_step": (C.c_int, [Handle, C.c_int]),
     "sfx_video_destroy": (C.c_int, [Handle]),
+    "sfx_video_create_mjpeg": (C.c_int, [Handle, P(Handle), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, P(Handle)]),
+    "sfx_video_submit_bytes": (C.c_int, [Handle, C.c_int, C.c_size_t]),
+    "sfx_video_status": (C.c_int, [Handle, C.c_int, P(C.c_int64), P(C.c_uint32)]),
+    "sfx_jpeg_decode": (C.c_int, [Handle, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32)]),
     "sfx_sequence_run": (C.c_int, [Handle, P(Sequence)]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),
     "sfx_device_free": (C.c_int, [Handle, C.c_void_p]),

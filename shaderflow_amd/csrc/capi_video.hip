@@ -12,8 +12,10 @@
 
 #include "host_state.hpp"
 #include "video_kernels.hpp"
+#include "jpeg_decode_kernels.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 
 using namespace sf;
@@ -28,6 +30,14 @@ struct Video : Object {
     std::vector<hipEvent_t> events;
     std::vector<int> state;                 // per slot: SLOT_*
     std::mutex guard;
+    // SFX_VIDEO_MJPEG: every slot holds a staged frame of its own length (jpeg_decode_kernels.hpp), at most frame_bytes of them
+    JpegDecodeGeometry jpeg{};
+    std::vector<uint32_t> intervals;        // restart intervals of the frame each slot holds
+    void* staging_block = nullptr;          // the slots' device staging as one allocation (`staging` holds views into it)
+    void* scratch = nullptr;                // [basis 64 f32][status: a word per slot][coefficients][planes]: the decode kernels run in stream order, one frame's scratch serves all slots
+    float* basis = nullptr; uint32_t* status = nullptr; int16_t* coefficients = nullptr; uint8_t* planes = nullptr;
+    uint32_t* first_bad = nullptr;          // pinned: {status, serial} of the first landed frame with a bad status since sfx_video_status last asked
+    uint32_t serial = 0;                    // frames landed so far
 };
 enum { SLOT_NEW = 0, SLOT_SUBMITTED = 1, SLOT_CONSUMED = 2 };
 
@@ -43,7 +53,10 @@ static void video_release(Video* v) {
     hipStreamSynchronize(v->ctx->stream);
     for (auto e : v->events) if (e) hipEventDestroy(e);
     for (auto p : v->host) if (p) hipHostFree(p);
-    for (auto p : v->staging) if (p) hipFree(p);
+    if (v->staging_block) hipFree(v->staging_block);
+    else for (auto p : v->staging) if (p) hipFree(p);
+    if (v->scratch) hipFree(v->scratch);
+    if (v->first_bad) hipHostFree(v->first_bad);
     if (v->copy) hipStreamDestroy(v->copy);
     v->magic = 0;
     delete v;
@@ -91,17 +104,72 @@ extern "C" int sfx_video_slot(sfx_handle h, int slot, void** host, size_t* nbyte
     return SFX_OK;
 }
 
-extern "C" int sfx_video_submit(sfx_handle h, int slot) {
-    Video* v = get<Video>(h, MAGIC_VIDEO);
-    if (!v || slot < 0 || slot >= v->slots) return fail(SFX_E_INVALID, "invalid video handle or slot %d", slot);
+// why a staged Motion-JPEG frame of `nbytes` bytes is not one the kernels may be given (null: it is)
+static const char* jpeg_frame_fault(const uint8_t* frame, size_t nbytes, const JpegDecodeGeometry& g) {
+    if (nbytes < (size_t)JPEG_FRAME_FIXED || nbytes > (size_t)g.capacity) return "its length is outside the fixed part … the slot's capacity";
+    uint32_t words[6];
+    memcpy(words, frame, sizeof words);
+    const unsigned long long total = (unsigned long long)g.mcus_x*g.mcus_y, scan_bytes = words[1], restart = words[2], intervals = words[3], scan_offset = words[4];
+    if (words[0] != JPEG_FRAME_MAGIC) return "no SFJD magic";
+    if (restart < 1 || intervals != (total + restart - 1)/restart) return "the interval count does not follow from the restart interval and the geometry";
+    if (scan_offset != (unsigned long long)JPEG_FRAME_FIXED + jpeg_interval_table_bytes((uint32_t)intervals) || scan_offset + scan_bytes > nbytes) return "the scan does not lie behind the interval table and inside the frame";
+    if ((int)words[5] != g.components) return "another component count than the video's";
+    for (int c = 0; c < g.components; c++)
+        if (frame[JPEG_FRAME_TQ + c] > 3 || frame[JPEG_FRAME_TD + c] > 1 || frame[JPEG_FRAME_TA + c] > 1) return "a table selector outside 0…3 (quantisation) or 0…1 (Huffman)";
+    for (int t = 0; t < 4; t++) {
+        int count = 0;
+        for (int k = 0; k < 16; k++) count += frame[JPEG_FRAME_HUFFMAN + t*JPEG_HUFFMAN_BYTES + k];
+        if (count > 256) return "a Huffman table with more than 256 codes";
+    }
+    return nullptr;
+}
+
+// `staged`: the frame's length is its own (SFX_VIDEO_MJPEG): it is checked, and its interval count kept, once the slot is known to be the host's
+static int video_submit(Video* v, int slot, size_t nbytes, bool staged = false) {
     std::lock_guard<std::mutex> lock(v->guard);
     if (v->state[slot] == SLOT_SUBMITTED) return fail(SFX_E_INVALID, "video: slot %d holds a submitted frame that was not consumed yet", slot);
+    if (staged) {
+        if (const char* fault = jpeg_frame_fault((const uint8_t*)v->host[slot], nbytes, v->jpeg)) return fail(SFX_E_INVALID, "video: the staged Motion-JPEG frame of %zu bytes in slot %d: %s", nbytes, slot, fault);
+        memcpy(&v->intervals[slot], (const uint8_t*)v->host[slot] + 12, sizeof(uint32_t));
+        nbytes = (nbytes + 15) & ~(size_t)15;
+    }
     USE_DEVICE(v->ctx);
     if (v->state[slot] == SLOT_CONSUMED) HIP_TRY(hipStreamWaitEvent(v->copy, v->events[slot], 0));      // the staging frame is still the last kernel's
-    HIP_TRY(hipMemcpyAsync(v->staging[slot], v->host[slot], v->frame_bytes, hipMemcpyHostToDevice, v->copy));
+    HIP_TRY(hipMemcpyAsync(v->staging[slot], v->host[slot], nbytes, hipMemcpyHostToDevice, v->copy));
     HIP_TRY(hipEventRecord(v->events[slot], v->copy));
     v->state[slot] = SLOT_SUBMITTED;
     return SFX_OK;
+}
+
+extern "C" int sfx_video_submit(sfx_handle h, int slot) {
+    Video* v = get<Video>(h, MAGIC_VIDEO);
+    if (!v || slot < 0 || slot >= v->slots) return fail(SFX_E_INVALID, "invalid video handle or slot %d", slot);
+    if (v->format == SFX_VIDEO_MJPEG) return fail(SFX_E_INVALID, "video: a Motion-JPEG frame has a length of its own: sfx_video_submit_bytes");
+    return video_submit(v, slot, v->frame_bytes);
+}
+
+extern "C" int sfx_video_submit_bytes(sfx_handle h, int slot, size_t nbytes) {
+    Video* v = get<Video>(h, MAGIC_VIDEO);
+    if (!v || slot < 0 || slot >= v->slots) return fail(SFX_E_INVALID, "invalid video handle or slot %d", slot);
+    if (v->format != SFX_VIDEO_MJPEG) {
+        if (nbytes != v->frame_bytes) return fail(SFX_E_INVALID, "video: a frame of this format has %zu bytes, not %zu", v->frame_bytes, nbytes);
+        return video_submit(v, slot, nbytes);
+    }
+    return video_submit(v, slot, nbytes, true);
+}
+
+// The three decode launches of one staged frame (jpeg_decode_kernels.hpp) on `stream`: `frame` with `intervals` restart intervals (a lane
+// each) → `rgb`. `status` is the frame's status word, cleared in front of them. The launches run in stream order, so one frame's
+// coefficients and planes serve every frame.
+static void jpeg_launch_decode(hipStream_t stream, const uint8_t* frame, uint32_t intervals, int16_t* coefficients, uint8_t* planes, const float* basis, uint32_t* status,
+                               uint32_t* first_bad, uint32_t serial, uint8_t* rgb, const JpegDecodeGeometry& g, int bottom_up) {
+    hipMemsetAsync(status, 0, sizeof(uint32_t), stream);
+    hipLaunchKernelGGL(k_jpeg_decode_entropy, dim3((intervals + 63)/64), dim3(64), 0, stream, frame, coefficients, status, g);
+    const size_t blocks = (size_t)g.mcus_x*g.mcus_y*g.blocks;
+    hipLaunchKernelGGL(k_jpeg_decode_planes, dim3((unsigned)((blocks + 3)/4)), dim3(256), 0, stream, frame, (const int16_t*)coefficients, planes, basis, (const uint32_t*)status,
+                       (volatile uint32_t*)first_bad, serial, g);
+    const long lanes = jpeg_pixel_lanes(g.width, g.height);
+    hipLaunchKernelGGL(k_jpeg_decode_pixels, dim3((unsigned)((lanes + 255)/256)), dim3(256), 0, stream, (const uint8_t*)planes, rgb, (const uint32_t*)status, g, bottom_up);
 }
 
 // One landing frame on the context's render stream, in stream order with the draws behind it
@@ -121,7 +189,10 @@ int video_launch_frame(sfx_handle h, Context* c, int slot) {
     std::rotate(v->boxes.begin(), v->boxes.end() - 1, v->boxes.end());
     const long lanes = video_frame_lanes(v->format, v->width, v->height);
     const dim3 grid((unsigned)((lanes + VIDEO_THREADS - 1)/VIDEO_THREADS)), block(VIDEO_THREADS);
-    if (v->format == SFX_VIDEO_I420) hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_I420>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
+    if (v->format == SFX_VIDEO_MJPEG) {
+        jpeg_launch_decode(v->ctx->stream, (const uint8_t*)v->staging[slot], v->intervals[slot], v->coefficients, v->planes, v->basis, v->status + slot,
+                           v->first_bad, v->serial++, (uint8_t*)front->data, v->jpeg, 1);
+    } else if (v->format == SFX_VIDEO_I420) hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_I420>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     else hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_RGB24>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     const int rc = launch_status();
     if (rc) return rc;
@@ -152,4 +223,118 @@ extern "C" int sfx_video_destroy(sfx_handle h) {
     if (!v) return fail(SFX_E_INVALID, "invalid video handle");
     video_release(v);
     return SFX_OK;
+}
+
+// ---- Motion-JPEG sources ---------------------------------------------------------------------------------------------------------------
+
+static int jpeg_decode_geometry(int width, int height, int components, int hs, int vs, size_t capacity, JpegDecodeGeometry* g) {
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(SFX_E_INVALID, "jpeg decode: %d x %d (extents 1…65535)", width, height);
+    if (components != 1 && components != 3) return fail(SFX_E_INVALID, "jpeg decode: %d components (1: grey, 3: YCbCr)", components);
+    if (components == 1) hs = vs = 1;
+    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return fail(SFX_E_INVALID, "jpeg decode: luma sampling %d x %d (2x2, 2x1 or 1x1)", hs, vs);
+    if (capacity < (size_t)JPEG_FRAME_FIXED + 16 || capacity > ((size_t)1 << 30)) return fail(SFX_E_INVALID, "jpeg decode: a staged frame of at most %zu bytes (%d … 2^30)", capacity, JPEG_FRAME_FIXED + 16);
+    g->width = width; g->height = height; g->components = components; g->hs = hs; g->vs = vs;
+    g->mcus_x = (width + 8*hs - 1)/(8*hs); g->mcus_y = (height + 8*vs - 1)/(8*vs); g->blocks = components == 1 ? 1 : hs*vs + 2;
+    g->capacity = (int)((capacity + 15) & ~(size_t)15);
+    return SFX_OK;
+}
+
+static void jpeg_basis(float* dct) {                                 // the encoder's (capi_jpeg.hip)
+    for (int u = 0; u < 8; u++)
+        for (int x = 0; x < 8; x++) dct[u*8 + x] = (float)((u == 0 ? std::sqrt(0.125) : 0.5)*std::cos((2*x + 1)*u*M_PI/16.0));
+}
+
+// [basis 64 f32][status words, 64 bytes' worth at least][coefficients][planes], each part 256-byte aligned
+static int jpeg_scratch(const JpegDecodeGeometry& g, int slots, void** scratch, float** basis, uint32_t** status, int16_t** coefficients, uint8_t** planes) {
+    const size_t status_bytes = ((size_t)slots*4 + 255) & ~(size_t)255, coefficient_bytes = (jpeg_decode_coefficients(g)*2 + 255) & ~(size_t)255;
+    if (hipMalloc(scratch, 256 + status_bytes + coefficient_bytes + jpeg_plane_bytes(g)) != hipSuccess) { (void)hipGetLastError(); *scratch = nullptr; return SFX_E_HIP; }
+    char* base = (char*)*scratch;
+    *basis = (float*)base; *status = (uint32_t*)(base + 256); *coefficients = (int16_t*)(base + 256 + status_bytes); *planes = (uint8_t*)(base + 256 + status_bytes + coefficient_bytes);
+    float dct[64];
+    jpeg_basis(dct);
+    if (hipMemcpy(*basis, dct, sizeof dct, hipMemcpyHostToDevice) != hipSuccess || hipMemset(*status, 0, status_bytes) != hipSuccess) { (void)hipGetLastError(); hipFree(*scratch); *scratch = nullptr; return SFX_E_HIP; }
+    return SFX_OK;
+}
+
+extern "C" int sfx_video_create_mjpeg(sfx_handle hc, const sfx_handle* boxes, int temporal, int width, int height, int components, int h_sampling, int v_sampling,
+                                      size_t capacity, int slots, sfx_handle* out) {
+    CTX_OR_FAIL(c, hc);
+    if (!boxes || !out || temporal < 1 || slots < 1 || slots > 256) return fail(SFX_E_INVALID, "video: null boxes or output, temporal %d, %d slots (1…256)", temporal, slots);
+    JpegDecodeGeometry g;
+    if (const int rc = jpeg_decode_geometry(width, height, components, h_sampling, v_sampling, capacity, &g)) return rc;
+    USE_DEVICE(c);
+    Video* v = new Video();
+    v->magic = MAGIC_VIDEO; v->ctx = c; v->temporal = temporal; v->width = width; v->height = height; v->format = SFX_VIDEO_MJPEG; v->slots = slots;
+    v->jpeg = g; v->frame_bytes = (size_t)g.capacity;
+    v->boxes.assign(boxes, boxes + temporal);
+    for (int d = 0; d < temporal; d++)
+        if (!video_texture(v->boxes[d], v)) { delete v; return fail(SFX_E_INVALID, "video: box %d is not a %d x %d RGB8 texture of this context (layers must be 1)", d, width, height); }
+    v->host.assign(slots, nullptr); v->staging.assign(slots, nullptr); v->events.assign(slots, nullptr); v->state.assign(slots, SLOT_NEW); v->intervals.assign(slots, 0);
+    bool ok = hipStreamCreateWithFlags(&v->copy, hipStreamNonBlocking) == hipSuccess && hipMalloc(&v->staging_block, v->frame_bytes*slots) == hipSuccess
+              && hipHostMalloc((void**)&v->first_bad, 64, hipHostMallocDefault) == hipSuccess
+              && jpeg_scratch(g, slots, &v->scratch, &v->basis, &v->status, &v->coefficients, &v->planes) == SFX_OK;
+    for (int k = 0; ok && k < slots; k++) {
+        v->staging[k] = (char*)v->staging_block + (size_t)k*v->frame_bytes;
+        ok = hipHostMalloc(&v->host[k], v->frame_bytes, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&v->events[k], hipEventDisableTiming) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        video_release(v);
+        return fail(SFX_E_HIP, "video: %d staging frames of %zu bytes (pinned and device) and the decoder's scratch could not be allocated", slots, (size_t)g.capacity);
+    }
+    memset(v->first_bad, 0, 64);
+    *out = handle_of(v);
+    return SFX_OK;
+}
+
+extern "C" int sfx_video_status(sfx_handle h, int wait, int64_t* frame, uint32_t* status) {
+    Video* v = get<Video>(h, MAGIC_VIDEO);
+    if (!v || !frame || !status) return fail(SFX_E_INVALID, "invalid video handle or null pointer");
+    *frame = -1; *status = 0;
+    if (v->format != SFX_VIDEO_MJPEG) return SFX_OK;                  // (uncompressed frames have nothing to go wrong)
+    volatile uint32_t* note = v->first_bad;
+    if (!wait && note[0] == 0u) return SFX_OK;
+    USE_DEVICE(v->ctx);
+    HIP_TRY(hipStreamSynchronize(v->ctx->stream));
+    if (note[0] != 0u) { *status = note[0]; *frame = (int64_t)note[1]; note[1] = 0u; note[0] = 0u; }
+    return SFX_OK;
+}
+
+extern "C" int sfx_jpeg_decode(sfx_handle hc, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling,
+                               int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status) {
+    CTX_OR_FAIL(c, hc);
+    if (!staged || !status) return fail(SFX_E_INVALID, "jpeg decode: null frame or status");
+    JpegDecodeGeometry g;
+    if (const int rc = jpeg_decode_geometry(width, height, components, h_sampling, v_sampling, std::max(nbytes, (size_t)JPEG_FRAME_FIXED + 16), &g)) return rc;
+    if (const char* fault = jpeg_frame_fault((const uint8_t*)staged, nbytes, g)) return fail(SFX_E_INVALID, "jpeg decode: the staged frame of %zu bytes: %s", nbytes, fault);
+    USE_DEVICE(c);
+    void *scratch = nullptr, *frame = nullptr, *pixels = nullptr;
+    float* basis; uint32_t* device_status; int16_t* device_coefficients; uint8_t* device_planes;
+    const size_t rgb_bytes = (size_t)width*height*3;
+    int rc = jpeg_scratch(g, 1, &scratch, &basis, &device_status, &device_coefficients, &device_planes);
+    if (rc == SFX_OK && (hipMalloc(&frame, (size_t)g.capacity) != hipSuccess || hipMalloc(&pixels, rgb_bytes) != hipSuccess)) rc = SFX_E_HIP;
+    if (rc == SFX_OK) {
+        uint32_t intervals;
+        memcpy(&intervals, (const uint8_t*)staged + 12, sizeof intervals);
+        bool ok = hipMemsetAsync(frame, 0, (size_t)g.capacity, c->stream) == hipSuccess && hipMemsetAsync(pixels, 0, rgb_bytes, c->stream) == hipSuccess
+                  && hipMemsetAsync(device_coefficients, 0, (size_t)(device_planes - (uint8_t*)device_coefficients) + jpeg_plane_bytes(g), c->stream) == hipSuccess
+                  && hipMemcpyAsync(frame, staged, nbytes, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+        if (ok) {
+            jpeg_launch_decode(c->stream, (const uint8_t*)frame, intervals, device_coefficients, device_planes, basis, device_status, nullptr, 0, (uint8_t*)pixels, g, 0);
+            ok = hipGetLastError() == hipSuccess;
+        }
+        if (ok && coefficients) ok = hipMemcpyAsync(coefficients, device_coefficients, jpeg_decode_coefficients(g)*2, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (ok && planes) ok = hipMemcpyAsync(planes, device_planes, jpeg_plane_bytes(g), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (ok && rgb) ok = hipMemcpyAsync(rgb, pixels, rgb_bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(status, device_status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        const hipError_t synced = hipStreamSynchronize(c->stream);
+        if (!ok || synced != hipSuccess) rc = fail(SFX_E_HIP, "jpeg decode: %s", hipGetErrorString(synced != hipSuccess ? synced : hipGetLastError()));
+    } else {
+        (void)hipGetLastError();
+        fail(SFX_E_HIP, "jpeg decode: the scratch of a %d x %d frame could not be allocated", width, height);
+    }
+    if (scratch) hipFree(scratch);
+    if (frame) hipFree(frame);
+    if (pixels) hipFree(pixels);
+    return rc;
 }

@@ -15,7 +15,14 @@ Where frames come from: the reference pipes the file through an `ffmpeg` subproc
     chroma layout, a higher bit depth, interlacing or `XCOLORRANGE=FULL` raise ValueError naming the tag;
   * `path=` a raw `.yuv` / `.i420` file with `width`, `height` and `fps` given: planar 4:2:0 frames, what this package's own
     yuv420p export writes (exporting.py);
-  * any other `path` is decoded by an `ffmpeg` binary on PATH when there is one (rawvideo rgb24 over a pipe),
+  * `path=` an `.avi` file with a Motion-JPEG video stream (fourcc `MJPG`: what `pixel_format="mjpeg"` exports, and what many cameras
+    and editors write) or a bare `.mjpeg` / `.mjpg` stream (JPEG images back to back; `fps=` given), read natively (mjpegsource.py):
+    the frames stay compressed in pinned memory and over the link — a quality-90 4K frame is about 665 KB against 24.9 MB of rgb24 —
+    and are decoded on the device into the texture (csrc/jpeg_decode_kernels.hpp: baseline, 8 bit, one interleaved scan, 4:2:0 /
+    4:2:2 / 4:4:4 / grey; anything else raises ValueError naming the marker or field). With `format="mjpeg"`, `frames=` yields such
+    streams as `bytes`. A frame whose entropy-coded data is damaged raises RuntimeError naming the source frame; it is not drawn. A
+    stream without restart markers decodes correctly but serially (one lane per frame): entropy decoding on the host is out of scope;
+  * any other `path` (an `.avi` with another codec included) is decoded by an `ffmpeg` binary on PATH when there is one (rawvideo rgb24 over a pipe),
     otherwise construction raises — there is no silent fallback.
 A source shorter than the scene keeps its last frame on screen (the reference's generator would raise
 StopIteration out of `update`).
@@ -42,6 +49,7 @@ from shaderflow_amd import _native as N
 from shaderflow_amd.module import ShaderModule, logger
 from shaderflow_amd.texture import ShaderTexture
 
+MJPEG_SUFFIXES = (".mjpeg", ".mjpg")
 Y4M_CHROMA = ("420", "420jpeg", "420mpeg2", "420paldv")              # all read as the same 8-bit 4:2:0 bytes (the siting is not interpolated)
 PLANAR_SUFFIXES = (".yuv", ".i420")                                   # raw planar frames: the suffixes exporting.py's yuv420p sink writes
 
@@ -164,9 +172,14 @@ class VideoStage:
             raise ValueError("a staged video needs an RGB8 texture with layers = 1")
         boxes = [box.texture for (_, _, box) in texture.boxes]
         self.serials = tuple(box.serial for box in boxes)              # which device textures the handle writes into
-        self.planar = video.format == "i420"
+        self.planar, self.compressed = video.format == "i420", video.format == "mjpeg"
         self.slots, self.handle = slots, N.Handle()
         handles = (N.Handle*len(boxes))(*[box.handle for box in boxes])
+        if self.compressed:
+            jpeg = video.jpeg
+            N.check(N.lib().sfx_video_create_mjpeg(video.scene.context.handle, handles, texture.temporal, video.width, video.height, jpeg.components,
+                                                   jpeg.sampling[0], jpeg.sampling[1], video.capacity, slots, C.byref(self.handle)))
+            return
         N.check(N.lib().sfx_video_create(video.scene.context.handle, handles, texture.temporal, video.width, video.height,
                                          N.VIDEO_I420 if self.planar else N.VIDEO_RGB24, slots, C.byref(self.handle)))
 
@@ -176,8 +189,19 @@ class VideoStage:
         N.check(N.lib().sfx_video_slot(self.handle, slot, C.byref(pointer), C.byref(nbytes)))
         return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(C.c_uint8)), shape=(nbytes.value,))
 
-    def submit(self, slot: int) -> None:
-        N.check(N.lib().sfx_video_submit(self.handle, slot))
+    def submit(self, slot: int, nbytes: Optional[int] = None) -> None:
+        """`nbytes`: the bytes the frame has (a compressed frame: only they are copied)"""
+        if nbytes is None:
+            N.check(N.lib().sfx_video_submit(self.handle, slot))
+        else:
+            N.check(N.lib().sfx_video_submit_bytes(self.handle, slot, nbytes))
+
+    def bad_frame(self, wait: bool = False) -> Optional[tuple[int, int]]:
+        """(how many frames the stage had landed before it, status) of the first landed frame since the last call whose compressed data
+        was bad — it was not drawn; None when there is none. `wait`: for everything queued on the context's stream first."""
+        frame, status = C.c_int64(-1), C.c_uint32(0)
+        N.check(N.lib().sfx_video_status(self.handle, 1 if wait else 0, C.byref(frame), C.byref(status)))
+        return None if frame.value < 0 else (frame.value, status.value)
 
     def step(self, slot: int) -> None:
         N.check(N.lib().sfx_video_step(self.handle, slot))
@@ -204,16 +228,22 @@ class ShaderVideo(ShaderModule):
     height: Optional[int] = None
     fps: Optional[float] = None
     format: Optional[str] = None
-    """None: the source yields rgb arrays; "i420": planar 4:2:0 frames of width*height*3//2 bytes (set by the planar file sources)"""
+    """None: the source yields rgb arrays; "i420": planar 4:2:0 frames of width*height*3//2 bytes (set by the planar file sources);
+    "mjpeg": baseline JPEG streams as `bytes` (set by the Motion-JPEG file sources)"""
+    jpeg: Optional[object] = None
+    """format "mjpeg": the first frame's header (mjpegsource.JpegHeader): the geometry and sampling every frame must have"""
+    capacity: int = 0
+    """format "mjpeg": bytes of a staged frame at the most (from the container's largest chunk; for `frames=` a raw picture's worth)"""
     _stage: Optional[VideoStage] = None
+    _clip: Optional[object] = None
     _reader: Optional[Iterator] = None
     _read: int = 0
     _exhausted: bool = False
 
     def __attrs_post_init__(self):
         ShaderModule.__attrs_post_init__(self)
-        if self.format not in (None, "i420"):
-            raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays) or 'i420'")
+        if self.format not in (None, "i420", "mjpeg"):
+            raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays), 'i420' or 'mjpeg'")
         self._reader = self._open()
         if not all((self.width, self.height, self.fps)):
             raise ValueError("ShaderVideo needs width, height and fps (give them, or a source they can be read from)")
@@ -226,6 +256,8 @@ class ShaderVideo(ShaderModule):
         if self.frames is not None:
             if isinstance(self.frames, np.ndarray) and self.format is None:
                 self.height, self.width = self.height or self.frames.shape[1], self.width or self.frames.shape[2]
+            if self.format == "mjpeg":
+                return self._open_compressed(iter(self.frames), None)
             return iter(self.frames)
         if self.path is None:
             raise ValueError("ShaderVideo needs `path=` or `frames=`")
@@ -246,12 +278,39 @@ class ShaderVideo(ShaderModule):
             clip = PlanarFile(self.path, self.width, self.height, self.fps)
             self.width, self.height, self.fps, self.format = clip.width, clip.height, self.fps or clip.fps, "i420"
             return clip
+        if suffix in MJPEG_SUFFIXES:
+            from shaderflow_amd.mjpegsource import RawReader
+            self._clip = clip = RawReader(self.path, self.fps)
+            return self._open_compressed(clip, clip.largest)
+        if suffix == ".avi":
+            from shaderflow_amd.mjpegsource import AviReader
+            try:
+                clip = AviReader(self.path)
+            except LookupError:                                       # an AVI file with another codec: ffmpeg's, as before
+                clip = None
+            if clip is not None:
+                self._clip, self.fps = clip, self.fps or clip.fps
+                return self._open_compressed(clip, clip.largest)
         if not (shutil.which("ffmpeg") and shutil.which("ffprobe")):
             raise RuntimeError(f"{self.path}: decoding this container needs the ffmpeg and ffprobe binaries; "
                                "give frames=, a .npy clip or a raw .rgb file instead")
         width, height, fps = _probe(self.path)
         self.width, self.height, self.fps = self.width or width, self.height or height, self.fps or fps
         return iter_video_frames(self.path, self.width, self.height)
+
+    def _open_compressed(self, source: Iterator, largest: Optional[int]) -> Iterator:
+        """A source of JPEG streams: the clip's geometry and sampling are its first frame's"""
+        import itertools
+        from shaderflow_amd.mjpegsource import capacity_for, parse_header
+        first = next(source, None)
+        if first is None:
+            raise ValueError(f"{self.name}: a Motion-JPEG source without a frame")
+        self.jpeg = parse_header(first)
+        if (self.width and self.width != self.jpeg.width) or (self.height and self.height != self.jpeg.height):
+            raise ValueError(f"{self.name}: the frames are {self.jpeg.width} x {self.jpeg.height}, not {self.width} x {self.height}")
+        self.width, self.height, self.format = self.jpeg.width, self.jpeg.height, "mjpeg"
+        self.capacity = capacity_for(self.jpeg, largest)
+        return itertools.chain([first], source)
 
     def update(self) -> None:
         if self._exhausted or not (self.scene.time > (self._read/self.fps)):       # video.py:60
@@ -262,28 +321,44 @@ class ShaderVideo(ShaderModule):
             self._exhausted = True
             logger.warning(f"{self.name}: source ended after {self._read} frames, holding the last one")
             return
+        if self.format == "mjpeg":
+            self._read += 1                                             # (a damaged frame is passed over: the next update() shows the next one)
+            self._show_staged(frame)
+            return
         if self.format == "i420":
-            self._show_planar(frame)
+            self._show_staged(frame)
         else:
             frame = np.ascontiguousarray(np.flip(np.asarray(frame, np.uint8), axis=0))
             self.texture.roll()
             self.texture.write(frame)
         self._read += 1
 
-    def _show_planar(self, frame) -> None:
-        """A planar frame through k_video_frame, the one definition of the conversion: a pinned slot, its copy, the kernel"""
+    def _show_staged(self, frame) -> None:
+        """A planar frame through k_video_frame, a compressed one through the decode kernels — the one definition of either: a pinned
+        slot, its copy, the launch"""
         boxes = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
         if self._stage is not None and self._stage.serials != boxes:      # the texture was re-made, or rolled by somebody else
             self._stage.release()
             self._stage = None
         if self._stage is None:
             self._stage = VideoStage(self, slots=1)
-        frame = np.asarray(frame, np.uint8).reshape(-1)
-        if frame.size != self.width*self.height*3//2:
-            raise ValueError(f"{self.name}: an i420 frame of {self.width} x {self.height} has {self.width*self.height*3//2} bytes, not {frame.size}")
-        np.copyto(self._stage.view(0), frame)
-        self._stage.submit(0)
-        self._stage.step(0)
+        if self.format == "mjpeg":
+            from shaderflow_amd.mjpegsource import describe_status, stage
+            source = self._read - 1
+            self._stage.submit(0, stage(frame, self.jpeg, self._stage.view(0), f"{self.name}: source frame {source}"))
+            self._stage.step(0)
+            bad = self._stage.bad_frame(wait=True)
+            if bad is not None:                                       # the device rolled its matrix and left the box alone: so does the host
+                self.texture.roll()
+                self._stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
+                raise RuntimeError(f"{self.name}: source frame {source} could not be decoded: {describe_status(bad[1])}")
+        else:
+            frame = np.asarray(frame, np.uint8).reshape(-1)
+            if frame.size != self.width*self.height*3//2:
+                raise ValueError(f"{self.name}: an i420 frame of {self.width} x {self.height} has {self.width*self.height*3//2} bytes, not {frame.size}")
+            np.copyto(self._stage.view(0), frame)
+            self._stage.submit(0)
+            self._stage.step(0)
         self.texture.roll()
         self._stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
         self.texture.refresh_host_copy()
@@ -292,3 +367,6 @@ class ShaderVideo(ShaderModule):
         if self._stage is not None:
             self._stage.release()
             self._stage = None
+        if self._clip is not None:                                     # a Motion-JPEG file's map
+            self._clip.close()
+            self._clip = None

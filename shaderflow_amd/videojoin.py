@@ -98,7 +98,9 @@ class VideoJoinedSequence(JoinedSource):
         self.frames = 0                                                # frames drawn by the native sequence (tests, measurements)
 
     def run(self, export: "ExportingHelper", turbo: bool):
-        return self.clock.run_source(export, self, turbo)
+        result = self.clock.run_source(export, self, turbo)
+        self.video.raise_undecoded()                                   # (a damaged Motion-JPEG frame found behind the last chunk)
+        return result
 
     def attach(self, sequence) -> None:
         super().attach(sequence)

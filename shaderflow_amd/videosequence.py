@@ -26,6 +26,12 @@ A scene takes this loop when `main(batch=None)` finds it applicable (after Clock
 (videojoin.py: this source joined with the tape's and the piano's). Out of scope, so they keep the frame loop: several videos,
 `layers != 1`, a subclass of ShaderVideo, sharded runs, a scene `update()` of its own, and — for the planar sources — bt709 or
 full-range input, chroma interpolation and 10-bit sources (the reader refuses what it can see of them).
+
+Motion-JPEG sources (`video.format == "mjpeg"`: mjpegsource.py) stay compressed in the slots: the reader stages each JPEG stream
+(`mjpegsource.stage`: tables, interval starts, scan), only those bytes are copied, and a landing launches the decode kernels
+(csrc/jpeg_decode_kernels.hpp) instead of `k_video_frame`. `slot_count` works from the slots' capacity; frames taken ahead go back in
+front of the source as the `bytes` they came as; a frame the device could not decode fails the export with RuntimeError naming the
+source frame (`undecoded`; found behind the last chunk, it is raised once the export is finished), and the context stays usable.
 """
 from __future__ import annotations
 
@@ -162,10 +168,31 @@ class VideoSequence(FrameSource):
             for i in range(count):
                 if slots[i] >= 0:
                     self.staged.pop(int(self.want[first + i]), None)
+                    self.streams.pop(int(self.want[first + i]), None)
             self.free.extend(used)
             self.landed += len(used)
             self.lock.notify_all()
         self.video.texture.roll(len(used))                            # the native call rolled its own copy of the matrix once per landing
+        if self.video.format == "mjpeg":
+            error = self.undecoded(wait=False)
+            if error is not None:
+                self.error = error
+                raise error
+
+    def undecoded(self, wait: bool) -> Optional[RuntimeError]:
+        """A compressed frame the device could not decode fails the export: the error that says so, or None (the kernels noted the
+        first such frame; asking costs no wait unless `wait` says so: a damaged frame is then found a chunk later, or behind the run)"""
+        bad = self.stage.bad_frame(wait) if self.stage is not None else None
+        if bad is None:
+            return None
+        from shaderflow_amd.mjpegsource import describe_status
+        return RuntimeError(f"{self.video.name}: source frame {self.first_read + bad[0]} could not be decoded: {describe_status(bad[1])}")
+
+    def raise_undecoded(self) -> None:
+        """Behind `run_source`: a damaged frame that only `settle`'s waiting check found. The run drew every frame, so the clock is
+        set and the export finished (a sink's file is whole) before the error leaves."""
+        if self.late is not None:
+            raise self.late
 
     # the reader ------------------------------------------------------------------------------------------------------------------------
 
@@ -173,6 +200,9 @@ class VideoSequence(FrameSource):
         """The reader thread: source frames first, first + 1, … into free slots, each submitted as soon as it is whole"""
         stage, video, nbytes = self.stage, self.video, self.frame_bytes
         readinto = getattr(source, "readinto", None) if video.format == "i420" else None
+        compressed, size = video.format == "mjpeg", None
+        if compressed:
+            from shaderflow_amd.mjpegsource import stage as stage_frame
         try:
             for index in range(first, first + needed):
                 with self.lock:
@@ -190,10 +220,14 @@ class VideoSequence(FrameSource):
                     except StopIteration:
                         whole = False
                     else:
-                        frame = np.asarray(frame, np.uint8)
-                        if frame.size != nbytes:
-                            raise ValueError(f"{video.name}: a frame of {video.width} x {video.height} has {nbytes} bytes, the source gave {frame.size}")
-                        np.copyto(view.reshape(frame.shape), frame)   # (a memory-mapped clip is read here, without the GIL)
+                        if compressed:                                # the stream's tables, interval starts and scan into the slot; only they are copied
+                            size = stage_frame(frame, video.jpeg, view, f"{video.name}: source frame {index}")
+                            self.streams[index] = frame
+                        else:
+                            frame = np.asarray(frame, np.uint8)
+                            if frame.size != nbytes:
+                                raise ValueError(f"{video.name}: a frame of {video.width} x {video.height} has {nbytes} bytes, the source gave {frame.size}")
+                            np.copyto(view.reshape(frame.shape), frame)   # (a memory-mapped clip is read here, without the GIL)
                         whole = True
                 with self.lock:
                     if not whole:
@@ -202,9 +236,9 @@ class VideoSequence(FrameSource):
                         self.lock.notify_all()
                         return
                     if self.stop:                                     # (the frame is whole but nobody will draw it: it goes back to the source)
-                        self.kept[index] = view.copy()
+                        self.kept[index] = self.streams.pop(index) if compressed else view.copy()
                         return
-                stage.submit(slot)
+                stage.submit(slot, size)
                 with self.lock:
                     self.staged[index] = slot
                     self.views[slot] = view
@@ -217,7 +251,9 @@ class VideoSequence(FrameSource):
     # the export ------------------------------------------------------------------------------------------------------------------------
 
     def run(self, export: "ExportingHelper", turbo: bool):
-        return self.clock.run_source(export, self, turbo)
+        result = self.clock.run_source(export, self, turbo)
+        self.raise_undecoded()
+        return result
 
     def prepare(self, times, dts, total: int) -> None:
         """The stage and the reader thread"""
@@ -225,11 +261,12 @@ class VideoSequence(FrameSource):
         self.first_read, self.was_exhausted, self.source = video._read, video._exhausted, video._reader
         # every landing of the export, were the source endless; where it ends is learnt from the reader
         self.want = landing_frames(times, video.fps, self.first_read) if not self.was_exhausted else np.full(total, -1, np.int64)
-        self.frame_bytes = video.width*video.height*3//(2 if video.format == "i420" else 1)
+        self.frame_bytes = video.capacity if video.format == "mjpeg" else video.width*video.height*3//(2 if video.format == "i420" else 1)
+        self.streams = {}                                              # source frame → the compressed stream staged for it (they go back as bytes)
         slots = slot_count(self.frame_bytes)
         self.per_chunk = slots//2
         self.free, self.staged, self.views, self.kept = list(range(slots)), {}, {}, {}
-        self.total, self.error, self.stop, self.exhausted_at = None, None, False, None
+        self.total, self.error, self.late, self.stop, self.exhausted_at = None, None, None, False, None
         self.landed = 0
         self.stage = VideoStage(video, slots)
         self.thread = threading.Thread(target=self.read_frames, args=(self.source, self.first_read, int((self.want >= 0).sum())),
@@ -248,14 +285,21 @@ class VideoSequence(FrameSource):
         if video._exhausted and not self.was_exhausted:
             logger.warning(f"{video.name}: source ended after {video._read} frames, holding the last one")
         # frames taken from the source but not drawn go back in front of it, in order, for a later update()
-        ahead = {index: self.views[slot].copy() for index, slot in self.staged.items()}
+        if video.format == "mjpeg":
+            ahead = {index: self.streams[index] for index in self.staged}
+        else:
+            ahead = {index: self.views[slot].copy() for index, slot in self.staged.items()}
         ahead.update(self.kept)
-        if ahead:
+        if ahead and video.format == "mjpeg":
+            video._reader = itertools.chain([ahead[index] for index in sorted(ahead)], self.source)
+        elif ahead:
             shape = (-1,) if video.format == "i420" else (video.height, video.width, 3)
             video._reader = itertools.chain([ahead[index].reshape(shape) for index in sorted(ahead)], self.source)
         # the host copies of the boxes the run wrote into, as `texture.write` keeps them: read back from the device
         for depth in range(min(self.landed, video.texture.temporal) if done else 0):
             video.texture.refresh_host_copy(depth)
+        if video.format == "mjpeg" and self.error is None:
+            self.late = self.undecoded(wait=True)
 
     def finished(self, done: int, total: int) -> bool:
         return self.error is None and not self.scene.quit and done == total
