@@ -433,6 +433,39 @@ int sfx_video_step(sfx_handle video, int slot);
  * builds from a stream's header (shaderflow_amd/mjpegsource.py). A slot holds at most `capacity` bytes. Everything else is
  * sfx_video_create's; sfx_video_step and a landing frame of sfx_sequence_run launch the decode kernels instead of k_video_frame —
  * the same event hand-over, the same roll. sfx_video_create itself keeps refusing format 2: the geometry it takes does not say enough. */
+/* The fixed part of a staged frame: what the host's reader puts at the start of a slot (mjpegsource.py mirrors it as the numpy record
+ * `STAGED`), all words little-endian. Behind it: one word per restart interval — where its entropy-coded bytes start, counted from the
+ * scan's start, 0xffffffff for an interval whose RSTn marker is missing — padded to 16 bytes; then, at `scan_offset`, the scan: the
+ * bytes between SOS's segment and the marker that ends the scan. */
+enum { SFX_JPEG_FRAME_MAGIC = 0x444a4653 /* "SFJD" */ };
+typedef struct sfx_jpeg_huffman { uint8_t bits[16]; uint8_t values[256]; } sfx_jpeg_huffman;       /* BITS and HUFFVAL */
+typedef struct sfx_jpeg_frame {
+    uint32_t magic;                 /* SFX_JPEG_FRAME_MAGIC */
+    uint32_t scan_bytes;
+    uint32_t restart;               /* MCUs per restart interval (the MCU count when the stream has none) */
+    uint32_t intervals;
+    uint32_t scan_offset;           /* where the scan starts in the staged frame */
+    uint32_t components;
+    uint8_t tq[4], td[4], ta[4];    /* per component: its quantisation, DC and AC table */
+    uint8_t reserved0[28];
+    uint8_t quant[4][64];           /* zigzag order */
+    sfx_jpeg_huffman huffman[4];    /* DC 0, DC 1, AC 0, AC 1 */
+    uint8_t reserved1[128];
+} sfx_jpeg_frame;
+#ifdef __cplusplus
+#define SFX_STATIC_ASSERT(condition, text) static_assert(condition, text)
+#else
+#define SFX_STATIC_ASSERT(condition, text) _Static_assert(condition, text)
+#endif
+SFX_STATIC_ASSERT(sizeof(sfx_jpeg_frame) == 1536, "the interval table starts at byte 1536");
+SFX_STATIC_ASSERT(offsetof(sfx_jpeg_frame, tq) == 24 && offsetof(sfx_jpeg_frame, td) == 28 && offsetof(sfx_jpeg_frame, ta) == 32
+                  && offsetof(sfx_jpeg_frame, quant) == 64 && offsetof(sfx_jpeg_frame, huffman) == 320, "the staged frame's layout");
+/* bits of a frame's status word (sfx_video_status, sfx_jpeg_decode) */
+enum { SFX_JPEG_BAD_CODE = 1,       /* a code that matches no Huffman code */
+       SFX_JPEG_BAD_RUN = 2,        /* a zero run past the block's 63rd term */
+       SFX_JPEG_BAD_RESTART = 4,    /* a missing or wrong RSTn marker */
+       SFX_JPEG_OUT_OF_BITS = 8,    /* the entropy-coded data ran out of bits */
+       SFX_JPEG_BAD_DESCRIPTOR = 16 /* a staged frame the kernels refuse */ };
 int sfx_video_create_mjpeg(sfx_handle ctx, const sfx_handle* boxes, int temporal, int width, int height, int components, int h_sampling, int v_sampling,
                            size_t capacity, int slots, sfx_handle* video);
 /* sfx_video_submit for a frame of `nbytes` bytes: only they are copied. A Motion-JPEG frame's words are validated here (magic, interval
@@ -440,8 +473,7 @@ int sfx_video_create_mjpeg(sfx_handle ctx, const sfx_handle* boxes, int temporal
  * formats `nbytes` must be the frame's size. */
 int sfx_video_submit_bytes(sfx_handle video, int slot, size_t nbytes);
 /* The first landed Motion-JPEG frame since the last call whose entropy-coded data was bad: `frame` = how many frames the handle had
- * landed before it (-1: none was bad), `status` = its bits: 1 a code that matches nothing, 2 a run past 63, 4 a missing or wrong RSTn,
- * 8 bits running out, 16 a descriptor the kernels refuse. Such a frame is not drawn: the texture it would have been written into keeps
+ * landed before it (-1: none was bad), `status` = its SFX_JPEG_* bits (above). Such a frame is not drawn: the texture it would have been written into keeps
  * its content. `wait` non-zero: waits for the context's stream first (else only frames whose kernels have run are seen). */
 int sfx_video_status(sfx_handle video, int wait, int64_t* frame, uint32_t* status);
 /* Test entry, in the spirit of sfx_jpeg_coefficients: one staged frame from host memory through the three decode kernels. Any of the

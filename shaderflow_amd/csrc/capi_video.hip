@@ -62,31 +62,78 @@ static void video_release(Video* v) {
     delete v;
 }
 
-extern "C" int sfx_video_create(sfx_handle hc, const sfx_handle* boxes, int temporal, int width, int height, int format, int slots, sfx_handle* out) {
-    CTX_OR_FAIL(c, hc);
-    if (!boxes || !out || temporal < 1 || width < 1 || height < 1 || slots < 1 || slots > 256) return fail(SFX_E_INVALID, "video: null boxes or output, or %d x %d, temporal %d, %d slots", width, height, temporal, slots);
-    if (format != SFX_VIDEO_RGB24 && format != SFX_VIDEO_I420) return fail(SFX_E_INVALID, "video: source format %d", format);
-    if (format == SFX_VIDEO_I420 && ((width & 1) || (height & 1))) return fail(SFX_E_INVALID, "video: a 4:2:0 source needs even extents, not %d x %d", width, height);
+static int jpeg_decode_geometry(int width, int height, int components, int hs, int vs, size_t capacity, JpegDecodeGeometry* g) {
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(SFX_E_INVALID, "jpeg decode: %d x %d (extents 1…65535)", width, height);
+    if (components != 1 && components != 3) return fail(SFX_E_INVALID, "jpeg decode: %d components (1: grey, 3: YCbCr)", components);
+    if (components == 1) hs = vs = 1;
+    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return fail(SFX_E_INVALID, "jpeg decode: luma sampling %d x %d (2x2, 2x1 or 1x1)", hs, vs);
+    if (capacity < (size_t)JPEG_FRAME_FIXED + 16 || capacity > ((size_t)1 << 30)) return fail(SFX_E_INVALID, "jpeg decode: a staged frame of at most %zu bytes (%d … 2^30)", capacity, JPEG_FRAME_FIXED + 16);
+    g->width = width; g->height = height; g->components = components; g->hs = hs; g->vs = vs;
+    g->mcus_x = (width + 8*hs - 1)/(8*hs); g->mcus_y = (height + 8*vs - 1)/(8*vs); g->blocks = components == 1 ? 1 : hs*vs + 2;
+    g->capacity = (int)((capacity + 15) & ~(size_t)15);
+    return SFX_OK;
+}
+
+// [basis 64 f32][status words, 64 bytes' worth at least][coefficients][planes], each part 256-byte aligned
+static int jpeg_scratch(const JpegDecodeGeometry& g, int slots, void** scratch, float** basis, uint32_t** status, int16_t** coefficients, uint8_t** planes) {
+    const size_t status_bytes = ((size_t)slots*4 + 255) & ~(size_t)255, coefficient_bytes = (jpeg_decode_coefficients(g)*2 + 255) & ~(size_t)255;
+    if (hipMalloc(scratch, 256 + status_bytes + coefficient_bytes + jpeg_plane_bytes(g)) != hipSuccess) { (void)hipGetLastError(); *scratch = nullptr; return SFX_E_HIP; }
+    char* base = (char*)*scratch;
+    *basis = (float*)base; *status = (uint32_t*)(base + 256); *coefficients = (int16_t*)(base + 256 + status_bytes); *planes = (uint8_t*)(base + 256 + status_bytes + coefficient_bytes);
+    float dct[64];
+    jpeg_dct_basis(dct);
+    if (hipMemcpy(*basis, dct, sizeof dct, hipMemcpyHostToDevice) != hipSuccess || hipMemset(*status, 0, status_bytes) != hipSuccess) { (void)hipGetLastError(); hipFree(*scratch); *scratch = nullptr; return SFX_E_HIP; }
+    return SFX_OK;
+}
+
+// The handle of either entry below: `slots` pinned frames of `frame_bytes` bytes, their device staging, an event each and the copy
+// stream. `jpeg` (SFX_VIDEO_MJPEG): the staging is one block and the decoder's scratch comes with it. Else every staging frame is an
+// allocation of its own with 16 bytes behind it: k_video_frame's 16-byte loads may reach past a frame's last row (video_kernels.hpp).
+static int video_create(Context* c, const sfx_handle* boxes, int temporal, int width, int height, int format, size_t frame_bytes, int slots,
+                        const JpegDecodeGeometry* jpeg, sfx_handle* out) {
+    if (!boxes || !out || temporal < 1 || width < 1 || height < 1 || slots < 1 || slots > 256)
+        return fail(SFX_E_INVALID, "video: null boxes or output, or %d x %d, temporal %d, %d slots (1…256)", width, height, temporal, slots);
     USE_DEVICE(c);
     Video* v = new Video();
     v->magic = MAGIC_VIDEO; v->ctx = c; v->temporal = temporal; v->width = width; v->height = height; v->format = format; v->slots = slots;
-    v->frame_bytes = format == SFX_VIDEO_I420 ? (size_t)width*height*3/2 : (size_t)width*height*3;
+    v->frame_bytes = frame_bytes;
+    if (jpeg) v->jpeg = *jpeg;
     v->boxes.assign(boxes, boxes + temporal);
     for (int d = 0; d < temporal; d++)
         if (!video_texture(v->boxes[d], v)) { delete v; return fail(SFX_E_INVALID, "video: box %d is not a %d x %d RGB8 texture of this context (layers must be 1)", d, width, height); }
-    v->host.assign(slots, nullptr); v->staging.assign(slots, nullptr); v->events.assign(slots, nullptr); v->state.assign(slots, SLOT_NEW);
+    v->host.assign(slots, nullptr); v->staging.assign(slots, nullptr); v->events.assign(slots, nullptr); v->state.assign(slots, SLOT_NEW); v->intervals.assign(slots, 0);
     bool ok = hipStreamCreateWithFlags(&v->copy, hipStreamNonBlocking) == hipSuccess;
-    for (int k = 0; ok && k < slots; k++)
-        ok = hipHostMalloc(&v->host[k], v->frame_bytes, hipHostMallocDefault) == hipSuccess && hipMalloc(&v->staging[k], v->frame_bytes + 16) == hipSuccess
-             && hipEventCreateWithFlags(&v->events[k], hipEventDisableTiming) == hipSuccess;
+    if (ok && jpeg)
+        ok = hipMalloc(&v->staging_block, frame_bytes*slots) == hipSuccess && hipHostMalloc((void**)&v->first_bad, 64, hipHostMallocDefault) == hipSuccess
+             && jpeg_scratch(*jpeg, slots, &v->scratch, &v->basis, &v->status, &v->coefficients, &v->planes) == SFX_OK;
+    for (int k = 0; ok && k < slots; k++) {
+        if (jpeg) v->staging[k] = (char*)v->staging_block + (size_t)k*frame_bytes;
+        else ok = hipMalloc(&v->staging[k], frame_bytes + 16) == hipSuccess;
+        ok = ok && hipHostMalloc(&v->host[k], frame_bytes, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&v->events[k], hipEventDisableTiming) == hipSuccess;
+    }
     if (!ok) {
-        const size_t frame_bytes = v->frame_bytes;
         (void)hipGetLastError();
         video_release(v);
-        return fail(SFX_E_HIP, "video: %d staging frames of %zu bytes (pinned and device) could not be allocated", slots, frame_bytes);
+        return fail(SFX_E_HIP, "video: %d staging frames of %zu bytes (pinned and device)%s could not be allocated", slots, frame_bytes, jpeg ? " and the decoder's scratch" : "");
     }
+    if (v->first_bad) memset(v->first_bad, 0, 64);
     *out = handle_of(v);
     return SFX_OK;
+}
+
+extern "C" int sfx_video_create(sfx_handle hc, const sfx_handle* boxes, int temporal, int width, int height, int format, int slots, sfx_handle* out) {
+    CTX_OR_FAIL(c, hc);
+    if (format != SFX_VIDEO_RGB24 && format != SFX_VIDEO_I420) return fail(SFX_E_INVALID, "video: source format %d", format);
+    if (format == SFX_VIDEO_I420 && ((width & 1) || (height & 1))) return fail(SFX_E_INVALID, "video: a 4:2:0 source needs even extents, not %d x %d", width, height);
+    return video_create(c, boxes, temporal, width, height, format, (size_t)width*height*3/(format == SFX_VIDEO_I420 ? 2 : 1), slots, nullptr, out);   // (extents below 1 are refused there)
+}
+
+extern "C" int sfx_video_create_mjpeg(sfx_handle hc, const sfx_handle* boxes, int temporal, int width, int height, int components, int h_sampling, int v_sampling,
+                                      size_t capacity, int slots, sfx_handle* out) {
+    CTX_OR_FAIL(c, hc);
+    JpegDecodeGeometry g;
+    if (const int rc = jpeg_decode_geometry(width, height, components, h_sampling, v_sampling, capacity, &g)) return rc;
+    return video_create(c, boxes, temporal, width, height, SFX_VIDEO_MJPEG, (size_t)g.capacity, slots, &g, out);
 }
 
 extern "C" int sfx_video_slot(sfx_handle h, int slot, void** host, size_t* nbytes) {
@@ -104,23 +151,23 @@ extern "C" int sfx_video_slot(sfx_handle h, int slot, void** host, size_t* nbyte
     return SFX_OK;
 }
 
-// why a staged Motion-JPEG frame of `nbytes` bytes is not one the kernels may be given (null: it is)
-static const char* jpeg_frame_fault(const uint8_t* frame, size_t nbytes, const JpegDecodeGeometry& g) {
-    if (nbytes < (size_t)JPEG_FRAME_FIXED || nbytes > (size_t)g.capacity) return "its length is outside the fixed part … the slot's capacity";
-    uint32_t words[6];
-    memcpy(words, frame, sizeof words);
-    const unsigned long long total = (unsigned long long)g.mcus_x*g.mcus_y, scan_bytes = words[1], restart = words[2], intervals = words[3], scan_offset = words[4];
-    if (words[0] != JPEG_FRAME_MAGIC) return "no SFJD magic";
-    if (restart < 1 || intervals != (total + restart - 1)/restart) return "the interval count does not follow from the restart interval and the geometry";
-    if (scan_offset != (unsigned long long)JPEG_FRAME_FIXED + jpeg_interval_table_bytes((uint32_t)intervals) || scan_offset + scan_bytes > nbytes) return "the scan does not lie behind the interval table and inside the frame";
-    if ((int)words[5] != g.components) return "another component count than the video's";
+// why a staged Motion-JPEG frame of `nbytes` bytes is not one the kernels may be given (null: it is, and `intervals` is its interval count)
+static const char* jpeg_frame_fault(const void* frame, size_t nbytes, const JpegDecodeGeometry& g, uint32_t* intervals) {
+    if (nbytes < sizeof(sfx_jpeg_frame) || nbytes > (size_t)g.capacity) return "its length is outside the fixed part … the slot's capacity";
+    sfx_jpeg_frame f;
+    memcpy(&f, frame, sizeof f);                                     // (sfx_jpeg_decode's caller owes no alignment)
+    static const char* const why[] = {nullptr, "no SFJD magic", "the interval count does not follow from the restart interval and the geometry",
+                                      "the scan does not lie behind the interval table and inside the frame"};
+    if (const int fault = jpeg_descriptor_fault(f, g.mcus_x, g.mcus_y, nbytes)) return why[fault];
+    if ((int)f.components != g.components) return "another component count than the video's";
     for (int c = 0; c < g.components; c++)
-        if (frame[JPEG_FRAME_TQ + c] > 3 || frame[JPEG_FRAME_TD + c] > 1 || frame[JPEG_FRAME_TA + c] > 1) return "a table selector outside 0…3 (quantisation) or 0…1 (Huffman)";
-    for (int t = 0; t < 4; t++) {
+        if (f.tq[c] > 3 || f.td[c] > 1 || f.ta[c] > 1) return "a table selector outside 0…3 (quantisation) or 0…1 (Huffman)";
+    for (const sfx_jpeg_huffman& table : f.huffman) {
         int count = 0;
-        for (int k = 0; k < 16; k++) count += frame[JPEG_FRAME_HUFFMAN + t*JPEG_HUFFMAN_BYTES + k];
+        for (int k = 0; k < 16; k++) count += table.bits[k];
         if (count > 256) return "a Huffman table with more than 256 codes";
     }
+    *intervals = f.intervals;
     return nullptr;
 }
 
@@ -129,8 +176,7 @@ static int video_submit(Video* v, int slot, size_t nbytes, bool staged = false) 
     std::lock_guard<std::mutex> lock(v->guard);
     if (v->state[slot] == SLOT_SUBMITTED) return fail(SFX_E_INVALID, "video: slot %d holds a submitted frame that was not consumed yet", slot);
     if (staged) {
-        if (const char* fault = jpeg_frame_fault((const uint8_t*)v->host[slot], nbytes, v->jpeg)) return fail(SFX_E_INVALID, "video: the staged Motion-JPEG frame of %zu bytes in slot %d: %s", nbytes, slot, fault);
-        memcpy(&v->intervals[slot], (const uint8_t*)v->host[slot] + 12, sizeof(uint32_t));
+        if (const char* fault = jpeg_frame_fault(v->host[slot], nbytes, v->jpeg, &v->intervals[slot])) return fail(SFX_E_INVALID, "video: the staged Motion-JPEG frame of %zu bytes in slot %d: %s", nbytes, slot, fault);
         nbytes = (nbytes + 15) & ~(size_t)15;
     }
     USE_DEVICE(v->ctx);
@@ -166,7 +212,7 @@ static void jpeg_launch_decode(hipStream_t stream, const uint8_t* frame, uint32_
     hipMemsetAsync(status, 0, sizeof(uint32_t), stream);
     hipLaunchKernelGGL(k_jpeg_decode_entropy, dim3((intervals + 63)/64), dim3(64), 0, stream, frame, coefficients, status, g);
     const size_t blocks = (size_t)g.mcus_x*g.mcus_y*g.blocks;
-    hipLaunchKernelGGL(k_jpeg_decode_planes, dim3((unsigned)((blocks + 3)/4)), dim3(256), 0, stream, frame, (const int16_t*)coefficients, planes, basis, (const uint32_t*)status,
+    hipLaunchKernelGGL(k_jpeg_decode_planes, dim3((unsigned)((blocks + 3)/4)), dim3(256), 0, stream, (const sfx_jpeg_frame*)frame, (const int16_t*)coefficients, planes, basis, (const uint32_t*)status,
                        (volatile uint32_t*)first_bad, serial, g);
     const long lanes = jpeg_pixel_lanes(g.width, g.height);
     hipLaunchKernelGGL(k_jpeg_decode_pixels, dim3((unsigned)((lanes + 255)/256)), dim3(256), 0, stream, (const uint8_t*)planes, rgb, (const uint32_t*)status, g, bottom_up);
@@ -227,66 +273,6 @@ extern "C" int sfx_video_destroy(sfx_handle h) {
 
 // ---- Motion-JPEG sources ---------------------------------------------------------------------------------------------------------------
 
-static int jpeg_decode_geometry(int width, int height, int components, int hs, int vs, size_t capacity, JpegDecodeGeometry* g) {
-    if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(SFX_E_INVALID, "jpeg decode: %d x %d (extents 1…65535)", width, height);
-    if (components != 1 && components != 3) return fail(SFX_E_INVALID, "jpeg decode: %d components (1: grey, 3: YCbCr)", components);
-    if (components == 1) hs = vs = 1;
-    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return fail(SFX_E_INVALID, "jpeg decode: luma sampling %d x %d (2x2, 2x1 or 1x1)", hs, vs);
-    if (capacity < (size_t)JPEG_FRAME_FIXED + 16 || capacity > ((size_t)1 << 30)) return fail(SFX_E_INVALID, "jpeg decode: a staged frame of at most %zu bytes (%d … 2^30)", capacity, JPEG_FRAME_FIXED + 16);
-    g->width = width; g->height = height; g->components = components; g->hs = hs; g->vs = vs;
-    g->mcus_x = (width + 8*hs - 1)/(8*hs); g->mcus_y = (height + 8*vs - 1)/(8*vs); g->blocks = components == 1 ? 1 : hs*vs + 2;
-    g->capacity = (int)((capacity + 15) & ~(size_t)15);
-    return SFX_OK;
-}
-
-static void jpeg_basis(float* dct) {                                 // the encoder's (capi_jpeg.hip)
-    for (int u = 0; u < 8; u++)
-        for (int x = 0; x < 8; x++) dct[u*8 + x] = (float)((u == 0 ? std::sqrt(0.125) : 0.5)*std::cos((2*x + 1)*u*M_PI/16.0));
-}
-
-// [basis 64 f32][status words, 64 bytes' worth at least][coefficients][planes], each part 256-byte aligned
-static int jpeg_scratch(const JpegDecodeGeometry& g, int slots, void** scratch, float** basis, uint32_t** status, int16_t** coefficients, uint8_t** planes) {
-    const size_t status_bytes = ((size_t)slots*4 + 255) & ~(size_t)255, coefficient_bytes = (jpeg_decode_coefficients(g)*2 + 255) & ~(size_t)255;
-    if (hipMalloc(scratch, 256 + status_bytes + coefficient_bytes + jpeg_plane_bytes(g)) != hipSuccess) { (void)hipGetLastError(); *scratch = nullptr; return SFX_E_HIP; }
-    char* base = (char*)*scratch;
-    *basis = (float*)base; *status = (uint32_t*)(base + 256); *coefficients = (int16_t*)(base + 256 + status_bytes); *planes = (uint8_t*)(base + 256 + status_bytes + coefficient_bytes);
-    float dct[64];
-    jpeg_basis(dct);
-    if (hipMemcpy(*basis, dct, sizeof dct, hipMemcpyHostToDevice) != hipSuccess || hipMemset(*status, 0, status_bytes) != hipSuccess) { (void)hipGetLastError(); hipFree(*scratch); *scratch = nullptr; return SFX_E_HIP; }
-    return SFX_OK;
-}
-
-extern "C" int sfx_video_create_mjpeg(sfx_handle hc, const sfx_handle* boxes, int temporal, int width, int height, int components, int h_sampling, int v_sampling,
-                                      size_t capacity, int slots, sfx_handle* out) {
-    CTX_OR_FAIL(c, hc);
-    if (!boxes || !out || temporal < 1 || slots < 1 || slots > 256) return fail(SFX_E_INVALID, "video: null boxes or output, temporal %d, %d slots (1…256)", temporal, slots);
-    JpegDecodeGeometry g;
-    if (const int rc = jpeg_decode_geometry(width, height, components, h_sampling, v_sampling, capacity, &g)) return rc;
-    USE_DEVICE(c);
-    Video* v = new Video();
-    v->magic = MAGIC_VIDEO; v->ctx = c; v->temporal = temporal; v->width = width; v->height = height; v->format = SFX_VIDEO_MJPEG; v->slots = slots;
-    v->jpeg = g; v->frame_bytes = (size_t)g.capacity;
-    v->boxes.assign(boxes, boxes + temporal);
-    for (int d = 0; d < temporal; d++)
-        if (!video_texture(v->boxes[d], v)) { delete v; return fail(SFX_E_INVALID, "video: box %d is not a %d x %d RGB8 texture of this context (layers must be 1)", d, width, height); }
-    v->host.assign(slots, nullptr); v->staging.assign(slots, nullptr); v->events.assign(slots, nullptr); v->state.assign(slots, SLOT_NEW); v->intervals.assign(slots, 0);
-    bool ok = hipStreamCreateWithFlags(&v->copy, hipStreamNonBlocking) == hipSuccess && hipMalloc(&v->staging_block, v->frame_bytes*slots) == hipSuccess
-              && hipHostMalloc((void**)&v->first_bad, 64, hipHostMallocDefault) == hipSuccess
-              && jpeg_scratch(g, slots, &v->scratch, &v->basis, &v->status, &v->coefficients, &v->planes) == SFX_OK;
-    for (int k = 0; ok && k < slots; k++) {
-        v->staging[k] = (char*)v->staging_block + (size_t)k*v->frame_bytes;
-        ok = hipHostMalloc(&v->host[k], v->frame_bytes, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&v->events[k], hipEventDisableTiming) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        video_release(v);
-        return fail(SFX_E_HIP, "video: %d staging frames of %zu bytes (pinned and device) and the decoder's scratch could not be allocated", slots, (size_t)g.capacity);
-    }
-    memset(v->first_bad, 0, 64);
-    *out = handle_of(v);
-    return SFX_OK;
-}
-
 extern "C" int sfx_video_status(sfx_handle h, int wait, int64_t* frame, uint32_t* status) {
     Video* v = get<Video>(h, MAGIC_VIDEO);
     if (!v || !frame || !status) return fail(SFX_E_INVALID, "invalid video handle or null pointer");
@@ -306,7 +292,8 @@ extern "C" int sfx_jpeg_decode(sfx_handle hc, const void* staged, size_t nbytes,
     if (!staged || !status) return fail(SFX_E_INVALID, "jpeg decode: null frame or status");
     JpegDecodeGeometry g;
     if (const int rc = jpeg_decode_geometry(width, height, components, h_sampling, v_sampling, std::max(nbytes, (size_t)JPEG_FRAME_FIXED + 16), &g)) return rc;
-    if (const char* fault = jpeg_frame_fault((const uint8_t*)staged, nbytes, g)) return fail(SFX_E_INVALID, "jpeg decode: the staged frame of %zu bytes: %s", nbytes, fault);
+    uint32_t intervals = 0;
+    if (const char* fault = jpeg_frame_fault(staged, nbytes, g, &intervals)) return fail(SFX_E_INVALID, "jpeg decode: the staged frame of %zu bytes: %s", nbytes, fault);
     USE_DEVICE(c);
     void *scratch = nullptr, *frame = nullptr, *pixels = nullptr;
     float* basis; uint32_t* device_status; int16_t* device_coefficients; uint8_t* device_planes;
@@ -314,8 +301,6 @@ extern "C" int sfx_jpeg_decode(sfx_handle hc, const void* staged, size_t nbytes,
     int rc = jpeg_scratch(g, 1, &scratch, &basis, &device_status, &device_coefficients, &device_planes);
     if (rc == SFX_OK && (hipMalloc(&frame, (size_t)g.capacity) != hipSuccess || hipMalloc(&pixels, rgb_bytes) != hipSuccess)) rc = SFX_E_HIP;
     if (rc == SFX_OK) {
-        uint32_t intervals;
-        memcpy(&intervals, (const uint8_t*)staged + 12, sizeof intervals);
         bool ok = hipMemsetAsync(frame, 0, (size_t)g.capacity, c->stream) == hipSuccess && hipMemsetAsync(pixels, 0, rgb_bytes, c->stream) == hipSuccess
                   && hipMemsetAsync(device_coefficients, 0, (size_t)(device_planes - (uint8_t*)device_coefficients) + jpeg_plane_bytes(g), c->stream) == hipSuccess
                   && hipMemcpyAsync(frame, staged, nbytes, hipMemcpyHostToDevice, c->stream) == hipSuccess;

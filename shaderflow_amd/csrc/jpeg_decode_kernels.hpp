@@ -23,13 +23,9 @@
 //       B = Y + ((116130 Cb' + 32768) >> 16)                         grey: R = G = B = Y;
 //   * output: the module's RGB8 texture, rows bottom-up, exactly as k_video_frame writes it.
 //
-// A staged frame (what the host's reader puts into a slot; all words little-endian):
-//   word 0 magic "SFJD", 1 scan bytes, 2 MCUs per restart interval (the MCU count when the stream has none), 3 intervals,
-//   4 where the scan starts in the staged frame, 5 components; bytes 24… quantiser, 28… DC table, 32… AC table of each component;
-//   bytes 64… four quantisation tables of 64 bytes in zigzag order; bytes 320… four Huffman tables (DC 0, DC 1, AC 0, AC 1) as 16 BITS
-//   and 256 HUFFVAL bytes; bytes 1536… one word per interval: where its entropy-coded bytes start, counted from the scan's start (the
-//   host's reader finds the FF D0…D7 pairs with numpy: DESIGN.md §7c says why), 0xffffffff for an interval whose marker is missing;
-//   then, 16-byte aligned, the scan: the bytes between SOS's segment and the marker that ends the scan.
+// A staged frame (what the host's reader puts into a slot) is `sfx_jpeg_frame` (include/shaderflow_hip.h: the six words, the components'
+// table selectors, four quantisation tables in zigzag order, four Huffman tables as BITS and HUFFVAL), one word per restart interval
+// behind it (the host's reader finds the FF D0…D7 pairs with numpy: DESIGN.md §7c says why), then, 16-byte aligned, the scan.
 // The host validates the words when a frame is submitted (capi_video.hip); the kernels check them again and clamp what they index with.
 //
 // Three kernels on the render stream:
@@ -46,18 +42,11 @@
 // read once (counted, not measured: DESIGN.md §7c).
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "jpeg_common.hpp"
 
 namespace sf {
 
-constexpr uint32_t JPEG_FRAME_MAGIC = 0x444a4653u;                  // "SFJD"
-constexpr int JPEG_FRAME_TQ = 24, JPEG_FRAME_TD = 28, JPEG_FRAME_TA = 32, JPEG_FRAME_QUANT = 64, JPEG_FRAME_HUFFMAN = 320;
-constexpr int JPEG_FRAME_FIXED = 1536;                              // the interval table starts here
-constexpr int JPEG_HUFFMAN_BYTES = 16 + 256;
-
-// bits of a frame's status word
-enum : uint32_t { JPEG_BAD_CODE = 1u, JPEG_BAD_RUN = 2u, JPEG_BAD_RESTART = 4u, JPEG_OUT_OF_BITS = 8u, JPEG_BAD_DESCRIPTOR = 16u };
+constexpr int JPEG_FRAME_FIXED = sizeof(sfx_jpeg_frame);               // the interval table starts here
 
 struct JpegDecodeGeometry {
     int width, height;
@@ -73,13 +62,6 @@ __host__ __device__ inline size_t jpeg_plane_offset(const JpegDecodeGeometry& g,
     return component == 0 ? 0 : luma + (component - 1)*chroma;
 }
 inline size_t jpeg_plane_bytes(const JpegDecodeGeometry& g) { return jpeg_plane_offset(g, g.components); }
-inline size_t jpeg_interval_table_bytes(uint32_t intervals) { return ((size_t)intervals*4 + 15) & ~(size_t)15; }
-
-// natural (row-major) index of each zigzag position
-static __device__ const uint8_t JPEG_NATURAL_OF[64] = {
-    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63,
-};
 
 // ---- 1. Huffman decoding, a lane per restart interval ------------------------------------------------------------------------------
 // The bit reader keeps up to 64 bits, right-aligned. Past the interval's end, or at a marker inside it, it feeds zero bits and counts
@@ -114,19 +96,17 @@ __global__ void __launch_bounds__(64) k_jpeg_decode_entropy(const uint8_t* __res
     __shared__ int maxcode[4][17], valoff[4][17];                       // Annex F.2.2.3: the largest code of each length (-1: none), VALPTR - MINCODE
     __shared__ uint8_t values[4][256];
     const int lane = threadIdx.x;
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(frame);
-    const uint32_t scan_bytes = words[1], restart = words[2], intervals = words[3], scan_offset = words[4];
+    const sfx_jpeg_frame& f = *reinterpret_cast<const sfx_jpeg_frame*>(frame);
+    const uint32_t scan_bytes = f.scan_bytes, restart = f.restart, intervals = f.intervals, scan_offset = f.scan_offset;
     const unsigned long long total = (unsigned long long)g.mcus_x*g.mcus_y;
-    const bool sane = words[0] == JPEG_FRAME_MAGIC && restart >= 1u && (unsigned long long)intervals == (total + restart - 1ull)/restart
-                      && (unsigned long long)scan_offset == (unsigned long long)JPEG_FRAME_FIXED + (((unsigned long long)intervals*4ull + 15ull) & ~15ull)
-                      && (unsigned long long)scan_offset + scan_bytes <= (unsigned long long)g.capacity;
+    const bool sane = jpeg_descriptor_fault(f, g.mcus_x, g.mcus_y, (unsigned long long)g.capacity) == 0;
     if (!sane) {                                                        // (uniform: the whole workgroup leaves)
-        if (blockIdx.x == 0 && lane == 0) atomicOr(status, JPEG_BAD_DESCRIPTOR);
+        if (blockIdx.x == 0 && lane == 0) atomicOr(status, SFX_JPEG_BAD_DESCRIPTOR);
         return;
     }
-    for (int k = lane; k < 4*256; k += 64) values[k >> 8][k & 255] = frame[JPEG_FRAME_HUFFMAN + (k >> 8)*JPEG_HUFFMAN_BYTES + 16 + (k & 255)];
+    for (int k = lane; k < 4*256; k += 64) values[k >> 8][k & 255] = f.huffman[k >> 8].values[k & 255];
     if (lane < 4) {
-        const uint8_t* bits = frame + JPEG_FRAME_HUFFMAN + lane*JPEG_HUFFMAN_BYTES;
+        const uint8_t* bits = f.huffman[lane].bits;
         int code = 0, first = 0;
         for (int length = 1; length <= 16; length++) {
             const int count = bits[length - 1];
@@ -157,8 +137,8 @@ __global__ void __launch_bounds__(64) k_jpeg_decode_entropy(const uint8_t* __res
     const uint8_t* scan = frame + scan_offset;
     const unsigned long long begin = offsets[interval], finish = interval + 1u < intervals ? (unsigned long long)offsets[interval + 1u] : (unsigned long long)scan_bytes + 2ull;
     uint32_t flags = 0;
-    if (begin > scan_bytes || finish < begin + 2ull || finish > (unsigned long long)scan_bytes + 2ull) flags = JPEG_BAD_RESTART;      // this interval's marker, or the next one's, is missing
-    else if (interval > 0u && (begin < 2ull || scan[begin - 2] != 0xffu || scan[begin - 1] != 0xd0u + ((interval - 1u) & 7u))) flags = JPEG_BAD_RESTART;
+    if (begin > scan_bytes || finish < begin + 2ull || finish > (unsigned long long)scan_bytes + 2ull) flags = SFX_JPEG_BAD_RESTART;      // this interval's marker, or the next one's, is missing
+    else if (interval > 0u && (begin < 2ull || scan[begin - 2] != 0xffu || scan[begin - 1] != 0xd0u + ((interval - 1u) & 7u))) flags = SFX_JPEG_BAD_RESTART;
     if (flags) { atomicOr(status, flags); return; }
 
     JpegBitReader reader{scan + begin, scan + (finish - 2ull), 0ull, 0, 0};
@@ -189,10 +169,10 @@ __global__ void __launch_bounds__(64) k_jpeg_decode_entropy(const uint8_t* __res
     for (int m = 0; m < mcus && !flags; m++) {
         for (int b = 0; b < g.blocks && !flags; b++, out += 64) {
             const int component = b < luma_blocks ? 0 : b - luma_blocks + 1;
-            const int dc_table = frame[JPEG_FRAME_TD + component] & 1, ac_table = 2 + (frame[JPEG_FRAME_TA + component] & 1);
+            const int dc_table = f.td[component] & 1, ac_table = 2 + (f.ta[component] & 1);
             for (int k = 0; k < 8; k++) reinterpret_cast<uint4*>(out)[k] = make_uint4(0u, 0u, 0u, 0u);
             int size = symbol(dc_table);
-            if (size < 0 || size > 15) { flags |= JPEG_BAD_CODE; break; }
+            if (size < 0 || size > 15) { flags |= SFX_JPEG_BAD_CODE; break; }
             const int difference = jpeg_extend(jpeg_take(reader, size), size);
             int& predictor = component == 0 ? predictor0 : (component == 1 ? predictor1 : predictor2);
             predictor += difference;
@@ -200,20 +180,20 @@ __global__ void __launch_bounds__(64) k_jpeg_decode_entropy(const uint8_t* __res
             int k = 1;
             for (int term = 0; term < 64 && k < 64; term++) {
                 const int code = symbol(ac_table);
-                if (code < 0) { flags |= JPEG_BAD_CODE; break; }
+                if (code < 0) { flags |= SFX_JPEG_BAD_CODE; break; }
                 const int run = code >> 4;
                 size = code & 15;
                 if (size == 0) {
                     if (run != 15) break;                               // EOB
                     k += 16;
-                    if (k > 64) { flags |= JPEG_BAD_RUN; break; }
+                    if (k > 64) { flags |= SFX_JPEG_BAD_RUN; break; }
                     continue;
                 }
                 k += run;
-                if (k > 63) { flags |= JPEG_BAD_RUN; break; }
+                if (k > 63) { flags |= SFX_JPEG_BAD_RUN; break; }
                 out[k++] = (int16_t)jpeg_extend(jpeg_take(reader, size), size);
             }
-            if (reader.n < reader.fake) flags |= JPEG_OUT_OF_BITS;
+            if (reader.n < reader.fake) flags |= SFX_JPEG_OUT_OF_BITS;
         }
     }
     if (flags) atomicOr(status, flags);
@@ -223,7 +203,7 @@ __global__ void __launch_bounds__(64) k_jpeg_decode_entropy(const uint8_t* __res
 // 256 threads = four 8 x 8 blocks, a thread per term in both passes. The planes are padded to whole MCUs: luma mcus_x*hs*8 wide,
 // chroma mcus_x*8. A frame whose status is bad is left alone (the texture keeps what it showed); the first such frame since the last
 // question is noted in `first_bad` = {status, serial} (pinned host memory) for sfx_video_status.
-__global__ void __launch_bounds__(256) k_jpeg_decode_planes(const uint8_t* __restrict__ frame, const int16_t* __restrict__ coefficients, uint8_t* __restrict__ planes,
+__global__ void __launch_bounds__(256) k_jpeg_decode_planes(const sfx_jpeg_frame* __restrict__ frame, const int16_t* __restrict__ coefficients, uint8_t* __restrict__ planes,
                                                             const float* __restrict__ basis, const uint32_t* __restrict__ status, volatile uint32_t* first_bad, uint32_t serial,
                                                             JpegDecodeGeometry g) {
     __shared__ float dct[64];
@@ -242,8 +222,8 @@ __global__ void __launch_bounds__(256) k_jpeg_decode_planes(const uint8_t* __res
     const int b = (int)(block - mcu*g.blocks), component = b < luma_blocks ? 0 : b - luma_blocks + 1;
     if (t < 64) dct[t] = basis[t];
     int value = 0;
-    if (live) value = (int)coefficients[block*64 + k]*(int)frame[JPEG_FRAME_QUANT + (frame[JPEG_FRAME_TQ + component] & 3)*64 + k];
-    terms[q][JPEG_NATURAL_OF[k]] = (float)value;
+    if (live) value = (int)coefficients[block*64 + k]*(int)frame->quant[frame->tq[component] & 3][k];
+    terms[q][JPEG_ZIGZAG.natural_of[k]] = (float)value;
     __syncthreads();
     const int hi = k >> 3, lo = k & 7;
     float acc = 0.0f;

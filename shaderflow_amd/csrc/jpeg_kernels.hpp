@@ -17,8 +17,7 @@
 // header behind the last).
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "jpeg_common.hpp"
 
 namespace sf {
 
@@ -31,7 +30,6 @@ constexpr int JPEG_MAX_HEADER = 1024;
 struct JpegTables {
     const float* dct;               // [8][8]: dct[u][x] = C(u)/2 cos((2x + 1) u pi / 16)
     const float* reciprocal;        // [2][64] natural order: 1/q of luminance, chrominance
-    const uint8_t* zigzag_of;       // [64]: natural index → zigzag position
     const uint32_t* huffman;        // [2][16 DC + 256 AC]: (length << 16) | code; luminance, chrominance
     const uint8_t* header;          // SOI … SOS
     int header_bytes;
@@ -91,7 +89,7 @@ __global__ void __launch_bounds__(384) k_jpeg_coefficients(const uint8_t* __rest
     int q = (int)truncf(scaled + copysignf(0.5f, scaled));                               // round half away from zero
     if (natural) q = min(1023, max(-1023, q));
     const size_t mcu = ((size_t)blockIdx.z*g.mcus_y + blockIdx.y)*g.mcus_x + blockIdx.x;
-    coefficients[mcu*384 + b*64 + tables.zigzag_of[natural]] = (int16_t)q;
+    coefficients[mcu*384 + b*64 + JPEG_ZIGZAG.zigzag_of[natural]] = (int16_t)q;
 }
 
 // ---- 2. Huffman coding of one restart interval per wave ------------------------------------------------------------------------------

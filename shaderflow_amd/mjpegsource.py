@@ -2,7 +2,7 @@
 Motion-JPEG sources of a ShaderVideo, read without ffmpeg: the containers this package writes (mjpeg.py) read back, and the same from
 other encoders — `.avi` (RIFF AVI 1.0 with an `MJPG` video stream) and `.mjpeg` / `.mjpg` (JPEG images back to back). The frames stay
 compressed on the host and over the link; the device decodes them where the texture lives (csrc/jpeg_decode_kernels.hpp defines the
-decode and the layout of a staged frame).
+decode, `sfx_jpeg_frame` of include/shaderflow_hip.h the layout of a staged frame, mirrored here as `STAGED`).
 
   * `parse_header(stream)`: a frame's marker segments up to its scan → `JpegHeader` (geometry, sampling, tables, where the scan
     starts), or ValueError naming the marker or field this decoder does not take: progressive, extended, lossless and arithmetic SOFs,
@@ -30,10 +30,16 @@ from typing import Iterator, Optional
 
 import numpy as np
 
-FRAME_MAGIC = 0x444a4653                                              # "SFJD" (csrc/jpeg_decode_kernels.hpp)
-FRAME_FIXED = 1536
-STATUS_BITS = {1: "a code that matches no Huffman code", 2: "a zero run past the block's 63rd term", 4: "a missing or wrong RSTn marker",
-               8: "the entropy-coded data ran out of bits", 16: "a staged frame the kernels refuse"}
+# include/shaderflow_hip.h: sfx_jpeg_frame, the fixed part of a staged frame (the interval table starts behind it), and SFX_JPEG_*
+FRAME_MAGIC = 0x444a4653                                              # "SFJD"
+STAGED = np.dtype([("magic", "<u4"), ("scan_bytes", "<u4"), ("restart", "<u4"), ("intervals", "<u4"), ("scan_offset", "<u4"), ("components", "<u4"),
+                   ("tq", "u1", 4), ("td", "u1", 4), ("ta", "u1", 4), ("reserved0", "u1", 28), ("quant", "u1", (4, 64)),
+                   ("huffman", [("bits", "u1", 16), ("values", "u1", 256)], 4), ("reserved1", "u1", 128)])
+assert STAGED.itemsize == 1536
+FRAME_FIXED = STAGED.itemsize
+BAD_CODE, BAD_RUN, BAD_RESTART, OUT_OF_BITS, BAD_DESCRIPTOR = 1, 2, 4, 8, 16
+STATUS_BITS = {BAD_CODE: "a code that matches no Huffman code", BAD_RUN: "a zero run past the block's 63rd term", BAD_RESTART: "a missing or wrong RSTn marker",
+               OUT_OF_BITS: "the entropy-coded data ran out of bits", BAD_DESCRIPTOR: "a staged frame the kernels refuse"}
 
 SOF_NAMES = {0xc1: "SOF1 (extended sequential)", 0xc2: "SOF2 (progressive)", 0xc3: "SOF3 (lossless)", 0xc5: "SOF5 (differential sequential)",
              0xc6: "SOF6 (differential progressive)", 0xc7: "SOF7 (differential lossless)", 0xc9: "SOF9 (arithmetic coding)",
@@ -228,17 +234,18 @@ def stage(stream, expected: Optional[JpegHeader], view: np.ndarray, name: str = 
     total = FRAME_FIXED + table_bytes + scan.size
     if total > view.size:
         raise ValueError(f"{name}: {len(data)} bytes need a slot of {total}, the slots hold {view.size}")
-    fixed = view[:FRAME_FIXED]
-    fixed[:] = 0
-    fixed[:24].view("<u4")[:] = (FRAME_MAGIC, scan.size, restart, intervals, FRAME_FIXED + table_bytes, header.components)
+    view[:FRAME_FIXED] = 0
+    fixed = view[:FRAME_FIXED].view(STAGED)[0]
+    fixed["magic"], fixed["scan_bytes"], fixed["restart"], fixed["intervals"] = FRAME_MAGIC, scan.size, restart, intervals
+    fixed["scan_offset"], fixed["components"] = FRAME_FIXED + table_bytes, header.components
     for k, (tq, td, ta) in enumerate(header.selectors):
-        fixed[24 + k], fixed[28 + k], fixed[32 + k] = tq, td, ta
+        fixed["tq"][k], fixed["td"][k], fixed["ta"][k] = tq, td, ta
     for table, values in header.quant.items():
-        fixed[64 + 64*table:128 + 64*table] = np.frombuffer(values, np.uint8)
+        fixed["quant"][table] = np.frombuffer(values, np.uint8)
     for (kind, table), (bits, values) in header.huffman.items():
-        base = 320 + 272*(2*kind + table)
-        fixed[base:base + 16] = np.frombuffer(bits, np.uint8)
-        fixed[base + 16:base + 16 + len(values)] = np.frombuffer(values, np.uint8)
+        entry = fixed["huffman"][2*kind + table]                      # DC 0, DC 1, AC 0, AC 1
+        entry["bits"] = np.frombuffer(bits, np.uint8)
+        entry["values"][:len(values)] = np.frombuffer(values, np.uint8)
     # where the intervals start: behind every FF D0…D7 pair of the scan (an FF inside entropy-coded data is followed by 00)
     offsets = view[FRAME_FIXED:FRAME_FIXED + table_bytes].view("<u4")
     offsets[:] = 0xffffffff

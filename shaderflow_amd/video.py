@@ -166,28 +166,48 @@ class VideoStage:
     copies (`submit`) and k_video_frame into the texture matrix (`step`, or a landing frame of the native sequence). The handle holds
     the matrix' boxes in their order at creation and rolls with every frame it lands: the host rolls its ShaderTexture alike."""
 
-    def __init__(self, video: "ShaderVideo", slots: int):
+    def __init__(self, video: "ShaderVideo", slots):
+        """`slots`: how many, or a function that says it from `frame_bytes` (videosequence.slot_count)"""
         texture = video.texture
         if texture.layers != 1 or texture.components != 3 or texture.dtype != np.uint8:
             raise ValueError("a staged video needs an RGB8 texture with layers = 1")
         boxes = [box.texture for (_, _, box) in texture.boxes]
         self.serials = tuple(box.serial for box in boxes)              # which device textures the handle writes into
         self.planar, self.compressed = video.format == "i420", video.format == "mjpeg"
-        self.slots, self.handle = slots, N.Handle()
+        self.width, self.height, self.jpeg = video.width, video.height, video.jpeg
+        self.frame_bytes = video.capacity if self.compressed else video.width*video.height*3//(2 if self.planar else 1)   # what a slot holds
+        self.slots, self.handle = slots(self.frame_bytes) if callable(slots) else slots, N.Handle()
         handles = (N.Handle*len(boxes))(*[box.handle for box in boxes])
         if self.compressed:
             jpeg = video.jpeg
             N.check(N.lib().sfx_video_create_mjpeg(video.scene.context.handle, handles, texture.temporal, video.width, video.height, jpeg.components,
-                                                   jpeg.sampling[0], jpeg.sampling[1], video.capacity, slots, C.byref(self.handle)))
+                                                   jpeg.sampling[0], jpeg.sampling[1], video.capacity, self.slots, C.byref(self.handle)))
             return
         N.check(N.lib().sfx_video_create(video.scene.context.handle, handles, texture.temporal, video.width, video.height,
-                                         N.VIDEO_I420 if self.planar else N.VIDEO_RGB24, slots, C.byref(self.handle)))
+                                         N.VIDEO_I420 if self.planar else N.VIDEO_RGB24, self.slots, C.byref(self.handle)))
 
     def view(self, slot: int) -> np.ndarray:
         """The slot's pinned frame as a 1-D uint8 array (waits until the frame it held before has been consumed)"""
         pointer, nbytes = C.c_void_p(), C.c_size_t()
         N.check(N.lib().sfx_video_slot(self.handle, slot, C.byref(pointer), C.byref(nbytes)))
         return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(C.c_uint8)), shape=(nbytes.value,))
+
+    def fill(self, view: np.ndarray, frame, label: str) -> Optional[int]:
+        """One source frame — an rgb array, an i420 array or a JPEG stream, as the video's format says — into the pinned `view`; returns
+        the bytes to `submit` (None: the format's fixed size). `label` names the frame in an error."""
+        if self.compressed:                                           # the stream's tables, interval starts and scan; only they are copied
+            from shaderflow_amd.mjpegsource import stage
+            return stage(frame, self.jpeg, view, label)
+        frame = np.asarray(frame, np.uint8)
+        if frame.size != self.frame_bytes:
+            raise ValueError(f"{label}: {'an i420' if self.planar else 'an rgb'} frame of {self.width} x {self.height} has {self.frame_bytes} bytes, the source gave {frame.size}")
+        np.copyto(view.reshape(frame.shape), frame)                   # (a memory-mapped clip is read here, without the GIL)
+        return None
+
+    def put_back(self, held):
+        """What goes back in front of the source for a frame that was taken from it and not drawn: `held` is the stream a compressed
+        frame came as, or the pinned view an uncompressed one was copied into — a copy of it, shaped as the source yields frames"""
+        return held if self.compressed else held.copy().reshape((-1,) if self.planar else (self.height, self.width, 3))
 
     def submit(self, slot: int, nbytes: Optional[int] = None) -> None:
         """`nbytes`: the bytes the frame has (a compressed frame: only they are copied)"""
@@ -323,17 +343,17 @@ class ShaderVideo(ShaderModule):
             return
         if self.format == "mjpeg":
             self._read += 1                                             # (a damaged frame is passed over: the next update() shows the next one)
-            self._show_staged(frame)
+            self._show_staged(frame, self._read - 1)
             return
         if self.format == "i420":
-            self._show_staged(frame)
+            self._show_staged(frame, self._read)
         else:
             frame = np.ascontiguousarray(np.flip(np.asarray(frame, np.uint8), axis=0))
             self.texture.roll()
             self.texture.write(frame)
         self._read += 1
 
-    def _show_staged(self, frame) -> None:
+    def _show_staged(self, frame, source: int) -> None:
         """A planar frame through k_video_frame, a compressed one through the decode kernels — the one definition of either: a pinned
         slot, its copy, the launch"""
         boxes = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
@@ -342,25 +362,15 @@ class ShaderVideo(ShaderModule):
             self._stage = None
         if self._stage is None:
             self._stage = VideoStage(self, slots=1)
-        if self.format == "mjpeg":
-            from shaderflow_amd.mjpegsource import describe_status, stage
-            source = self._read - 1
-            self._stage.submit(0, stage(frame, self.jpeg, self._stage.view(0), f"{self.name}: source frame {source}"))
-            self._stage.step(0)
-            bad = self._stage.bad_frame(wait=True)
-            if bad is not None:                                       # the device rolled its matrix and left the box alone: so does the host
-                self.texture.roll()
-                self._stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
-                raise RuntimeError(f"{self.name}: source frame {source} could not be decoded: {describe_status(bad[1])}")
-        else:
-            frame = np.asarray(frame, np.uint8).reshape(-1)
-            if frame.size != self.width*self.height*3//2:
-                raise ValueError(f"{self.name}: an i420 frame of {self.width} x {self.height} has {self.width*self.height*3//2} bytes, not {frame.size}")
-            np.copyto(self._stage.view(0), frame)
-            self._stage.submit(0)
-            self._stage.step(0)
-        self.texture.roll()
-        self._stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
+        stage = self._stage
+        stage.submit(0, stage.fill(stage.view(0), frame, f"{self.name}: source frame {source}"))
+        stage.step(0)
+        bad = stage.bad_frame(wait=True)                              # (only a compressed frame can be bad: nothing is waited for otherwise)
+        self.texture.roll()                                           # (the device rolled its matrix even when it left a bad frame's box alone)
+        stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
+        if bad is not None:
+            from shaderflow_amd.mjpegsource import describe_status
+            raise RuntimeError(f"{self.name}: source frame {source} could not be decoded: {describe_status(bad[1])}")
         self.texture.refresh_host_copy()
 
     def destroy(self) -> None:

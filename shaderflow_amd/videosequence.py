@@ -168,21 +168,20 @@ class VideoSequence(FrameSource):
             for i in range(count):
                 if slots[i] >= 0:
                     self.staged.pop(int(self.want[first + i]), None)
-                    self.streams.pop(int(self.want[first + i]), None)
+                    self.held.pop(int(self.want[first + i]), None)
             self.free.extend(used)
             self.landed += len(used)
             self.lock.notify_all()
         self.video.texture.roll(len(used))                            # the native call rolled its own copy of the matrix once per landing
-        if self.video.format == "mjpeg":
-            error = self.undecoded(wait=False)
-            if error is not None:
-                self.error = error
-                raise error
+        error = self.undecoded(wait=False)
+        if error is not None:
+            self.error = error
+            raise error
 
     def undecoded(self, wait: bool) -> Optional[RuntimeError]:
         """A compressed frame the device could not decode fails the export: the error that says so, or None (the kernels noted the
         first such frame; asking costs no wait unless `wait` says so: a damaged frame is then found a chunk later, or behind the run)"""
-        bad = self.stage.bad_frame(wait) if self.stage is not None else None
+        bad = self.stage.bad_frame(wait) if self.stage is not None else None      # (an uncompressed frame is never bad, and nothing waits for one)
         if bad is None:
             return None
         from shaderflow_amd.mjpegsource import describe_status
@@ -198,11 +197,8 @@ class VideoSequence(FrameSource):
 
     def read_frames(self, source, first: int, needed: int) -> None:
         """The reader thread: source frames first, first + 1, … into free slots, each submitted as soon as it is whole"""
-        stage, video, nbytes = self.stage, self.video, self.frame_bytes
-        readinto = getattr(source, "readinto", None) if video.format == "i420" else None
-        compressed, size = video.format == "mjpeg", None
-        if compressed:
-            from shaderflow_amd.mjpegsource import stage as stage_frame
+        stage, video = self.stage, self.video
+        readinto = getattr(source, "readinto", None) if stage.planar else None
         try:
             for index in range(first, first + needed):
                 with self.lock:
@@ -212,6 +208,7 @@ class VideoSequence(FrameSource):
                         return
                     slot = self.free.pop(0)
                 view = stage.view(slot)                               # (waits for the kernel that consumed the slot's last frame)
+                size, held = None, view                               # `held`: what `put_back` gets should nobody draw the frame
                 if readinto is not None:
                     whole = readinto(view)
                 else:
@@ -220,14 +217,8 @@ class VideoSequence(FrameSource):
                     except StopIteration:
                         whole = False
                     else:
-                        if compressed:                                # the stream's tables, interval starts and scan into the slot; only they are copied
-                            size = stage_frame(frame, video.jpeg, view, f"{video.name}: source frame {index}")
-                            self.streams[index] = frame
-                        else:
-                            frame = np.asarray(frame, np.uint8)
-                            if frame.size != nbytes:
-                                raise ValueError(f"{video.name}: a frame of {video.width} x {video.height} has {nbytes} bytes, the source gave {frame.size}")
-                            np.copyto(view.reshape(frame.shape), frame)   # (a memory-mapped clip is read here, without the GIL)
+                        size = stage.fill(view, frame, f"{video.name}: source frame {index}")
+                        held = view if size is None else frame        # (a frame with a size of its own came as a stream: that goes back)
                         whole = True
                 with self.lock:
                     if not whole:
@@ -236,12 +227,12 @@ class VideoSequence(FrameSource):
                         self.lock.notify_all()
                         return
                     if self.stop:                                     # (the frame is whole but nobody will draw it: it goes back to the source)
-                        self.kept[index] = self.streams.pop(index) if compressed else view.copy()
+                        self.kept[index] = stage.put_back(held)
                         return
                 stage.submit(slot, size)
                 with self.lock:
                     self.staged[index] = slot
-                    self.views[slot] = view
+                    self.held[index] = held
                     self.lock.notify_all()
         except BaseException as error:                                # whatever the source raised fails the export, in the thread that drives it
             with self.lock:
@@ -261,14 +252,12 @@ class VideoSequence(FrameSource):
         self.first_read, self.was_exhausted, self.source = video._read, video._exhausted, video._reader
         # every landing of the export, were the source endless; where it ends is learnt from the reader
         self.want = landing_frames(times, video.fps, self.first_read) if not self.was_exhausted else np.full(total, -1, np.int64)
-        self.frame_bytes = video.capacity if video.format == "mjpeg" else video.width*video.height*3//(2 if video.format == "i420" else 1)
-        self.streams = {}                                              # source frame → the compressed stream staged for it (they go back as bytes)
-        slots = slot_count(self.frame_bytes)
+        self.stage = VideoStage(video, slot_count)
+        slots = self.stage.slots
         self.per_chunk = slots//2
-        self.free, self.staged, self.views, self.kept = list(range(slots)), {}, {}, {}
+        self.free, self.staged, self.held, self.kept = list(range(slots)), {}, {}, {}   # held: source frame → its stream, or its slot's view
         self.total, self.error, self.late, self.stop, self.exhausted_at = None, None, None, False, None
         self.landed = 0
-        self.stage = VideoStage(video, slots)
         self.thread = threading.Thread(target=self.read_frames, args=(self.source, self.first_read, int((self.want >= 0).sum())),
                                        name="shaderflow-video-reader", daemon=True)
         self.thread.start()
@@ -285,20 +274,14 @@ class VideoSequence(FrameSource):
         if video._exhausted and not self.was_exhausted:
             logger.warning(f"{video.name}: source ended after {video._read} frames, holding the last one")
         # frames taken from the source but not drawn go back in front of it, in order, for a later update()
-        if video.format == "mjpeg":
-            ahead = {index: self.streams[index] for index in self.staged}
-        else:
-            ahead = {index: self.views[slot].copy() for index, slot in self.staged.items()}
+        ahead = {index: self.stage.put_back(self.held[index]) for index in self.staged}
         ahead.update(self.kept)
-        if ahead and video.format == "mjpeg":
+        if ahead:
             video._reader = itertools.chain([ahead[index] for index in sorted(ahead)], self.source)
-        elif ahead:
-            shape = (-1,) if video.format == "i420" else (video.height, video.width, 3)
-            video._reader = itertools.chain([ahead[index].reshape(shape) for index in sorted(ahead)], self.source)
         # the host copies of the boxes the run wrote into, as `texture.write` keeps them: read back from the device
         for depth in range(min(self.landed, video.texture.temporal) if done else 0):
             video.texture.refresh_host_copy(depth)
-        if video.format == "mjpeg" and self.error is None:
+        if self.error is None:
             self.late = self.undecoded(wait=True)
 
     def finished(self, done: int, total: int) -> bool:
@@ -308,4 +291,4 @@ class VideoSequence(FrameSource):
         if self.stage is not None:
             self.stage.release()
             self.stage = None
-        self.views = {}
+        self.held = {}

@@ -310,6 +310,46 @@ def test_chunks_of_seven_frames(kind, clip_fps, monkeypatch, tmp_path):
     assert_same_host_state(loop, scene)
 
 
+def test_one_slot_filler_serves_the_frame_loop_and_the_sequence(monkeypatch):
+    """`VideoStage.fill` behind `update()` and behind the sequence's reader: the same texture bytes for an rgb, an i420 and a 4:2:0
+    Motion-JPEG clip of 5 frames at 40 x 24 (a partial MCU at 4:2:0; `slot_count` is at its clamp there), and the same words for a
+    wrong-sized i420 frame"""
+    import sys
+    from pathlib import Path
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    import jpeg_ref as J
+    from shaderflow_amd.videosequence import SLOTS_MAX
+    w, h, count = 40, 24, 5
+    rng = np.random.default_rng(7)
+    rgb = rng.integers(0, 256, (count, h, w, 3), dtype=np.uint8)
+    planar = rng.integers(0, 256, (count, w*h*3//2), dtype=np.uint8)
+    streams = [J.encode(J.picture("noise", w, h, seed), 90) for seed in range(count)]
+    clips = {"rgb": lambda: dict(frames=iter(rgb), width=w, height=h, fps=FPS),
+             "i420": lambda: dict(frames=iter(planar), width=w, height=h, fps=FPS, format="i420"),
+             "mjpeg": lambda: dict(frames=iter(streams), fps=FPS, format="mjpeg")}
+    for kind, source in clips.items():
+        loop, want, scene, got = both_ways(video_scene(source, temporal=count), count + 1, monkeypatch)      # (nothing lands on the first scene frame)
+        assert scene.video._read == count and scene.video.format == (None if kind == "rgb" else kind)
+        assert scene.video_sequence.per_chunk == SLOTS_MAX//2
+        assert_same_host_state(loop, scene)                            # every box of the matrix: the five frames' texture bytes
+        boxes = [scene.video.texture.get_box(depth).texture.read() for depth in range(count)]
+        assert len({box.tobytes() for box in boxes}) == count, kind
+
+    def short_frame_at_two():
+        for k, frame in enumerate(planar):
+            yield frame[:-1] if k == 2 else frame
+    words = {}
+    for mode in ("0", "1"):
+        monkeypatch.setenv("SHADERFLOW_VIDEO_SEQUENCE", mode)
+        scene = video_scene(lambda: dict(frames=short_frame_at_two(), width=w, height=h, fps=FPS, format="i420"))()
+        with pytest.raises(ValueError) as raised:
+            scene.main(width=W, height=H, fps=FPS, time=(count + 1)/FPS, freewheel=True)
+        assert (scene.video_sequence is not None) == (mode == "1")
+        words[mode] = str(raised.value)
+    assert words["0"] == words["1"]
+    assert all(part in words["1"] for part in ("source frame 2", f"{w} x {h}", str(w*h*3//2), str(w*h*3//2 - 1)))
+
+
 def test_the_video_example_takes_the_sequence():
     from examples.scenes import Video
     scene = type("Video", (Video,), {"clip": (rgb_clip(6), 30.0)})()

@@ -5,6 +5,8 @@ decode against libjpeg's pixels (stored by tests/golden/make_golden_jpeg_streams
 """
 from __future__ import annotations
 
+import hashlib
+import json
 import os
 import struct
 import sys
@@ -22,6 +24,9 @@ from shaderflow_amd import mjpegsource as M  # noqa: E402
 from shaderflow_amd.mjpeg import AviWriter  # noqa: E402
 
 GOLDEN = Path(__file__).resolve().parent/"golden"/"jpeg_streams.npz"
+# tests/golden/make_golden_staged.py: every stream's staged frame as `stage` wrote it before it filled the `STAGED` record, and the
+# Annex K Huffman tables as the device library's encoder writes them into its header
+STAGED_GOLDEN = json.loads((Path(__file__).resolve().parent/"golden"/"staged_sha256.json").read_text())
 # the largest difference between the restatement and libjpeg's pixels (Pillow 12.2) on each stored stream, measured with this file's
 # restatement; the check is deterministic, so it has no margin
 PILLOW_GAP = 3
@@ -193,6 +198,32 @@ def test_the_staged_frame_says_what_the_stream_says(name):
         assert list(view[base:base + 16]) == bits and list(view[base + 16:base + 16 + len(values)]) == values
     for table, quant in info["quant"].items():
         assert np.array_equal(view[64 + 64*table:128 + 64*table][np.argsort(J.ZIGZAG)], quant)
+
+
+def test_the_staged_record_mirrors_the_header_struct():
+    fields = M.STAGED.fields
+    assert M.STAGED.itemsize == 1536 == M.FRAME_FIXED
+    assert [fields[name][1] for name in ("tq", "td", "ta", "quant", "huffman")] == [24, 28, 32, 64, 320]
+    assert [fields[name][1] for name in ("magic", "scan_bytes", "restart", "intervals", "scan_offset", "components")] == [0, 4, 8, 12, 16, 20]
+    assert M.STAGED["huffman"].subdtype[0].itemsize == 16 + 256 and sorted(M.STATUS_BITS) == [1, 2, 4, 8, 16]
+
+
+def test_every_stream_has_a_recorded_staged_frame():
+    assert sorted(STAGED_GOLDEN["staged"]) == sorted(STREAMS)
+
+
+@pytest.mark.parametrize("name", sorted(STREAMS))
+def test_the_staged_frame_is_byte_for_byte_the_recorded_one(name):
+    stream = STREAMS[name][0]
+    header = M.parse_header(stream)
+    view = np.full(M.capacity_for(header, len(stream)), 0xaa, np.uint8)
+    total = M.stage(stream, header, view)
+    assert hashlib.sha256(view[:total].tobytes()).hexdigest() == STAGED_GOLDEN["staged"][name]
+
+
+def test_annex_k_is_the_device_library_s():
+    recorded = {(int(key[0]), int(key[1])): (bytes.fromhex(bits), bytes.fromhex(values)) for key, (bits, values) in STAGED_GOLDEN["annex_k"].items()}
+    assert recorded == M.ANNEX_K
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------------------------
