@@ -365,6 +365,16 @@ static float np_pairwise_sum_f32(const float* a, int64_t n, int64_t stride) {
     return lo + hi;
 }
 
+/* np.mean / np.std of a whole float32 array (numpy 2.x): the buffered iterator hands the flat sequence to the pairwise sum in runs
+ * of np.getbufsize() = 8192 elements, and the runs' sums are added in order (tests/loudness_ref.py, pinned by test_host_loudness.py) */
+#define NP_BUFFER_RUN 8192
+static float np_buffered_sum_f32(const float* a, int64_t n) {
+    float total = 0.0f;
+    for (int64_t first = 0; first < n; first += NP_BUFFER_RUN)
+        total = total + np_pairwise_sum_f32(a + first, n - first < NP_BUFFER_RUN ? n - first : NP_BUFFER_RUN, 1);
+    return total;
+}
+
 /* waveform.py:80-87: chunks = data[:, -(chunk*points + off + 1) : -(off + 1)].reshape(c, -1, chunk);
  * reducer (:15-22) over axis 2; transposed to (points, channels) */
 void sfo_waveform_row(const float* pcm, int64_t total, int channels, int64_t tell,
@@ -411,17 +421,15 @@ void sfo_volume_std(const float* pcm, int64_t total, int channels, int64_t tell,
         for (int i = 0; i < n; i++)
             x[(int64_t)c*n + i] = stream_sample(pcm, total, c, tell - n - 1 + i);
     for (int64_t i = 0; i < count; i++) { float s = x[i]*x[i]; q[i] = s; }
-    float mean_sq = np_pairwise_sum_f32(q, count, 1)/(float)count;
+    float mean_sq = np_buffered_sum_f32(q, count)/(float)count;
     float rms = sqrtf(mean_sq);
     float twice = 2.0f*rms;
     *volume_target = twice*(float)1.4142135623730951;                   /* python float 2**0.5 → f32 (NEP 50) */
 
-    /* np.std on the strided (channels, n) view: per-row pairwise sums added in row order */
-    float sum = 0.0f;
-    for (int c = 0; c < channels; c++) sum = sum + np_pairwise_sum_f32(x + (int64_t)c*n, n, 1);
-    float mean = sum/(float)count;
+    /* np.std: mean and variance over the flat channel-major sequence, the same runs */
+    float mean = np_buffered_sum_f32(x, count)/(float)count;
     for (int64_t i = 0; i < count; i++) { float d = x[i] - mean; float s = d*d; q[i] = s; }
-    float var = np_pairwise_sum_f32(q, count, 1)/(float)count;
+    float var = np_buffered_sum_f32(q, count)/(float)count;
     *std_target = sqrtf(var);
     free(x); free(q);
 }

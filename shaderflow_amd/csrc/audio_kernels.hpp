@@ -247,14 +247,20 @@ __global__ __launch_bounds__(256) void k_waveform_rows(const float* __restrict__
 
 // ---- K5 ---------------------------------------------------------------------------------------------------
 // One block per frame over channels*n samples: volume target = 2*sqrt(mean(x²))*sqrt(2) and std target
-// = sqrt(mean((x-mean)²)), with numpy's float32 arithmetic (audio/module.py:74-75,457-458): its means are float32 PAIRWISE sums
-// (pairwise_sum_FLOAT: runs of at most 128 values summed with eight accumulators, longer runs split in two at a multiple of 8 and
-// the halves added), so the targets are the reference's bits. They have to be: the DynamicNumbers these targets drive stop moving
-// when |target - value| < 1e-6 (dynamics.py:222-225), and a target one ulp away flips that branch — on the benchmark's sweep the
-// volume's trajectory left the reference's for good at frame 803 when the sums were taken in float64.
-// The tree of a sum is fixed by its length: thread 0 lists the leaf runs depth first, every thread sums leaves, thread 0 adds the
-// leaves back up the same tree (no recursion on the device: an explicit stack, depth < 32).
-constexpr int PAIRWISE_LEAVES = 1024;                               // 8 820 values (0.1 s of 44.1 kHz stereo) have 128 leaves
+// = sqrt(mean((x-mean)²)), with numpy's float32 arithmetic (audio/module.py:74-75,457-458). What numpy does for np.mean / np.std of a
+// whole float32 array, the strided (channels, n) slice of the ring and its contiguous temporaries alike: its buffered iterator cuts the
+// flat, channel-major sequence into runs of np.getbufsize() = 8192 elements, each run is summed PAIRWISE (pairwise_sum_FLOAT: at most
+// 128 values with eight accumulators, longer runs split in two at a multiple of 8 and the halves added), and the runs' sums are added
+// in order to a float32 zero. All three sums here (x², x, (x-mean)²) go through buffered_sum_block, which does exactly that.
+// tests/loudness_ref.py restates the order in numpy scalars; test_host_loudness.py holds the restatement to numpy and to the
+// reference's captured targets, test_gpu_audio.py::test_volume_std_equals_numpy holds this kernel to the restatement, bit for bit.
+// The bits matter: the DynamicNumbers these targets drive stop moving when |target - value| < 1e-6 (dynamics.py:222-225), and a target
+// one ulp away flips that branch — on the benchmark's sweep the volume's trajectory left the reference's for good at frame 803 when
+// the sums were taken in float64.
+// The tree of a run is fixed by its length: thread 0 lists the leaf runs depth first, every thread sums leaves, thread 0 adds the
+// leaves back up the same tree (no recursion on the device: an explicit stack; a run of 8192 is at most 8 levels deep).
+constexpr int NUMPY_RUN = 8192;                                     // np.getbufsize(), asserted by test_host_loudness.py
+constexpr int PAIRWISE_LEAVES = 128;                                // every leaf of a run longer than 128 holds at least 64 values (65 leaves at most)
 struct PairwiseScratch { int start[PAIRWISE_LEAVES]; int len[PAIRWISE_LEAVES]; float part[PAIRWISE_LEAVES]; int leaves; };
 
 template <class At>
@@ -274,20 +280,17 @@ __device__ float pairwise_leaf(int start, int n, const At& at) {     // n <= 128
     return res;
 }
 
-// numpy's pairwise sum of at(first) ... at(first + n - 1), called by every thread of the block; the result is valid in thread 0 only
+// numpy's pairwise sum of at(first) ... at(first + n - 1), n <= NUMPY_RUN, called by every thread of the block; the result is valid in
+// thread 0 only
 template <class At>
 __device__ float pairwise_sum_block(int first, int n, const At& at, PairwiseScratch& sh) {
     struct Node { int s, l, stage; float lo; };
     if (threadIdx.x == 0) {                                           // the leaves, left to right
-        Node st[32]; int top = 0, leaves = 0;
+        Node st[16]; int top = 0, leaves = 0;
         st[0] = {first, n, 0, 0.0f};
         while (top >= 0) {
             const Node f = st[top--];
-            if (f.l <= 128) {
-                if (leaves < PAIRWISE_LEAVES) { sh.start[leaves] = f.s; sh.len[leaves] = f.l; }
-                leaves++;
-                continue;
-            }
+            if (f.l <= 128) { sh.start[leaves] = f.s; sh.len[leaves] = f.l; leaves++; continue; }
             int n2 = f.l/2; n2 -= n2 % 8;
             st[++top] = {f.s + n2, f.l - n2, 0, 0.0f};
             st[++top] = {f.s, n2, 0, 0.0f};
@@ -295,18 +298,16 @@ __device__ float pairwise_sum_block(int first, int n, const At& at, PairwiseScra
         sh.leaves = leaves;
     }
     __syncthreads();
-    const bool listed = sh.leaves <= PAIRWISE_LEAVES;                 // (longer sums: thread 0 sums the leaves itself below)
-    if (listed)
-        for (int i = threadIdx.x; i < sh.leaves; i += blockDim.x) sh.part[i] = pairwise_leaf(sh.start[i], sh.len[i], at);
+    for (int i = threadIdx.x; i < sh.leaves; i += blockDim.x) sh.part[i] = pairwise_leaf(sh.start[i], sh.len[i], at);
     __syncthreads();
     float result = 0.0f;
     if (threadIdx.x == 0) {                                           // lo + hi up the tree, in the order of the recursion
-        Node st[32]; int top = 0, leaf = 0;
+        Node st[16]; int top = 0, leaf = 0;
         float ret = 0.0f;
         st[0] = {first, n, 0, 0.0f};
         while (top >= 0) {
             Node& f = st[top];
-            if (f.l <= 128) { ret = listed ? sh.part[leaf] : pairwise_leaf(f.s, f.l, at); leaf++; top--; continue; }
+            if (f.l <= 128) { ret = sh.part[leaf++]; top--; continue; }
             int n2 = f.l/2; n2 -= n2 % 8;
             if (f.stage == 0) { f.stage = 1; st[top + 1] = {f.s, n2, 0, 0.0f}; top++; }
             else if (f.stage == 1) { f.lo = ret; f.stage = 2; st[top + 1] = {f.s + n2, f.l - n2, 0, 0.0f}; top++; }
@@ -318,23 +319,30 @@ __device__ float pairwise_sum_block(int first, int n, const At& at, PairwiseScra
     return result;
 }
 
+// numpy's sum of at(0) ... at(count - 1): float32 zero plus the pairwise sum of each run of 8192, in order; valid in thread 0 only
+template <class At>
+__device__ float buffered_sum_block(int count, const At& at, PairwiseScratch& sh) {
+    float total = 0.0f;
+    for (int first = 0; first < count; first += NUMPY_RUN)
+        total = total + pairwise_sum_block(first, min(NUMPY_RUN, count - first), at, sh);
+    return total;
+}
+
 __global__ __launch_bounds__(256) void k_volume_std(const float* __restrict__ pcm, long total, int channels,
                                                     const long* __restrict__ tell, int n, float* __restrict__ out) {
     __shared__ PairwiseScratch sh;
+    __shared__ float mean_sh;
     const int frame = blockIdx.x;
     const long first = tell[frame] - n - 1;
     const int count = n*channels;
-    // the last n samples of every channel as one (channels, n) float32 array, element e = channel e/n, sample e%n
+    // the last n samples of every channel as one (channels, n) float32 array, flat: element e = channel e/n, sample e%n
     auto x = [&](int e) { return stream_at(pcm, total, e / n, first + (e % n)); };
-    const float mean_sq = pairwise_sum_block(0, count, [&](int e) { const float v = x(e); return v*v; }, sh)/(float)count;
-    // np.std: the mean over the (channels, n) array is the channels' pairwise sums added in row order, then the pairwise sum of (x - mean)²
-    float sum = 0.0f;
-    for (int c = 0; c < channels; c++) sum = sum + pairwise_sum_block(c*n, n, x, sh);
-    __shared__ float mean_sh;
+    const float mean_sq = buffered_sum_block(count, [&](int e) { const float v = x(e); return v*v; }, sh)/(float)count;
+    const float sum = buffered_sum_block(count, x, sh);
     if (threadIdx.x == 0) mean_sh = sum/(float)count;
     __syncthreads();
     const float mean = mean_sh;
-    const float var = pairwise_sum_block(0, count, [&](int e) { const float d = x(e) - mean; return d*d; }, sh)/(float)count;
+    const float var = buffered_sum_block(count, [&](int e) { const float d = x(e) - mean; return d*d; }, sh)/(float)count;
     if (threadIdx.x == 0) {
         const float rms = sqrtf(mean_sq);
         out[2*frame] = (2.0f*rms)*(float)1.4142135623730951;

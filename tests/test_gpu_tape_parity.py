@@ -4,7 +4,7 @@ test_gpu_fullsize.py compares the tape's frames with the oracle running on the O
 only ask for the edge-aware bound (a supersample on a bar's outline may change sides). Here the two stages are split:
 
   audio   the device tape of every frame of the benchmark's 60 s sweep (3 600 frames, 60 batches) against oracle_audio_tape within
-          1e-5 relative; a 300-frame tape byte-equal to the 60-frame one (bank rotation, state hand-over)
+          1e-5 relative, the loudness targets bit for bit; a 300-frame tape byte-equal to the 60-frame one (bank rotation, state hand-over)
   pixels  whole frames of every tape configuration bench.py times against oracle_tape_frame fed the DEVICE's own tape values of that
           frame — max <= 1 LSB on every value: C3 (60- and 300-frame launches, per-frame tables, the fixed blur bound of the tape
           launch), C2 (no SSAA: two passes), 1920x1080 2xSSAA, MusicBars and Waveform at 3840x2160 2xSSAA
@@ -160,7 +160,8 @@ def test_audio_tape_of_every_frame_of_the_benchmark_clip(c3, clip):
         bad = ~np.isclose(t[name], want, rtol=1e-5, atol=1e-9*peak)
         assert not bad.any(), (name, np.argwhere(bad)[:5].tolist(), float(np.abs(t[name] - want).max()))
     assert np.allclose(t["rows"], oracle.rows, rtol=1e-5, atol=1e-9), float(np.abs(t["rows"] - oracle.rows).max())
-    assert np.allclose(t["loudness"], oracle.loudness, rtol=1e-5, atol=1e-12), np.argwhere(~np.isclose(t["loudness"], oracle.loudness, rtol=1e-5, atol=1e-12))[:5]
+    # the loudness targets are numpy's bits on both sides (tests/loudness_ref.py has the order; the oracle is held to it on the CPU)
+    assert np.array_equal(t["loudness"].astype(np.float64), oracle.loudness), np.argwhere(t["loudness"] != oracle.loudness)[:5].tolist()
     for column, want in ((2, oracle.volume), (3, oracle.integral), (4, oracle.std)):
         bad = ~np.isclose(t["uniforms"][:, column], want, rtol=1e-5, atol=1e-9)
         assert not bad.any(), (column, np.argwhere(bad)[:5].ravel().tolist())
