@@ -482,6 +482,17 @@ int sfx_video_status(sfx_handle video, int wait, int64_t* frame, uint32_t* statu
  * top row first. Synchronous. */
 int sfx_jpeg_decode(sfx_handle ctx, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling,
                     int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status);
+/* Test entry: sfx_jpeg_decode with the entropy path chosen (csrc/jpeg_decode_kernels.hpp, 1b: a lane per subsequence, synchronisation
+ * rounds, a scan, a write pass, the lane-per-interval kernel as the fall-back). `subsequence_bytes` 2 … 2^20: that path with pieces of
+ * this size; 0: the path and the production values a video handle would take for this frame (SHADERFLOW_JPEG_SYNC=0 / 1 force the
+ * lane-per-interval kernel / the subsequence path; else the subsequence path when scan_bytes / intervals is at least four production
+ * subsequences of 64 bytes). `round_budget`: rounds per phase, 0 … 255 (more count as 255), negative: the production value. `info` (may be null):
+ * {subsequences (lanes; 0: the lane-per-interval kernel ran alone), rounds used, 1 when the rounds did not settle and the
+ * lane-per-interval kernel decoded the frame}. sfx_jpeg_decode itself stays the lane-per-interval kernel. Synchronous. */
+int sfx_jpeg_decode_sync(sfx_handle ctx, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling,
+                         int subsequence_bytes, int round_budget, int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status, uint32_t* info /* [3] */);
+/* How many landed Motion-JPEG frames of the handle took the subsequence path, and how many the lane-per-interval kernel alone */
+int sfx_video_jpeg_paths(sfx_handle video, uint64_t* subsequence_frames, uint64_t* interval_frames);
 /* video.py:57-66 has no counterpart: stops the copy stream, then frees the staging */
 int sfx_video_destroy(sfx_handle video);
 

@@ -215,6 +215,9 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_video_submit_bytes": (C.c_int, [Handle, C.c_int, C.c_size_t]),
     "sfx_video_status": (C.c_int, [Handle, C.c_int, P(C.c_int64), P(C.c_uint32)]),
     "sfx_jpeg_decode": (C.c_int, [Handle, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32)]),
+    "sfx_jpeg_decode_sync": (C.c_int, [Handle, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       P(C.c_uint32), P(C.c_uint32)]),
+    "sfx_video_jpeg_paths": (C.c_int, [Handle, P(C.c_uint64), P(C.c_uint64)]),
     "sfx_sequence_run": (C.c_int, [Handle, P(Sequence)]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),
     "sfx_device_free": (C.c_int, [Handle, C.c_void_p]),

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <mutex>
 
 using namespace sf;
@@ -32,7 +33,11 @@ struct Video : Object {
     std::mutex guard;
     // SFX_VIDEO_MJPEG: every slot holds a staged frame of its own length (jpeg_decode_kernels.hpp), at most frame_bytes of them
     JpegDecodeGeometry jpeg{};
-    std::vector<uint32_t> intervals;        // restart intervals of the frame each slot holds
+    std::vector<uint32_t> intervals, scan_bytes;     // restart intervals and scan bytes of the frame each slot holds
+    void* sync_block = nullptr;             // the subsequence path's records (jpeg_decode_kernels.hpp, 1b), for capacity/JPEG_SYNC_SUBSEQUENCE lanes and one per interval
+    JpegSyncScratch sync{};
+    uint32_t sync_bytes = 0;                // a subsequence's bytes on this handle
+    uint64_t sync_frames = 0, serial_frames = 0;    // landed frames by entropy path (sfx_video_jpeg_paths)
     void* staging_block = nullptr;          // the slots' device staging as one allocation (`staging` holds views into it)
     void* scratch = nullptr;                // [basis 64 f32][status: a word per slot][coefficients][planes]: the decode kernels run in stream order, one frame's scratch serves all slots
     float* basis = nullptr; uint32_t* status = nullptr; int16_t* coefficients = nullptr; uint8_t* planes = nullptr;
@@ -56,6 +61,7 @@ static void video_release(Video* v) {
     if (v->staging_block) hipFree(v->staging_block);
     else for (auto p : v->staging) if (p) hipFree(p);
     if (v->scratch) hipFree(v->scratch);
+    if (v->sync_block) hipFree(v->sync_block);
     if (v->first_bad) hipHostFree(v->first_bad);
     if (v->copy) hipStreamDestroy(v->copy);
     v->magic = 0;
@@ -86,6 +92,42 @@ static int jpeg_scratch(const JpegDecodeGeometry& g, int slots, void** scratch, 
     return SFX_OK;
 }
 
+// The production values of the subsequence path: a subsequence's bytes (64, 128 and 256 were measured, 64 was the fastest on every clip:
+// DESIGN.md §7c, profiles/mjpeg_in_bench.txt), the rounds of a phase (the most the two phases allow; rounds end when nothing changes), and
+// how many subsequences a frame's mean restart interval must hold at least for the frame to take the path.
+enum { JPEG_SYNC_SUBSEQUENCE = 64, JPEG_SYNC_ROUNDS = 255, JPEG_SYNC_RULE = 4 };
+
+// Records for frames of `capacity` bytes cut into pieces of `subsequence` bytes: [records][handoff][rounds: two phases][control: 64 bytes]
+static int jpeg_sync_scratch(const JpegDecodeGeometry& g, size_t capacity, uint32_t subsequence, void** block, JpegSyncScratch* out) {
+    const size_t mcus = (size_t)g.mcus_x*g.mcus_y;
+    const size_t records = capacity/subsequence + 1 + std::min(mcus, capacity/4);      // (an interval costs the frame a table word)
+    const size_t workgroups = (records + JPEG_SYNC_LANES - 1)/JPEG_SYNC_LANES;
+    if (records > 0xffffffffull) return SFX_E_TOO_LARGE;
+    const size_t record_bytes = records*sizeof(JpegSyncRecord), handoff_bytes = workgroups*sizeof(uint2), round_bytes = (2*workgroups*4 + 63) & ~(size_t)63;
+    if (hipMalloc(block, record_bytes + handoff_bytes + round_bytes + 64) != hipSuccess) { (void)hipGetLastError(); *block = nullptr; return SFX_E_HIP; }
+    if (hipMemset(*block, 0, record_bytes + handoff_bytes + round_bytes + 64) != hipSuccess) { (void)hipGetLastError(); hipFree(*block); *block = nullptr; return SFX_E_HIP; }
+    char* base = (char*)*block;
+    out->records = (JpegSyncRecord*)base; out->handoff = (uint2*)(base + record_bytes); out->rounds = (uint32_t*)(base + record_bytes + handoff_bytes);
+    out->control = (uint32_t*)(base + record_bytes + handoff_bytes + round_bytes); out->capacity = (uint32_t)records;
+    return SFX_OK;
+}
+
+// A subsequence's bytes for a new handle: the production value, or SHADERFLOW_JPEG_SYNC_BYTES (2 … 2^20; for measurements)
+static uint32_t jpeg_sync_bytes() {
+    const char* text = getenv("SHADERFLOW_JPEG_SYNC_BYTES");
+    const long asked = text ? strtol(text, nullptr, 10) : 0;
+    return asked >= 2 && asked <= (1 << 20) ? (uint32_t)asked : (uint32_t)JPEG_SYNC_SUBSEQUENCE;
+}
+
+// Which entropy path a frame takes: SHADERFLOW_JPEG_SYNC=0 / 1 force the lane-per-interval kernel / the subsequence path; else the
+// subsequence path when the frame's mean restart interval holds JPEG_SYNC_RULE subsequences. (Read per frame: tests switch it.)
+static bool jpeg_sync_chosen(uint32_t scan_bytes, uint32_t intervals, uint32_t subsequence) {
+    const char* forced = getenv("SHADERFLOW_JPEG_SYNC");
+    if (forced && forced[0] == '0' && !forced[1]) return false;
+    if (forced && forced[0] == '1' && !forced[1]) return true;
+    return intervals > 0 && scan_bytes/intervals >= (unsigned long long)JPEG_SYNC_RULE*subsequence;
+}
+
 // The handle of either entry below: `slots` pinned frames of `frame_bytes` bytes, their device staging, an event each and the copy
 // stream. `jpeg` (SFX_VIDEO_MJPEG): the staging is one block and the decoder's scratch comes with it. Else every staging frame is an
 // allocation of its own with 16 bytes behind it: k_video_frame's 16-byte loads may reach past a frame's last row (video_kernels.hpp).
@@ -97,15 +139,16 @@ static int video_create(Context* c, const sfx_handle* boxes, int temporal, int w
     Video* v = new Video();
     v->magic = MAGIC_VIDEO; v->ctx = c; v->temporal = temporal; v->width = width; v->height = height; v->format = format; v->slots = slots;
     v->frame_bytes = frame_bytes;
-    if (jpeg) v->jpeg = *jpeg;
+    if (jpeg) { v->jpeg = *jpeg; v->sync_bytes = jpeg_sync_bytes(); }
     v->boxes.assign(boxes, boxes + temporal);
     for (int d = 0; d < temporal; d++)
         if (!video_texture(v->boxes[d], v)) { delete v; return fail(SFX_E_INVALID, "video: box %d is not a %d x %d RGB8 texture of this context (layers must be 1)", d, width, height); }
-    v->host.assign(slots, nullptr); v->staging.assign(slots, nullptr); v->events.assign(slots, nullptr); v->state.assign(slots, SLOT_NEW); v->intervals.assign(slots, 0);
+    v->host.assign(slots, nullptr); v->staging.assign(slots, nullptr); v->events.assign(slots, nullptr); v->state.assign(slots, SLOT_NEW); v->intervals.assign(slots, 0); v->scan_bytes.assign(slots, 0);
     bool ok = hipStreamCreateWithFlags(&v->copy, hipStreamNonBlocking) == hipSuccess;
     if (ok && jpeg)
         ok = hipMalloc(&v->staging_block, frame_bytes*slots) == hipSuccess && hipHostMalloc((void**)&v->first_bad, 64, hipHostMallocDefault) == hipSuccess
-             && jpeg_scratch(*jpeg, slots, &v->scratch, &v->basis, &v->status, &v->coefficients, &v->planes) == SFX_OK;
+             && jpeg_scratch(*jpeg, slots, &v->scratch, &v->basis, &v->status, &v->coefficients, &v->planes) == SFX_OK
+             && jpeg_sync_scratch(*jpeg, frame_bytes, v->sync_bytes, &v->sync_block, &v->sync) == SFX_OK;
     for (int k = 0; ok && k < slots; k++) {
         if (jpeg) v->staging[k] = (char*)v->staging_block + (size_t)k*frame_bytes;
         else ok = hipMalloc(&v->staging[k], frame_bytes + 16) == hipSuccess;
@@ -152,7 +195,7 @@ extern "C" int sfx_video_slot(sfx_handle h, int slot, void** host, size_t* nbyte
 }
 
 // why a staged Motion-JPEG frame of `nbytes` bytes is not one the kernels may be given (null: it is, and `intervals` is its interval count)
-static const char* jpeg_frame_fault(const void* frame, size_t nbytes, const JpegDecodeGeometry& g, uint32_t* intervals) {
+static const char* jpeg_frame_fault(const void* frame, size_t nbytes, const JpegDecodeGeometry& g, uint32_t* intervals, uint32_t* scan_bytes) {
     if (nbytes < sizeof(sfx_jpeg_frame) || nbytes > (size_t)g.capacity) return "its length is outside the fixed part … the slot's capacity";
     sfx_jpeg_frame f;
     memcpy(&f, frame, sizeof f);                                     // (sfx_jpeg_decode's caller owes no alignment)
@@ -168,6 +211,7 @@ static const char* jpeg_frame_fault(const void* frame, size_t nbytes, const Jpeg
         if (count > 256) return "a Huffman table with more than 256 codes";
     }
     *intervals = f.intervals;
+    *scan_bytes = f.scan_bytes;
     return nullptr;
 }
 
@@ -176,7 +220,7 @@ static int video_submit(Video* v, int slot, size_t nbytes, bool staged = false) 
     std::lock_guard<std::mutex> lock(v->guard);
     if (v->state[slot] == SLOT_SUBMITTED) return fail(SFX_E_INVALID, "video: slot %d holds a submitted frame that was not consumed yet", slot);
     if (staged) {
-        if (const char* fault = jpeg_frame_fault(v->host[slot], nbytes, v->jpeg, &v->intervals[slot])) return fail(SFX_E_INVALID, "video: the staged Motion-JPEG frame of %zu bytes in slot %d: %s", nbytes, slot, fault);
+        if (const char* fault = jpeg_frame_fault(v->host[slot], nbytes, v->jpeg, &v->intervals[slot], &v->scan_bytes[slot])) return fail(SFX_E_INVALID, "video: the staged Motion-JPEG frame of %zu bytes in slot %d: %s", nbytes, slot, fault);
         nbytes = (nbytes + 15) & ~(size_t)15;
     }
     USE_DEVICE(v->ctx);
@@ -204,13 +248,29 @@ extern "C" int sfx_video_submit_bytes(sfx_handle h, int slot, size_t nbytes) {
     return video_submit(v, slot, nbytes, true);
 }
 
-// The three decode launches of one staged frame (jpeg_decode_kernels.hpp) on `stream`: `frame` with `intervals` restart intervals (a lane
-// each) → `rgb`. `status` is the frame's status word, cleared in front of them. The launches run in stream order, so one frame's
-// coefficients and planes serve every frame.
-static void jpeg_launch_decode(hipStream_t stream, const uint8_t* frame, uint32_t intervals, int16_t* coefficients, uint8_t* planes, const float* basis, uint32_t* status,
+// The decode launches of one staged frame (jpeg_decode_kernels.hpp) on `stream`: `frame` with `intervals` restart intervals and `scan_bytes`
+// bytes of scan → `rgb`. `status` is the frame's status word, cleared in front of them. Entropy decoding: a lane per interval, or, with
+// `sync` (its records hold the frame's lanes: the caller has seen to that), a lane per subsequence of `subsequence` bytes with `budget`
+// rounds per phase — two launches of rounds when the frame has more than one workgroup of lanes, the scan, the write pass, and the
+// lane-per-interval kernel behind them, which returns at once unless the rounds did not settle. The launch sizes follow from the words
+// sfx_video_submit_bytes validated. A budget of JPEG_SYNC_LANES - 1 rounds at the most: then a chain that settles in `budget` rounds of
+// the whole frame settles in the two phases (phase 0 gives every lane the chain behind it in its workgroup, `budget` lanes long at the
+// most; phase 1 joins the workgroups' chains). The launches run in stream order, so one frame's scratch serves every frame.
+static void jpeg_launch_decode(hipStream_t stream, const uint8_t* frame, uint32_t intervals, uint32_t scan_bytes, const JpegSyncScratch* sync, uint32_t subsequence, int budget,
+                               int16_t* coefficients, uint8_t* planes, const float* basis, uint32_t* status,
                                uint32_t* first_bad, uint32_t serial, uint8_t* rgb, const JpegDecodeGeometry& g, int bottom_up) {
     hipMemsetAsync(status, 0, sizeof(uint32_t), stream);
-    hipLaunchKernelGGL(k_jpeg_decode_entropy, dim3((intervals + 63)/64), dim3(64), 0, stream, frame, coefficients, status, g);
+    if (sync) {
+        budget = std::max(0, std::min(budget, JPEG_SYNC_LANES - 1));
+        const unsigned long long lanes = jpeg_sync_lanes(scan_bytes, intervals, subsequence);
+        const unsigned workgroups = (unsigned)((lanes + JPEG_SYNC_LANES - 1)/JPEG_SYNC_LANES);
+        const int phases = workgroups > 1 && budget > 0 ? 2 : 1;
+        for (int phase = 0; phase < phases; phase++)
+            hipLaunchKernelGGL(k_jpeg_sync_rounds, dim3(workgroups), dim3(JPEG_SYNC_LANES), 0, stream, frame, *sync, g, subsequence, budget, phase);
+        hipLaunchKernelGGL(k_jpeg_sync_scan, dim3(1), dim3(JPEG_SYNC_LANES), 0, stream, frame, *sync, g, subsequence, (uint32_t)workgroups, phases);
+        hipLaunchKernelGGL(k_jpeg_sync_write, dim3(workgroups), dim3(JPEG_SYNC_LANES), 0, stream, frame, coefficients, status, *sync, g, subsequence);
+    }
+    hipLaunchKernelGGL(k_jpeg_decode_entropy, dim3((intervals + 63)/64), dim3(64), 0, stream, frame, coefficients, status, g, sync ? (const uint32_t*)sync->control : (const uint32_t*)nullptr);
     const size_t blocks = (size_t)g.mcus_x*g.mcus_y*g.blocks;
     hipLaunchKernelGGL(k_jpeg_decode_planes, dim3((unsigned)((blocks + 3)/4)), dim3(256), 0, stream, (const sfx_jpeg_frame*)frame, (const int16_t*)coefficients, planes, basis, (const uint32_t*)status,
                        (volatile uint32_t*)first_bad, serial, g);
@@ -236,8 +296,11 @@ int video_launch_frame(sfx_handle h, Context* c, int slot) {
     const long lanes = video_frame_lanes(v->format, v->width, v->height);
     const dim3 grid((unsigned)((lanes + VIDEO_THREADS - 1)/VIDEO_THREADS)), block(VIDEO_THREADS);
     if (v->format == SFX_VIDEO_MJPEG) {
-        jpeg_launch_decode(v->ctx->stream, (const uint8_t*)v->staging[slot], v->intervals[slot], v->coefficients, v->planes, v->basis, v->status + slot,
-                           v->first_bad, v->serial++, (uint8_t*)front->data, v->jpeg, 1);
+        // (the records hold capacity/sync_bytes lanes and an interval's each: every frame sfx_video_submit_bytes let through fits)
+        const bool sync = jpeg_sync_chosen(v->scan_bytes[slot], v->intervals[slot], v->sync_bytes) && jpeg_sync_lanes(v->scan_bytes[slot], v->intervals[slot], v->sync_bytes) <= v->sync.capacity;
+        (sync ? v->sync_frames : v->serial_frames)++;
+        jpeg_launch_decode(v->ctx->stream, (const uint8_t*)v->staging[slot], v->intervals[slot], v->scan_bytes[slot], sync ? &v->sync : nullptr, v->sync_bytes, JPEG_SYNC_ROUNDS,
+                           v->coefficients, v->planes, v->basis, v->status + slot, v->first_bad, v->serial++, (uint8_t*)front->data, v->jpeg, 1);
     } else if (v->format == SFX_VIDEO_I420) hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_I420>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     else hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_RGB24>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     const int rc = launch_status();
@@ -286,40 +349,72 @@ extern "C" int sfx_video_status(sfx_handle h, int wait, int64_t* frame, uint32_t
     return SFX_OK;
 }
 
-extern "C" int sfx_jpeg_decode(sfx_handle hc, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling,
-                               int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status) {
+extern "C" int sfx_video_jpeg_paths(sfx_handle h, uint64_t* subsequence_frames, uint64_t* interval_frames) {
+    Video* v = get<Video>(h, MAGIC_VIDEO);
+    if (!v || !subsequence_frames || !interval_frames) return fail(SFX_E_INVALID, "invalid video handle or null pointer");
+    std::lock_guard<std::mutex> lock(v->guard);
+    *subsequence_frames = v->sync_frames; *interval_frames = v->serial_frames;
+    return SFX_OK;
+}
+
+// sfx_jpeg_decode and sfx_jpeg_decode_sync. `subsequence_bytes` < 0: the lane-per-interval kernel; 0: the path a video handle would choose,
+// with the production values; else the subsequence path with pieces of that size. `info`: {subsequences, rounds used, fell back} or null.
+static int jpeg_decode_once(sfx_handle hc, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling, int subsequence_bytes,
+                            int round_budget, int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status, uint32_t* info) {
     CTX_OR_FAIL(c, hc);
     if (!staged || !status) return fail(SFX_E_INVALID, "jpeg decode: null frame or status");
+    if (subsequence_bytes == 1 || subsequence_bytes > (1 << 20)) return fail(SFX_E_INVALID, "jpeg decode: subsequences of %d bytes (2 … 2^20)", subsequence_bytes);
     JpegDecodeGeometry g;
     if (const int rc = jpeg_decode_geometry(width, height, components, h_sampling, v_sampling, std::max(nbytes, (size_t)JPEG_FRAME_FIXED + 16), &g)) return rc;
-    uint32_t intervals = 0;
-    if (const char* fault = jpeg_frame_fault(staged, nbytes, g, &intervals)) return fail(SFX_E_INVALID, "jpeg decode: the staged frame of %zu bytes: %s", nbytes, fault);
+    uint32_t intervals = 0, scan_bytes = 0;
+    if (const char* fault = jpeg_frame_fault(staged, nbytes, g, &intervals, &scan_bytes)) return fail(SFX_E_INVALID, "jpeg decode: the staged frame of %zu bytes: %s", nbytes, fault);
+    const uint32_t subsequence = subsequence_bytes > 0 ? (uint32_t)subsequence_bytes : jpeg_sync_bytes();
+    const bool sync = subsequence_bytes > 0 || (subsequence_bytes == 0 && jpeg_sync_chosen(scan_bytes, intervals, subsequence));
+    if (info) info[0] = info[1] = info[2] = 0u;
     USE_DEVICE(c);
-    void *scratch = nullptr, *frame = nullptr, *pixels = nullptr;
+    void *scratch = nullptr, *frame = nullptr, *pixels = nullptr, *records = nullptr;
     float* basis; uint32_t* device_status; int16_t* device_coefficients; uint8_t* device_planes;
+    JpegSyncScratch sync_scratch{};
     const size_t rgb_bytes = (size_t)width*height*3;
     int rc = jpeg_scratch(g, 1, &scratch, &basis, &device_status, &device_coefficients, &device_planes);
+    if (rc == SFX_OK && sync) rc = jpeg_sync_scratch(g, (size_t)g.capacity, subsequence, &records, &sync_scratch);
     if (rc == SFX_OK && (hipMalloc(&frame, (size_t)g.capacity) != hipSuccess || hipMalloc(&pixels, rgb_bytes) != hipSuccess)) rc = SFX_E_HIP;
     if (rc == SFX_OK) {
         bool ok = hipMemsetAsync(frame, 0, (size_t)g.capacity, c->stream) == hipSuccess && hipMemsetAsync(pixels, 0, rgb_bytes, c->stream) == hipSuccess
                   && hipMemsetAsync(device_coefficients, 0, (size_t)(device_planes - (uint8_t*)device_coefficients) + jpeg_plane_bytes(g), c->stream) == hipSuccess
                   && hipMemcpyAsync(frame, staged, nbytes, hipMemcpyHostToDevice, c->stream) == hipSuccess;
         if (ok) {
-            jpeg_launch_decode(c->stream, (const uint8_t*)frame, intervals, device_coefficients, device_planes, basis, device_status, nullptr, 0, (uint8_t*)pixels, g, 0);
+            jpeg_launch_decode(c->stream, (const uint8_t*)frame, intervals, scan_bytes, sync ? &sync_scratch : nullptr, subsequence, round_budget < 0 ? (int)JPEG_SYNC_ROUNDS : round_budget,
+                               device_coefficients, device_planes, basis, device_status, nullptr, 0, (uint8_t*)pixels, g, 0);
             ok = hipGetLastError() == hipSuccess;
         }
         if (ok && coefficients) ok = hipMemcpyAsync(coefficients, device_coefficients, jpeg_decode_coefficients(g)*2, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
         if (ok && planes) ok = hipMemcpyAsync(planes, device_planes, jpeg_plane_bytes(g), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
         if (ok && rgb) ok = hipMemcpyAsync(rgb, pixels, rgb_bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
         if (ok) ok = hipMemcpyAsync(status, device_status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        uint32_t control[3] = {0u, 0u, 0u};
+        if (ok && sync) ok = hipMemcpyAsync(control, sync_scratch.control, sizeof control, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
         const hipError_t synced = hipStreamSynchronize(c->stream);
         if (!ok || synced != hipSuccess) rc = fail(SFX_E_HIP, "jpeg decode: %s", hipGetErrorString(synced != hipSuccess ? synced : hipGetLastError()));
+        else if (info && sync) { info[0] = control[2]; info[1] = control[1]; info[2] = control[0]; }
     } else {
         (void)hipGetLastError();
-        fail(SFX_E_HIP, "jpeg decode: the scratch of a %d x %d frame could not be allocated", width, height);
+        fail(rc, "jpeg decode: the scratch of a %d x %d frame could not be allocated", width, height);
     }
     if (scratch) hipFree(scratch);
+    if (records) hipFree(records);
     if (frame) hipFree(frame);
     if (pixels) hipFree(pixels);
     return rc;
+}
+
+extern "C" int sfx_jpeg_decode(sfx_handle hc, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling,
+                               int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status) {
+    return jpeg_decode_once(hc, staged, nbytes, width, height, components, h_sampling, v_sampling, -1, 0, coefficients, planes, rgb, status, nullptr);
+}
+
+extern "C" int sfx_jpeg_decode_sync(sfx_handle hc, const void* staged, size_t nbytes, int width, int height, int components, int h_sampling, int v_sampling,
+                                    int subsequence_bytes, int round_budget, int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status, uint32_t* info) {
+    if (subsequence_bytes < 0) return fail(SFX_E_INVALID, "jpeg decode: subsequences of %d bytes (0: the production rule; 2 … 2^20)", subsequence_bytes);
+    return jpeg_decode_once(hc, staged, nbytes, width, height, components, h_sampling, v_sampling, subsequence_bytes, round_budget, coefficients, planes, rgb, status, info);
 }

@@ -16,8 +16,10 @@ decode, `sfx_jpeg_frame` of include/shaderflow_hip.h the layout of a staged fram
   * `AviReader(path)`, `RawReader(path, fps)`: iterators of `bytes`, one JPEG stream per frame, with `width`, `height`, `fps`,
     `sampling` and `largest` (the largest frame's bytes: the slots' capacity).
 
-Entropy decoding runs on the device alone. A stream without restart markers is ONE restart interval per frame: one lane decodes it,
-correctly and serially (frames still overlap each other and the draws). Decoding such files on the host is out of scope.
+Entropy decoding runs on the device alone. A frame whose restart intervals are short takes a lane per interval; a frame with long
+intervals — a stream without restart markers is ONE interval per frame — is cut into subsequences of `SYNC_SUBSEQUENCE` bytes, a lane
+each, which synchronise themselves (csrc/jpeg_decode_kernels.hpp, 1b; SHADERFLOW_JPEG_SYNC=0 / 1 forces either path). Decoding such
+files on the host is out of scope.
 """
 from __future__ import annotations
 
@@ -38,6 +40,9 @@ STAGED = np.dtype([("magic", "<u4"), ("scan_bytes", "<u4"), ("restart", "<u4"), 
 assert STAGED.itemsize == 1536
 FRAME_FIXED = STAGED.itemsize
 BAD_CODE, BAD_RUN, BAD_RESTART, OUT_OF_BITS, BAD_DESCRIPTOR = 1, 2, 4, 8, 16
+# csrc/capi_video.hip: the subsequence path's production values — a subsequence's bytes, rounds per phase, and how many subsequences a
+# frame's mean restart interval (scan bytes / intervals) must hold for the frame to take the path
+SYNC_SUBSEQUENCE, SYNC_ROUNDS, SYNC_RULE = 64, 255, 4
 STATUS_BITS = {BAD_CODE: "a code that matches no Huffman code", BAD_RUN: "a zero run past the block's 63rd term", BAD_RESTART: "a missing or wrong RSTn marker",
                OUT_OF_BITS: "the entropy-coded data ran out of bits", BAD_DESCRIPTOR: "a staged frame the kernels refuse"}
 
@@ -412,10 +417,14 @@ class AviReader(MjpegClip):
         self.describe()
 
 
-def device_decode(stream, context=None) -> dict:
-    """One JPEG stream through the three decode kernels, outside any video (sfx_jpeg_decode, the test entry): {"status", "coefficients"
-    (mcus, blocks per MCU, 64) int16 in zigzag order, "planes" the components' padded 8-bit planes as one vector, "rgb" (height,
-    width, 3) top row first, "header"}"""
+def device_decode(stream, context=None, sync=None, subsequence_bytes=None, round_budget=None) -> dict:
+    """One JPEG stream through the decode kernels, outside any video (the test entries): {"status", "coefficients" (mcus, blocks per
+    MCU, 64) int16 in zigzag order, "planes" the components' padded 8-bit planes as one vector, "rgb" (height, width, 3) top row
+    first, "header", "sync"}. Entropy decoding: the lane-per-interval kernel (sfx_jpeg_decode; "sync" is None) unless one of the
+    keywords asks for sfx_jpeg_decode_sync — `sync=True`: the subsequence path, with subsequences of `subsequence_bytes` bytes and
+    `round_budget` rounds per phase (None: the production values); `sync="auto"`: whichever path a video handle would choose for this
+    frame (SHADERFLOW_JPEG_SYNC is honoured); `sync=False`: the lane-per-interval kernel. "sync" is then the info record
+    {"subsequences" (0: the lane-per-interval kernel ran alone), "rounds_used", "fell_back"}."""
     import ctypes as C
 
     from shaderflow_amd import _native as N
@@ -429,6 +438,24 @@ def device_decode(stream, context=None) -> dict:
     planes = np.zeros(header.mcus*64*blocks, np.uint8)
     rgb = np.zeros((header.height, header.width, 3), np.uint8)
     status = C.c_uint32(0)
-    N.check(N.lib().sfx_jpeg_decode(context.handle, view.ctypes.data, total, header.width, header.height, header.components, h, v,
-                                    coefficients.ctypes.data, planes.ctypes.data, rgb.ctypes.data, C.byref(status)))
-    return {"status": status.value, "coefficients": coefficients, "planes": planes, "rgb": rgb, "header": header}
+    if sync is None and (subsequence_bytes is not None or round_budget is not None):
+        sync = True
+    if sync not in (None, False, True, "auto"):
+        raise ValueError(f"sync={sync!r}: None, False, True or \"auto\"")
+    info = None
+    if not sync:
+        N.check(N.lib().sfx_jpeg_decode(context.handle, view.ctypes.data, total, header.width, header.height, header.components, h, v,
+                                        coefficients.ctypes.data, planes.ctypes.data, rgb.ctypes.data, C.byref(status)))
+        if sync is False:
+            info = {"subsequences": 0, "rounds_used": 0, "fell_back": 0}
+    else:
+        words = (C.c_uint32*3)()
+        size = 0 if sync == "auto" else int(subsequence_bytes if subsequence_bytes is not None else SYNC_SUBSEQUENCE)
+        N.check(N.lib().sfx_jpeg_decode_sync(context.handle, view.ctypes.data, total, header.width, header.height, header.components, h, v, size,
+                                             -1 if round_budget is None else int(round_budget), coefficients.ctypes.data, planes.ctypes.data, rgb.ctypes.data,
+                                             C.byref(status), words))
+        info = {"subsequences": int(words[0]), "rounds_used": int(words[1]), "fell_back": int(words[2])}
+    return {"status": status.value, "coefficients": coefficients, "planes": planes, "rgb": rgb, "header": header, "sync": info}
+
+
+decode_on_device = device_decode

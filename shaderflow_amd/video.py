@@ -21,7 +21,7 @@ Where frames come from: the reference pipes the file through an `ffmpeg` subproc
     and are decoded on the device into the texture (csrc/jpeg_decode_kernels.hpp: baseline, 8 bit, one interleaved scan, 4:2:0 /
     4:2:2 / 4:4:4 / grey; anything else raises ValueError naming the marker or field). With `format="mjpeg"`, `frames=` yields such
     streams as `bytes`. A frame whose entropy-coded data is damaged raises RuntimeError naming the source frame; it is not drawn. A
-    stream without restart markers decodes correctly but serially (one lane per frame): entropy decoding on the host is out of scope;
+    stream without restart markers is cut into subsequences that decode in parallel (DESIGN.md §7c): entropy decoding on the host is out of scope;
   * any other `path` (an `.avi` with another codec included) is decoded by an `ffmpeg` binary on PATH when there is one (rawvideo rgb24 over a pipe),
     otherwise construction raises — there is no silent fallback.
 A source shorter than the scene keeps its last frame on screen (the reference's generator would raise
@@ -222,6 +222,12 @@ class VideoStage:
         frame, status = C.c_int64(-1), C.c_uint32(0)
         N.check(N.lib().sfx_video_status(self.handle, 1 if wait else 0, C.byref(frame), C.byref(status)))
         return None if frame.value < 0 else (frame.value, status.value)
+
+    def jpeg_paths(self) -> tuple[int, int]:
+        """Landed Motion-JPEG frames by entropy path: (a lane per subsequence, a lane per restart interval)"""
+        sync, serial = C.c_uint64(0), C.c_uint64(0)
+        N.check(N.lib().sfx_video_jpeg_paths(self.handle, C.byref(sync), C.byref(serial)))
+        return sync.value, serial.value
 
     def step(self, slot: int) -> None:
         N.check(N.lib().sfx_video_step(self.handle, slot))

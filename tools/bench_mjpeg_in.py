@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """One synthetic clip as rgb24 `.npy`, as `.y4m` and as Motion-JPEG `.avi` — with a restart interval per MCU row (what this package's
-device encoder writes) and, when Pillow is there to write it, without restart markers (one interval per frame: the serial case) —
-through the video sequence (videosequence.py) at 1920x1080 and 3840x2160, render-only, all in one process: every configuration runs
-once untimed and twice timed, the faster run is reported, with the bytes a staged frame takes. Then, in a run of its own under
-`rocprofv3 --kernel-trace --stats` (a fresh child process), the `.avi` with restart intervals again for the decode kernels' times.
-GPU box only.
+device encoder writes) and, when Pillow is there to write it, without restart markers (one interval per frame) — through the video
+sequence (videosequence.py) at 1920x1080 and 3840x2160, render-only, all in one process: every configuration runs once untimed and
+three times timed, the fastest run is reported with the spread, and the bytes a staged frame takes. Each `.avi` runs under both entropy
+paths (csrc/jpeg_decode_kernels.hpp): a lane per restart interval (SHADERFLOW_JPEG_SYNC=0: the only path before the subsequence
+path existed) and a lane per subsequence (SHADERFLOW_JPEG_SYNC=1) at several subsequence sizes (SHADERFLOW_JPEG_SYNC_BYTES), the
+variants taking turns; one frame of each is decoded on both paths and compared first. Then, in runs of their own under
+`rocprofv3 --kernel-trace --stats` (fresh child processes), both `.avi` again for the decode kernels' times. GPU box only.
 
     python tools/bench_mjpeg_in.py [--frames 60] [--out profiles/mjpeg_in_bench.txt] [--sizes 1920x1080 3840x2160] [--no-profile]
 """
@@ -101,10 +103,18 @@ def write_clips(folder: Path, width: int, height: int, frames: int) -> dict:
     return clips
 
 
-def run(source: dict, width: int, height: int, frames: int):
+SYNC_SIZES = (64, 128, 256)
+VARIANTS = {"a lane per interval": {"SHADERFLOW_JPEG_SYNC": "0"},
+            **{f"subsequences of {size} bytes": {"SHADERFLOW_JPEG_SYNC": "1", "SHADERFLOW_JPEG_SYNC_BYTES": str(size)} for size in SYNC_SIZES}}
+
+
+def run(source: dict, width: int, height: int, frames: int, switches: dict = {}):
     from shaderflow_amd.scene import ShaderScene
     from shaderflow_amd.video import ShaderVideo
     os.environ["SHADERFLOW_VIDEO_SEQUENCE"] = "1"
+    for name in ("SHADERFLOW_JPEG_SYNC", "SHADERFLOW_JPEG_SYNC_BYTES"):
+        os.environ.pop(name, None)
+    os.environ.update(switches)
 
     class Video(ShaderScene):
         def build(self):
@@ -120,10 +130,23 @@ def run(source: dict, width: int, height: int, frames: int):
     return took, staged
 
 
-def profile_child(width: int, height: int, frames: int) -> None:
+def same_on_both_paths(path: Path) -> str:
+    """The clip's first frame through both entropy paths: its coefficients must not differ"""
+    from shaderflow_amd.mjpegsource import AviReader, device_decode
+    frame = next(iter(AviReader(path)))
+    old = device_decode(frame)
+    for size in SYNC_SIZES:
+        new = device_decode(frame, sync=True, subsequence_bytes=size)
+        if new["status"] or old["status"] or not np.array_equal(new["coefficients"], old["coefficients"]) or not np.array_equal(new["rgb"], old["rgb"]):
+            raise RuntimeError(f"{path.name}: the subsequence path at {size} bytes differs from the lane-per-interval kernel (status {new['status']}, {old['status']})")
+    return f"{new['sync']['subsequences']} subsequences of {SYNC_SIZES[-1]} bytes, {new['sync']['rounds_used']} rounds, fell back: {new['sync']['fell_back']}"
+
+
+def profile_child(width: int, height: int, frames: int, clip: str) -> None:
     with tempfile.TemporaryDirectory(prefix="mjpeg_in_") as folder:
         clips = write_clips(Path(folder), width, height, frames)
-        run(clips["avi, an interval per MCU row"], width, height, frames)
+        if clip in clips:
+            run(clips[clip], width, height, frames, {"SHADERFLOW_JPEG_SYNC": "1"} if "no restart" in clip else {})
 
 
 def main() -> None:
@@ -133,10 +156,11 @@ def main() -> None:
     p.add_argument("--sizes", nargs="*", default=["1920x1080", "3840x2160"])
     p.add_argument("--no-profile", action="store_true")
     p.add_argument("--profile-child", default=None, help=argparse.SUPPRESS)
+    p.add_argument("--profile-clip", default="avi, an interval per MCU row", help=argparse.SUPPRESS)
     args = p.parse_args()
     if args.profile_child:
         width, height = map(int, args.profile_child.split("x"))
-        return profile_child(width, height, args.frames)
+        return profile_child(width, height, args.frames, args.profile_clip)
     from shaderflow_amd import _native
     lines = []
 
@@ -149,23 +173,36 @@ def main() -> None:
         with tempfile.TemporaryDirectory(prefix="mjpeg_in_") as folder:
             clips = write_clips(Path(folder), width, height, args.frames)
             for name, source in clips.items():
-                run(source, width, height, min(30, args.frames))
-                took, staged = min(run(source, width, height, args.frames) for _ in range(2))
-                say(f"{size:9s} {name:30s}: {args.frames} frames in {took*1e3:8.1f} ms = {args.frames/took:7.1f} frames/s, a slot holds {staged/1e6:6.2f} MB")
+                variants = VARIANTS if name.startswith("avi") else {"": {}}
+                if name.startswith("avi"):
+                    say(f"{size:9s} {name:30s}: both paths give the same coefficients and pixels ({same_on_both_paths(source['path'])})")
+                times = {variant: [] for variant in variants}
+                for variant, switches in variants.items():
+                    run(source, width, height, min(30, args.frames), switches)
+                for _ in range(3):                                    # the variants take turns
+                    for variant, switches in variants.items():
+                        took, staged = run(source, width, height, args.frames, switches)
+                        times[variant].append(took)
+                for variant, runs in times.items():
+                    label = f"{name}, {variant}" if variant else name
+                    say(f"{size:9s} {label:58s}: {args.frames} frames in {min(runs)*1e3:8.1f} ms (of {', '.join(f'{t*1e3:.1f}' for t in runs)}) = {args.frames/min(runs):7.1f} frames/s, "
+                        f"a slot holds {staged/1e6:6.2f} MB")
         if args.no_profile or not shutil.which("rocprofv3"):
             continue
-        with tempfile.TemporaryDirectory(prefix="mjpeg_in_prof_") as folder:
-            done = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", folder, "-o", "run", "--output-format", "csv", "--",
-                                   sys.executable, str(Path(__file__).resolve()), "--profile-child", size, "--frames", str(args.frames)],
-                                  cwd=ROOT, capture_output=True, text=True, timeout=600)
-            if done.returncode != 0:
-                say(f"{size:9s} rocprofv3 run failed ({done.returncode}): {done.stderr.strip()[-300:]}")
-                continue
-            for stats in Path(folder).rglob("*kernel_stats.csv"):
-                with open(stats, newline="") as file:
-                    for row in csv.DictReader(file):
-                        if "jpeg" in row["Name"] or "video" in row["Name"]:
-                            say(f"{size:9s} rocprofv3 {row['Name'].split('(')[0][:60]:60s} calls {row['Calls']:>5s} mean {float(row['AverageNs'])/1e3:9.1f} us")
+        for clip in ("avi, an interval per MCU row", "avi, no restart markers"):
+            with tempfile.TemporaryDirectory(prefix="mjpeg_in_prof_") as folder:
+                done = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", folder, "-o", "run", "--output-format", "csv", "--",
+                                       sys.executable, str(Path(__file__).resolve()), "--profile-child", size, "--profile-clip", clip, "--frames", str(args.frames)],
+                                      cwd=ROOT, capture_output=True, text=True, timeout=600)
+                if done.returncode != 0:
+                    say(f"{size:9s} rocprofv3 run failed ({done.returncode}): {done.stderr.strip()[-300:]}")
+                    continue
+                for stats in Path(folder).rglob("*kernel_stats.csv"):
+                    with open(stats, newline="") as file:
+                        for row in csv.DictReader(file):
+                            if "jpeg" in row["Name"] or "video" in row["Name"]:
+                                say(f"{size:9s} rocprofv3 ({clip}{', subsequence path' if 'no restart' in clip else ''}) {row['Name'].split('(')[0][:40]:40s} calls {row['Calls']:>5s} "
+                                    f"mean {float(row['AverageNs'])/1e3:9.1f} us")
     args.out.parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "a") as file:
         file.write("".join(line + "\n" for line in lines))
