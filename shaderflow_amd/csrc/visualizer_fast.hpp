@@ -789,7 +789,17 @@ struct VisualizerStrip {
         const int4 wx = t.block_x[(long)frame*t.blocks_x + bx], wy = t.block_y[(long)frame*t.blocks_y + by];
         const bool fits = wx.z && wy.z;
         const Tex& bg = a.tex[TEX_BACKGROUND];
-        const VisualizerConsts c = a.vis_consts ? a.vis_consts[a.frame0 + frame] : a.vis;
+        // (two loads behind a branch, not one load through a selected pointer: that one is a flat load into VECTOR registers — wave-uniform
+        // values that then cost the <72, 12, 2, 9> instance a spill at its 80 registers. The tape's constants were written by an earlier
+        // kernel: constant memory as far as this one goes, scalar loads)
+        VisualizerConsts c;
+        if constexpr (S != 2) c = a.vis_consts ? a.vis_consts[a.frame0 + frame] : a.vis;          // (the other instances as they were measured)
+        else if (a.vis_consts) {
+            typedef const float __attribute__((address_space(4))) * constant_floats;
+            static_assert(sizeof(VisualizerConsts) == 9*sizeof(float), "the fields one by one");
+            const constant_floats tape = (constant_floats)(uintptr_t)(a.vis_consts + (a.frame0 + frame));
+            c = VisualizerConsts{tape[0], tape[1], tape[2], tape[3], tape[4], tape[5], tape[6], tape[7], tape[8]};
+        } else c = a.vis;
         const float4* ce = t.columns + ((long)frame*a.wr + i)*VIS_ENTRY_QUADS;
 
         if (fits) visualizer_fast_stage<TILE_PITCH, THREADS, HALF ? TILE_ROWS*TILE_PITCH : 0>(bg, sh.cells, wx.x, wy.x, wx.y, wy.y, tid);
