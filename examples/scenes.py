@@ -373,7 +373,7 @@ class PianoAudio(_AudioScene):
     """A piano roll with its sound track (not one of the reference's): PianoRoll's keyboard and falling notes, and under the keyboard
     a spectrum strip — one bin of iSpectrogram per key, drawn in the key's column — while the keys glow with iAudioVolume. `score` as
     for PianoRoll; `audio` as for the audio scenes, and without one the score's own sound (synth.score_clip). No python logic between
-    frames: the piano and the audio tape feed one native sequence (shaderflow_amd/pianotape.py)."""
+    frames: the piano and the audio tape feed one native sequence (shaderflow_amd/sequence.py)."""
     score = None
     SPECTRUM_LOW, SPECTRUM_HIGH = 21, 108                           # A0 … C8: one spectrogram bin per key of an 88-key piano
     FRAGMENT = """
@@ -465,7 +465,7 @@ class MusicVideo(_AudioScene):
     bottom edge runs a spectrum strip, one bin of iSpectrogram per column. `clip` as for Video — (frames, fps), or a path: a `.npy`, a
     `.y4m` file, or what an ffmpeg binary decodes — and without one a drifting synthetic picture at 30 frames a second; `audio` as for
     the audio scenes, and without one a sine sweep. No python logic between frames: the staged video and the audio tape feed one
-    native sequence (shaderflow_amd/videojoin.py)."""
+    native sequence (shaderflow_amd/sequence.py)."""
     clip = None
     CLIP_SIZE, CLIP_FPS = (320, 180), 30.0
     FRAGMENT = """

@@ -9,7 +9,7 @@ behind every sampler of a temporal texture after its `roll()` (texture.py:295-29
 per frame: one `sfx_uniform_set_clock`, one `sfx_sampler_bind_many` per rolled texture matrix, the draws, the resolve, the read-out.
 Same launches in the same order with the same uniform values as the frame loop, so the same frames byte for byte
 (tests/test_gpu_multipass.py); anything it is not sure about takes the frame loop. The loops that put something in front of the frames'
-passes — an audio tape, a piano, a staged video — run the same native sequence through a `FrameSource`, `run_source` and `sequence_gate`.
+passes — an audio tape, a piano, a staged video — run the same native sequence through a `FrameSource` and `run_source` (sequence.py).
 """
 from __future__ import annotations
 
@@ -22,7 +22,6 @@ from shaderflow_amd import _native as N
 from shaderflow_amd.camera import CameraMode, ShaderCamera
 from shaderflow_amd.dynamics import ShaderDynamics
 from shaderflow_amd.module import ShaderModule
-from shaderflow_amd.parallel import is_sharded
 from shaderflow_amd.scheduler import freewheel_clock
 from shaderflow_amd.shader import ShaderProgram
 from shaderflow_amd.texture import ShaderTexture
@@ -41,7 +40,7 @@ def end_clock(policy: str, fps: float, speed: float, done: int) -> tuple[float, 
     """(time, dt, rdt) a loop leaves on the scene behind `done` >= 1 frames; the three loops differ on purpose, and tests pin them.
     "last": the last frame drawn (ClockLoop); "last_dt": the same with rdt = dt, as FrameTape.export leaves it (TapeSequence); "next": what
     scene.next leaves behind the last frame — it integrates time AFTER the frame (reference scene.py:475-479), so what a frame more
-    would have seen (PianoSequence, VideoSequence)."""
+    would have seen (a Sequence with a piano or a video). sequence.ROWS says which sequence leaves which."""
     times, dts, rdts = freewheel_clock(fps, done + 1, speed)
     if policy == "next":
         return times[done], dts[done], rdts[done]
@@ -51,10 +50,10 @@ def end_clock(policy: str, fps: float, speed: float, done: int) -> tuple[float, 
 
 class FrameSource:
     """What feeds sfx_sequence_run beside the clock: an audio tape, a piano, a staged video (tapesequence.py, pianosequence.py,
-    videosequence.py), or several of them joined (JoinedSource). `run_native` calls batches … consumed of its source, `run_source` the rest; as they stand here they do nothing,
+    videosequence.py), or several of them joined (JoinedSource; sequence.py's Sequence). `run_native` calls batches … consumed of its source, `run_source` the rest; as they stand here they do nothing,
     and that is the clock loop's own source."""
     end = "last"                                                       # the clock behind the run (end_clock)
-    chunked = True                                                     # sequence_gate saw to it that every chunk can be ONE native call; False: native_sequence is asked
+    chunked = True                                                     # the loop's gate saw to it that every chunk can be ONE native call; False: native_sequence is asked
 
     def prepare(self, times, dts, total): pass                        # in front of `prime`: the device objects, what the run needs for every frame
     def batches(self, total): return [(0, total)]                     # the frame ranges (first, size) the run is cut into; a chunk stays inside one
@@ -68,7 +67,7 @@ class FrameSource:
 
 
 class JoinedSource(FrameSource):
-    """Several frame sources in front of the same frames (pianotape.py: a piano and its sound track), in the order given. Every call
+    """Several frame sources in front of the same frames (sequence.py: a piano and its sound track), in the order given. Every call
     goes to every part in that order, `release` in reverse. At most one part may cut the run into batches (the tape), and a part whose
     `take` shortens a call must be the last: what the parts in front of it set for the call must not have depended on the longer count.
     `settle` reaches every part even when one raised; the first exception is raised again behind the last. `end` and `chunked` are the
@@ -127,34 +126,12 @@ class JoinedSource(FrameSource):
             part.release()
 
 
-def sequence_gate(scene: "ShaderScene", flag: str, export: "Optional[ExportingHelper]" = None, turbo: bool = True, kind: Optional[type] = None,
-                  taped=lambda module: (module,), chunked: bool = True):
-    """The shared opening of the sequences' `applicable`: SHADERFLOW_<flag> is not "0"; a freewheel run that is not sharded; exactly one
-    module of `kind` and of no subclass of it (which may update() differently from what the device computes); when the loop is `chunked`
-    (FrameSource.chunked) turbo, no progress relay and every program compiled; everything but the modules `taped(module)` names is what
-    ClockLoop takes: no python logic, no other module type. Returns the module (the scene without a `kind`), else None."""
-    import os
-    if os.environ.get(f"SHADERFLOW_{flag}", "1") == "0" or not scene.freewheel or is_sharded():
-        return None
-    if export is not None and export.mjpeg:                         # sfx_sequence_run's own sink knows rgb24 and yuv420p: the loop from before the sequences draws
-        return None
-    found = [scene] if kind is None else [m for m in scene.modules if isinstance(m, kind)]
-    if len(found) != 1 or type(found[0]) is not (kind or type(scene)):
-        return None
-    module = found[0]
-    if chunked and (not turbo or (export is not None and export.relay is not None)):
-        return None
-    if not ClockLoop.applicable(scene, taped=frozenset(id(m) for m in taped(module))):
-        return None
-    if chunked and not all(m.program is not None for m in scene.modules if isinstance(m, ShaderProgram)):
-        return None
-    return module
-
-
 class ClockLoop:
+    attribute = None                                                   # ShaderScene.main keeps no clock loop behind the run
+
     @staticmethod
     def applicable(scene: "ShaderScene", export: "Optional[ExportingHelper]" = None, turbo: bool = True, taped: frozenset = frozenset()) -> bool:
-        """`taped`: ids of the modules a sequence computes for the caller (tapesequence.py) — left to its own judgement"""
+        """`taped`: ids of the modules a sequence computes for the caller (sequence.py) — left to its own judgement"""
         from shaderflow_amd.scene import ShaderScene
         if type(scene).update is not ShaderModule.update:
             return False
@@ -313,7 +290,7 @@ class ClockLoop:
                 keep.clear()
 
     def run_source(self, export: "ExportingHelper", source: "FrameSource", turbo: bool = True):
-        """The export of a loop that feeds the native sequence (tapesequence.py, pianosequence.py, videosequence.py). Whatever ends the
+        """The export of a loop that feeds the native sequence (sequence.py). Whatever ends the
         run — the last frame, scene.quit, an encoder that died, a device error — the source settles the host objects at the last frame
         that was drawn, and the clock is the one its loop leaves there (`end_clock`)."""
         scene, total = self.scene, export.total_frames

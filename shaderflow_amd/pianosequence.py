@@ -1,5 +1,5 @@
 """
-PianoSequence: the frame loop of piano-roll scenes without python logic (no reference equivalent).
+PianoSequence: the piano in front of the frames of piano-roll scenes without python logic (no reference equivalent).
 
 `ShaderPiano.update()` (piano/module.py) runs on the host every frame: a handful of numpy selections over the whole score, two
 `DynamicNumber` steps, and three texture uploads — iPianoRoll alone is 128 x 256 x RGBA32F = 512 KB a frame. No fast loop knew the
@@ -16,10 +16,9 @@ targets for every frame of the export come from one vectorised pass over frames 
 the module's own `DynamicNumber.next`, before the first frame; the native call stores frame k's pair into the uniform of every
 program that declares it.
 
-A scene takes this loop when `main(batch=None)` finds it applicable (after ClockLoop, before TapeSequence) and
-`SHADERFLOW_PIANO_SEQUENCE` is not "0". Out of scope, so they keep the frame loop: python `update()` logic, a subclass of ShaderPiano,
-several pianos, sharded runs, and a key-press system whose early-out can fire (`precision != 0`) or that integrates. A piano beside
-audio modules is not this loop's either: it takes `PianoTapeSequence` (pianotape.py: this source and the tape's, joined).
+Which scenes run this way, alone or beside audio modules or a video, is `Sequence`'s to say (sequence.py). Out of scope, so they keep
+the frame loop: python `update()` logic, a subclass of ShaderPiano, several pianos, sharded runs, and a key-press system whose early-out
+can fire (`precision != 0`) or that integrates.
 """
 from __future__ import annotations
 
@@ -30,12 +29,11 @@ from typing import TYPE_CHECKING
 import numpy as np
 
 from shaderflow_amd import _native as N
-from shaderflow_amd.clockloop import ClockLoop, FrameSource, sequence_gate
+from shaderflow_amd.clockloop import FrameSource
 from shaderflow_amd.piano.module import MAX_NOTE, MAX_ROLLING, ShaderPiano
 from shaderflow_amd.tape import _coefficients_f32
 
 if TYPE_CHECKING:
-    from shaderflow_amd.exporting import ExportingHelper
     from shaderflow_amd.scene import ShaderScene
 
 # sfx_piano_tick (include/shaderflow_hip.h) as a numpy record: the table of an export is filled without a python loop
@@ -112,8 +110,8 @@ def piano_textures(piano: ShaderPiano) -> tuple:
 
 
 def piano_fits(piano: ShaderPiano) -> bool:
-    """Whether this piano is what k_piano_frame and the host-stepped note range compute (PianoSequence, and PianoTapeSequence beside an
-    audio tape): its textures as build() made them, a key-press system the kernel steps, a score inside the textures"""
+    """Whether this piano is what k_piano_frame and the host-stepped note range compute (PianoSequence, alone or beside
+    other sources): its textures as build() made them, a key-press system the kernel steps, a score inside the textures"""
     if any(texture is None for texture in (piano.keys_texture, piano.channel_texture, piano.roll_texture, piano.tempo_texture)):
         return False
     if (piano.keys_texture.size, piano.channel_texture.size, piano.roll_texture.size) != ((MAX_NOTE, 1), (MAX_NOTE, 1), (MAX_ROLLING, MAX_NOTE)):
@@ -140,20 +138,10 @@ def piano_fits(piano: ShaderPiano) -> bool:
 
 
 class PianoSequence(FrameSource):
-    end = "next"                                                       # the clock as scene.next leaves it behind the last frame
-
-    @staticmethod
-    def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
-        # no python logic, no audio modules, no module type beside the piano and its textures that ClockLoop does not take
-        piano = sequence_gate(scene, "PIANO_SEQUENCE", export, turbo, ShaderPiano, taped=piano_textures)
-        return piano is not None and piano_fits(piano)
-
     def __init__(self, scene: "ShaderScene"):
         self.scene = scene
-        self.clock = ClockLoop(scene)                                  # the pass and matrix tables, the chunk size
         self.piano = next(m for m in scene.modules if type(m) is ShaderPiano)
         self.handle = None
-        self.frames = 0                                                # frames drawn by the native sequence (tests, measurements)
         self._ticks = None
         self._aliased = None                                           # `previous is target` on the host object, as the device has stepped so far
         self.dynamic_name = f"{self.piano.name}Dynamic".encode()       # the uniform ShaderPiano.pipeline() yields the note range under
@@ -210,9 +198,6 @@ class PianoSequence(FrameSource):
 
     # the export: the native sequence with the piano's frame in front of every frame's passes ---------------------------------------------
 
-    def run(self, export: "ExportingHelper", turbo: bool):
-        return self.clock.run_source(export, self, turbo)
-
     def prepare(self, times, dts, total: int) -> None:
         """The score on the device and the per-frame table: the clock in float64, the key-press coefficients, iPianoDynamic of every frame"""
         piano, keys, note_range = self.piano, self.piano.key_press_dynamics, self.piano.note_range_dynamics
@@ -241,7 +226,6 @@ class PianoSequence(FrameSource):
         the key-press state and the textures' host copies are read from the device (which a native call that failed half-way may have
         left up to a chunk ahead)"""
         note_range, times, dts = self.piano.note_range_dynamics, self._times, self._dts
-        self.frames = done
         if done < len(times):
             for name, value in self._before.items():
                 setattr(note_range, name, value)

@@ -64,11 +64,8 @@ class ShaderScene(ShaderModule):
     """Scenes in which only the clock moves between frames take clockloop.ClockLoop (same frames, a fifth of the python per frame)"""
 
     tape_loop = None                                          # plain class attribute: the TapeLoop of the last main(), if it took one
-    tape_sequence = None                                      # … and the TapeSequence (tapesequence.py)
-    piano_sequence = None                                     # … and the PianoSequence (pianosequence.py)
-    piano_tape = None                                         # … and the PianoTapeSequence (pianotape.py)
-    video_sequence = None                                     # … and the VideoSequence (videosequence.py)
-    video_join = None                                         # … and the VideoJoinedSequence (videojoin.py)
+    # … and its Sequence, under the attribute that sequence.ROWS names for the sources the scene has
+    tape_sequence = piano_sequence = piano_tape = video_sequence = video_join = None
     _fused_this_frame: bool = False
     _skip_render: bool = False
     shard_warmup = "auto"                                     # plain class attribute: subclasses override it like `life_period`
@@ -347,11 +344,7 @@ class ShaderScene(ShaderModule):
         self.relay(ShaderMessage.Shader.Compile)
         self.scheduler.clear()
         self.tape_loop = None
-        self.tape_sequence = None
-        self.piano_sequence = None
-        self.piano_tape = None
-        self.video_sequence = None
-        self.video_join = None
+        self.tape_sequence = self.piano_sequence = self.piano_tape = self.video_sequence = self.video_join = None
 
         _width, _height = self.resize(width=width, height=height, ratio=ratio, scale=scale)
 
@@ -392,27 +385,21 @@ class ShaderScene(ShaderModule):
                                         frameskip=frameskip, precise=True)
         if self.exporting and (is_sharded() or shard is not None):
             return self._sharded_frame_loop(export, turbo, *(shard or rank_world()))
-        # The loops that spare scene.next, in the order they are asked; the one that ran is kept under its attribute (tests, tools):
-        # nothing but the clock moves between frames (clockloop.py: the lean loop, same frames); a ShaderVideo without python logic, its
-        # frames staged ahead (videosequence.py); the same beside audio modules, a piano or both, the staged video, the device tape and
-        # the piano in one native call (videojoin.py); a ShaderPiano without python logic, its score on the device (pianosequence.py); the
-        # same beside audio modules, the piano and the device tape in one native call (pianotape.py); audio-reactive layered / temporal
-        # / multi-program scenes on the device tape (tapesequence.py); audio scenes with python logic of their own, the user's update()
-        # frame by frame (tapeloop.py)
+        # The loops that spare scene.next; the one that ran is kept under its attribute (tests, tools): nothing but the clock moves
+        # between frames (clockloop.py: the lean loop, same frames); a piano, audio modules, a video or several of them without python
+        # logic, computed on the device in front of the frames of one native call (sequence.py: its ROWS name the attribute); audio
+        # scenes with python logic of their own, the user's update() frame by frame (tapeloop.py). The sequence's rows exclude one
+        # another — a row refuses the module types of a source it has not, through ClockLoop.applicable — and no scene is both the clock
+        # loop's and the sequence's: among those the order carries no behaviour. The sequence must be asked before the tape loop, which
+        # also accepts single-program scenes with audio beside a piano or a video (where they go when their join's flag is "0").
         from shaderflow_amd.clockloop import ClockLoop
-        from shaderflow_amd.pianosequence import PianoSequence
-        from shaderflow_amd.pianotape import PianoTapeSequence
+        from shaderflow_amd.sequence import Sequence
         from shaderflow_amd.tapeloop import TapeLoop
-        from shaderflow_amd.tapesequence import TapeSequence
-        from shaderflow_amd.videojoin import VideoJoinedSequence
-        from shaderflow_amd.videosequence import VideoSequence
-        loops = ((None, ClockLoop), ("video_sequence", VideoSequence), ("video_join", VideoJoinedSequence), ("piano_sequence", PianoSequence),
-                 ("piano_tape", PianoTapeSequence), ("tape_sequence", TapeSequence), ("tape_loop", TapeLoop))
-        for attribute, loop in loops[0 if self.freewheel and self.clock_loop else 1:]:
+        for loop in (ClockLoop, Sequence, TapeLoop)[0 if self.freewheel and self.clock_loop else 1:]:
             if batch is None and loop.applicable(self, export, turbo):
                 runner = loop(self)
-                if attribute:
-                    setattr(self, attribute, runner)
+                if runner.attribute:
+                    setattr(self, runner.attribute, runner)
                 return runner.run(export, turbo)
         while (task := self.scheduler.next()):
             if (task is not self.vsync):

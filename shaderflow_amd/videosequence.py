@@ -1,5 +1,5 @@
 """
-VideoSequence: the frame loop of video scenes without python logic (no reference equivalent).
+VideoSequence: the staged video in front of the frames of video scenes without python logic (no reference equivalent).
 
 `ShaderVideo.update()` (video.py) runs on the host for every source frame: the next array from a python iterator, a flipped contiguous
 host copy of it (6.2 MB at 1080p, 24.9 MB at 4K), a synchronous upload, and only then the draw. No fast loop knew the module, so a scene
@@ -21,11 +21,9 @@ Behind a run — finished, quit or failed — the host objects are where the fra
 `_exhausted`, the texture's host copies (read back from the device) and the clock; frames the reader took from the source ahead of the
 draws go back in front of it for a later `update()`.
 
-A scene takes this loop when `main(batch=None)` finds it applicable (after ClockLoop, before PianoSequence) and
-`SHADERFLOW_VIDEO_SEQUENCE` is not "0". A video beside audio modules or a piano is not this loop's: it takes `VideoJoinedSequence`
-(videojoin.py: this source joined with the tape's and the piano's). Out of scope, so they keep the frame loop: several videos,
-`layers != 1`, a subclass of ShaderVideo, sharded runs, a scene `update()` of its own, and — for the planar sources — bt709 or
-full-range input, chroma interpolation and 10-bit sources (the reader refuses what it can see of them).
+Which scenes run this way, alone or beside audio modules or a piano, is `Sequence`'s to say (sequence.py). Out of scope, so they keep
+the frame loop: several videos, `layers != 1`, a subclass of ShaderVideo, sharded runs, a scene `update()` of its own, and — for the
+planar sources — bt709 or full-range input, chroma interpolation and 10-bit sources (the reader refuses what it can see of them).
 
 Motion-JPEG sources (`video.format == "mjpeg"`: mjpegsource.py) stay compressed in the slots: the reader stages each JPEG stream
 (`mjpegsource.stage`: tables, interval starts, scan), only those bytes are copied, and a landing launches the decode kernels
@@ -42,12 +40,11 @@ from typing import TYPE_CHECKING, Optional
 
 import numpy as np
 
-from shaderflow_amd.clockloop import ClockLoop, FrameSource, sequence_gate
+from shaderflow_amd.clockloop import ClockLoop, FrameSource
 from shaderflow_amd.module import logger
 from shaderflow_amd.video import ShaderVideo, VideoStage
 
 if TYPE_CHECKING:
-    from shaderflow_amd.exporting import ExportingHelper
     from shaderflow_amd.scene import ShaderScene
 
 SLOT_BYTES = 256 << 20                                                 # pinned staging of one run, at most (and as much on the device)
@@ -77,7 +74,7 @@ def landing_frames(times, fps: float, first_read: int = 0, available: Optional[i
 
 
 def video_fits(video: ShaderVideo) -> bool:
-    """Whether this video's texture is what k_video_frame writes (VideoSequence, and VideoJoinedSequence beside a tape or a piano): one
+    """Whether this video's texture is what k_video_frame writes (VideoSequence, alone or beside other sources): one
     layer of RGB8 of the clip's own size that follows no resolution, every box on the device"""
     texture = video.texture
     if texture is None or texture.layers != 1 or texture.components != 3 or texture.dtype != np.uint8:
@@ -86,20 +83,11 @@ def video_fits(video: ShaderVideo) -> bool:
 
 
 class VideoSequence(FrameSource):
-    end = "next"                                                       # the clock as scene.next leaves it behind the last frame
-
-    @staticmethod
-    def applicable(scene: "ShaderScene", export: "ExportingHelper | None" = None, turbo: bool = True) -> bool:
-        # no python logic, no audio modules, no piano, no module type beside the video and its texture that ClockLoop does not take
-        video = sequence_gate(scene, "VIDEO_SEQUENCE", export, turbo, ShaderVideo, taped=lambda video: (video, video.texture))
-        return video is not None and video_fits(video)
-
-    def __init__(self, scene: "ShaderScene"):
+    def __init__(self, scene: "ShaderScene", clock: ClockLoop):
         self.scene = scene
-        self.clock = ClockLoop(scene)                                  # the pass and matrix tables, the chunk size
+        self.clock = clock                                             # the run's (sequence.py): the sampler names of the video's matrix
         self.video = next(m for m in scene.modules if type(m) is ShaderVideo)
         self.stage: Optional[VideoStage] = None
-        self.frames = 0                                                # frames drawn by the native sequence (tests, measurements)
         self.landed = 0                                                # source frames those frames landed
         self.lock = threading.Condition()
         self.thread: Optional[threading.Thread] = None
@@ -241,11 +229,6 @@ class VideoSequence(FrameSource):
 
     # the export ------------------------------------------------------------------------------------------------------------------------
 
-    def run(self, export: "ExportingHelper", turbo: bool):
-        result = self.clock.run_source(export, self, turbo)
-        self.raise_undecoded()
-        return result
-
     def prepare(self, times, dts, total: int) -> None:
         """The stage and the reader thread"""
         video = self.video
@@ -268,7 +251,6 @@ class VideoSequence(FrameSource):
             self.stop = True
             self.lock.notify_all()
         self.thread.join()
-        self.frames = done
         video._read = self.first_read + self.landed
         video._exhausted = self.was_exhausted or (self.exhausted_at is not None and self.exhausted_at < done)
         if video._exhausted and not self.was_exhausted:

@@ -10,7 +10,7 @@ Motion-JPEG sources on the device (csrc/jpeg_decode_kernels.hpp, csrc/capi_video
      the magnitudes of these 8-bit pictures (Σ|terms| of a block stays near its samples' range), inside the 1e-3 the issue sets;
   2. a decoded frame lands bottom-up in the texture and a temporal matrix rolls; damaged scans set the status, raise RuntimeError from
      update() and from an export, and the frame behind them decodes;
-  3. a scene with an `.avi` source: the frame loop, VideoSequence and VideoJoinedSequence (beside audio) give the same bytes; a clip
+  3. a scene with an `.avi` source: the frame loop and the video sequence, alone and joined (beside audio), give the same bytes; a clip
      shorter than the scene holds its last frame; an exported `.avi` read back shows the device decode of that file's frames.
 """
 from __future__ import annotations

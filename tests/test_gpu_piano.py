@@ -298,7 +298,7 @@ def test_a_piano_under_another_name(monkeypatch):
     monkeypatch.setenv("SHADERFLOW_PIANO_SEQUENCE", "1")
     scene = Scene()
     got = render(scene, frames)
-    assert scene.piano_sequence is not None and scene.piano_sequence.dynamic_name == b"iRollDynamic"
+    assert scene.piano_sequence is not None and scene.piano_sequence.piano.dynamic_name == b"iRollDynamic"
     assert scene.shader.translated and not scene.shader.fallback
     names = {u.name for u in scene.shader.full_pipeline()}
     assert {"iRollDynamic", "iRollRoll0x0", "iRollKeys0x0"} <= names and "iPianoDynamic" not in names

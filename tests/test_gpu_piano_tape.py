@@ -1,5 +1,5 @@
 """
-The piano-and-tape sequence (shaderflow_amd/pianotape.py): a piano roll beside audio modules, without python logic, is drawn by ONE native
+The piano-and-tape sequence (shaderflow_amd/sequence.py): a piano roll beside audio modules, without python logic, is drawn by ONE native
 sequence that names the piano and the audio tape, and every frame equals the frame loop's (`ShaderScene.next`) byte for byte.
 
 The frame loop here is the real one: `SHADERFLOW_PIANO_TAPE=0` alone would hand a single-program scene of this kind to the tape loop

@@ -330,7 +330,7 @@ def test_one_slot_filler_serves_the_frame_loop_and_the_sequence(monkeypatch):
     for kind, source in clips.items():
         loop, want, scene, got = both_ways(video_scene(source, temporal=count), count + 1, monkeypatch)      # (nothing lands on the first scene frame)
         assert scene.video._read == count and scene.video.format == (None if kind == "rgb" else kind)
-        assert scene.video_sequence.per_chunk == SLOTS_MAX//2
+        assert scene.video_sequence.video.per_chunk == SLOTS_MAX//2
         assert_same_host_state(loop, scene)                            # every box of the matrix: the five frames' texture bytes
         boxes = [scene.video.texture.get_box(depth).texture.read() for depth in range(count)]
         assert len({box.tobytes() for box in boxes}) == count, kind
@@ -481,10 +481,13 @@ def test_scenes_the_sequence_does_not_take_keep_the_frame_loop(case, monkeypatch
     want = render(Scene(), 30, batch=False)
     monkeypatch.setenv("SHADERFLOW_VIDEO_SEQUENCE", "1")
     scene = Scene()
-    from shaderflow_amd.videosequence import VideoSequence
+    from shaderflow_amd.sequence import Sequence
     got = render(scene, 30)
     assert scene.video_sequence is None
     scene.freewheel = True
-    assert not VideoSequence.applicable(scene)
+    if case == "audio-beside":
+        assert Sequence.taken(scene) != "video_sequence"                # (a video beside audio may be the join's)
+    else:
+        assert not Sequence.applicable(scene)
     assert_frames_equal(want, got)
     assert scene.video._read >= 13 and scene.video.texture.get_box().texture.read().any()      # the host module wrote its texture

@@ -1,5 +1,5 @@
 """
-The host halves of the video-joined sequence (shaderflow_amd/videojoin.py) that need no device: `clockloop.JoinedSource` with THREE parts
+The host halves of the video-joined sequence (shaderflow_amd/sequence.py) that need no device: `clockloop.JoinedSource` with THREE parts
 that record their calls — the piano, the tape that cuts the run, and last the video that shortens calls — the `video_join` field of the
 sequence descriptor, the translator's sampler slots beside the two the tape replaces, and `video_fits`.
 """
@@ -184,15 +184,20 @@ def test_video_fits_is_the_texture_half_of_the_video_sequences_answer():
 
 
 def test_the_video_sequence_asks_video_fits(monkeypatch):
-    """VideoSequence.applicable is the gate and then video_fits, for the same video: the two classes cannot drift apart"""
-    from shaderflow_amd import videojoin, videosequence
-    assert videojoin.video_fits is videosequence.video_fits
+    """Sequence.applicable for a video alone is the gate and then video_fits, for the same video: the video's answer is the same
+    function alone and in a join"""
+    from shaderflow_amd import sequence, videosequence
+    from shaderflow_amd.video import ShaderVideo
+    assert sequence.video_fits is videosequence.video_fits
     asked = []
-    video = SimpleNamespace(width=64, height=36, texture=texture())
-    monkeypatch.setattr(videosequence, "sequence_gate", lambda scene, flag, *args, **kwargs: asked.append(flag) or video)
-    assert videosequence.VideoSequence.applicable(object()) is True
+    video = object.__new__(ShaderVideo)                                 # (no device: the fields video_fits and the gate's caller read)
+    video.name, video.width, video.height, video.texture = "iVideo", 64, 36, texture()
+    scene = SimpleNamespace(modules=[video])
+    monkeypatch.setattr(sequence, "sequence_gate", lambda scene, export, turbo, taped, chunked: asked.append(list(taped)) or True)
+    assert sequence.Sequence.applicable(scene) is True and sequence.Sequence.taken(scene) == "video_sequence"
+    del asked[1:]
     video.texture.layers = 2
-    assert videosequence.VideoSequence.applicable(object()) is False
-    monkeypatch.setattr(videosequence, "sequence_gate", lambda *args, **kwargs: None)
-    assert videosequence.VideoSequence.applicable(object()) is False
-    assert asked == ["VIDEO_SEQUENCE", "VIDEO_SEQUENCE"]
+    assert sequence.Sequence.applicable(scene) is False
+    monkeypatch.setattr(sequence, "sequence_gate", lambda *args, **kwargs: False)
+    assert sequence.Sequence.applicable(scene) is False
+    assert asked == [[video, video.texture], [video, video.texture]]

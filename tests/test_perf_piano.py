@@ -12,7 +12,7 @@ pytestmark = pytest.mark.perf
 def test_piano_sequence_is_at_least_twice_the_frame_loop():
     """PianoRoll at 1920x1080, 1x SSAA, render-only: the frame loop pays ShaderPiano.update() on the host and a 512 KB upload of iPianoRoll
     every frame, the sequence one kernel launch. The factor 2 is a floor only a path that still does per-frame host work or per-frame
-    uploads would miss (tools/bench_piano_sequence.py measures the gain itself; DESIGN §2d holds the figures); both paths run in this
+    uploads would miss (tools/bench_sequences.py measures the gain itself; DESIGN §2d holds the figures); both paths run in this
     process, on this box."""
     import torch
     if not torch.cuda.is_available():
