@@ -56,6 +56,8 @@ def test_multipass_both_layers_bit_exact(gpu):
     gpu.set_uniforms(prog, u)
     assert gpu.bind(prog, "background", gpu.texture(background))
     layer0 = gpu.render(prog, w, h, layer=0)
+    kernel = gpu.lib.sfx_last_kernel().decode()
+    assert "k_render<" in kernel and "Plain" in kernel, kernel            # layer 0 is the generic kernel's
     u.iLayer = 0
     want0 = O.render("multipass", u, {"background": O.make_texture(background)}, w, h, threads=4)
     assert np.array_equal(layer0, want0), lsb_report(layer0, want0)
@@ -64,6 +66,7 @@ def test_multipass_both_layers_bit_exact(gpu):
     assert gpu.bind(prog, "iScreen0x0", first)
     assert not gpu.bind(prog, "iScreen0x1", first)                        # no restated fragment samples layer 1
     layer1 = gpu.render(prog, w, h, layer=1)
+    assert gpu.lib.sfx_last_kernel().decode() == "k_multipass_layer1", gpu.lib.sfx_last_kernel()
     u.iLayer = 1
     want1 = O.render("multipass", u, {"background": O.make_texture(background), 0: O.make_texture(want0, "linear", False, False)}, w, h, threads=8)
     assert np.array_equal(layer1, want1), lsb_report(layer1, want1)
@@ -87,6 +90,7 @@ def test_motionblur_history_bit_exact(gpu, temporal):
     for t in range(temporal):
         assert gpu.bind(prog, f"iScreen{t}x0", gpu.texture(history[t], "linear", False, False))
     got = gpu.render(prog, w, h, layer=1)
+    assert gpu.lib.sfx_last_kernel().decode() == "k_motionblur_layer1", gpu.lib.sfx_last_kernel()
     assert np.array_equal(got, want), lsb_report(got, want)
 
 
