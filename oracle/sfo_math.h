@@ -10,8 +10,23 @@
  * admissible implementation: every function below is a finite sequence of correctly-rounded
  * binary32 operations (+ - * / sqrtf fmaf floorf rintf and integer bit moves), evaluated in the
  * written order with no contraction (-ffp-contract=off). The HIP device code restates the same
- * sequences independently (shaderflow_amd/csrc/sfmath.hpp); tests compare both bit for bit, and
- * compare this file against libm in double precision (tests/test_oracle_math.py: ≤ 4 ulp).
+ * sequences independently (shaderflow_amd/csrc/sfmath.hpp); tests compare both bit for bit, value by
+ * value, on the x86 host build and on the device (tests/test_host_math.py, tests/test_gpu_math.py over
+ * the inputs of tests/math_cases.py: specials, subnormals, every binade, the ends of each reduction),
+ * and compare them against libm in double precision. What holds, as measured there:
+ *   sin, cos for |x| <= 2^20, atan, atan2, log2, log, exp2 everywhere: within 4 ulp (1.49 / 1.47 /
+ *     2.55 / 2.88 / 1.91 / 2.01 / 0.96 measured); next to a zero of sin or cos other than 0
+ *     (|value| < |x|*2^-25) 2.5e-7 absolute instead, the one rounding of the reduction's first step.
+ *   sin, cos beyond 2^20: OUTSIDE the domain of these sequences. k = rint(x*2/pi) stops being the
+ *     nearest integer (5.4 ulp in [1.5*2^20, 2^21), 3e-4 absolute at 2^24, values up to 15
+ *     in [2^25, 2^26), -2.5e16 at 1e10, infinities by 1e15). Run-time translated fragments take fmodf(x, TAU)
+ *     first there (csrc/jit_runtime.hpp, SINCOS_REACH): bounded, deterministic, not accurate. This
+ *     file and the restated kernels call the sequences as they are; the tests compare sin and cos
+ *     with this file for |x| <= 2^20 only.
+ *   exp = exp2(x*log2e) rounds the product first: within GLSL's 3 + 2|x| ulp (62.0 ulp at x = 87.3),
+ *     not within 4. pow = exp2(y*log2(x)) likewise: 109.6 ulp on (0, 8] x [-8, 8].
+ *   atan2(+-inf, +-inf) is NaN (inf/inf); a NaN operand of atan2 may be dropped by min/max
+ *     (atan2(NaN, 0) = 0). Pinned by the tests, not fixed.
  *
  * Polynomial coefficients: Cephes single-precision sinf/cosf/atanf/logf/expf (S. Moshier, public
  * domain) — published constants, restated.
@@ -73,7 +88,7 @@ static inline float sfo_sincos_reduce(float x, int32_t* quadrant) {
     float r = fmaf(-k, 0x1.921fb6p+0f, x);             /* pi/2 = HI + MID + LO */
     r = fmaf(-k, -0x1.777a5cp-25f, r);
     r = fmaf(-k, -0x1.ee59dap-50f, r);
-    /* |k| beyond int32 is outside the supported domain (|x| < 1e9); clamp keeps C defined */
+    /* the supported domain is |x| <= 2^20 (see the top of this file); |k| beyond int32: the clamp keeps C defined */
     float kc = sfo_clamp(k, -2147483520.0f, 2147483520.0f);
     *quadrant = (int32_t)kc;
     return r;

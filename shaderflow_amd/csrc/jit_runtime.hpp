@@ -245,12 +245,32 @@ SF_RT_ARITH(vec3, 3)
 SF_RT_ARITH(vec4, 4)
 
 // ---- built-in functions (GLSL 3.30 §8.1-8.3) --------------------------------------------------------------------------
-// scalar forms; every transcendental is sfmath's fixed sequence of binary32 operations
+// scalar forms; every transcendental is sfmath's fixed sequence of binary32 operations. What tests/math_cases.py measures and
+// tests/test_host_math.py / test_gpu_math.py hold, value by value, on the x86 host build, on gfx950 and (where it has the function) in
+// the parity oracle's restatement (sfo_math.h) — the same bits on all three:
+//   * sin, cos for |x| <= SINCOS_REACH = 2^20, atan, atan(y, x), log2, log, exp2 on every input: within 4 ulp of libm (measured
+//     1.49 / 1.47 / 2.55 / 2.88 / 1.91 / 2.01 / 0.96). Next to a zero of sin or cos other than x = 0, where |value| < |x|*2^-25, the
+//     one rounding of the first Cody-Waite step (half an ulp of k*(HI - pi/2) = |x|*2^-25.1) outweighs an ulp of the value: there
+//     the bound is 2.5e-7 absolute.
+//   * beyond SINCOS_REACH sfmath's reduction degrades (k = rint(x*2/pi) stops being the nearest integer: 5.4 ulp in [1.5*2^20,
+//     2^21), 3e-4 absolute at 2^24, 15 in [2^25, 2^26), -2.5e16 at 1e10, infinities by 1e15) — sf::sin is meant for the arguments the restated kernels
+//     have. The wrappers below first take the exact remainder fmodf(x, TAU): |sin|, |cos| <= 1 for every finite x, the same bits
+//     on host and device, NaN for an infinity or a NaN, and NO accuracy promise (TAU is the float nearest 2 pi: the phase is off
+//     by x*2.8e-8 radians). At or below the reach the bits are sf::sin's and sf::cos's. tan, rotate2d, polar2rect, cexp and the
+//     noise functions go through the wrappers.
+//   * exp is exp2(x*log2e), the product rounded: within GLSL's own 3 + 2|x| ulp (62.0 ulp measured at x = 87.3), not within 4.
+//     pow is exp2(y*log2(x)) and inherits the rounding of y*log2(x) the same way (109.6 ulp on (0, 8] x [-8, 8]). sinh and cosh
+//     are sums of two such exp and stay within the same 3 + 2|x| ulp (0.54 of it), sinh and tanh with ulp(1) as the smallest unit:
+//     around zero (exp(x) - exp(-x))/2 cancels (sinh(x) = 0 for |x| <= 2^-25, sinh(1e-4) is 2281 ulp off, 2e-7 absolute at most):
+//     fine for a pixel, not fixed. tan 3.02, asin 3.12, acos 3.15, inversesqrt 1.39 ulp: bounds in tests/math_cases.py.
+//   * atan(y, x) with both operands infinite is NaN (inf/inf); round() takes exact halves towards +inf.
+constexpr float SINCOS_REACH = 1048576.0f;
+SF_HD float within_reach(float x) { return (sf::abs(x) > SINCOS_REACH) ? ::fmodf(x, TAU) : x; }
 SF_HD float radians(float x) { return x*(PI/180.0f); }
 SF_HD float degrees(float x) { return x*(180.0f/PI); }
-SF_HD float sin(float x) { return sf::sin(x); }
-SF_HD float cos(float x) { return sf::cos(x); }
-SF_HD float tan(float x) { return sf::sin(x)/sf::cos(x); }
+SF_HD float sin(float x) { return sf::sin(within_reach(x)); }
+SF_HD float cos(float x) { return sf::cos(within_reach(x)); }
+SF_HD float tan(float x) { const float r = within_reach(x); return sf::sin(r)/sf::cos(r); }
 SF_HD float atan(float x) { return sf::atan(x); }
 SF_HD float atan(float y, float x) { return sf::atan(y, x); }
 SF_HD float asin(float x) { return sf::atan(x, sf::sqrt((1.0f - x)*(1.0f + x))); }
@@ -270,7 +290,7 @@ SF_HD float sign(float x) { return sf::sign(x); }
 SF_HD float floor(float x) { return ::floorf(x); }
 SF_HD float ceil(float x) { return ::ceilf(x); }
 SF_HD float trunc(float x) { return ::truncf(x); }
-SF_HD float round(float x) { return ::floorf(x + 0.5f); }
+SF_HD float round(float x) { const float f = ::floorf(x); return (x - f >= 0.5f) ? f + 1.0f : f; }      // x - f is exact or rounds to 1: no x + 0.5 to round first
 SF_HD float roundEven(float x) { return ::rintf(x); }
 SF_HD float fract(float x) { return sf::fract(x); }
 SF_HD float mod(float x, float y) { return sf::mod(x, y); }

@@ -7,13 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import binding as O
-
-
-def ulp_error(got32, want64):
-    want32 = want64.astype(np.float32)
-    ulp = np.spacing(np.abs(want32)).astype(np.float64)
-    ulp[ulp == 0] = np.finfo(np.float32).tiny
-    return np.abs(got32.astype(np.float64) - want64)/ulp
+from tests.math_cases import ulp_error
 
 
 def test_sfmath_accuracy():
