@@ -201,6 +201,14 @@ int sfx_ring_destroy(sfx_handle ring);
 int sfx_ring_create_sized(sfx_handle ctx, size_t capacity, int slots, int framing, sfx_handle* ring);
 /* payload sizes of the frames written so far, in write order (the index of an AVI file); `out` may be null to ask for the count */
 int sfx_ring_sizes(sfx_handle ring, uint32_t* out, size_t capacity, size_t* count);
+/* A side track behind the frames of a sized ring with `framing` 1 (the PCM stream of an AVI file): `ends[j]` is where, in `bytes`, the
+ * share of the ring's j-th frame ends; the first share begins at 0. After the writer has written frame j it writes "01wb", the
+ * little-endian size, bytes [ends[j-1], ends[j]) and a pad byte to an even length, in the same run of bytes as the frame; an empty
+ * share writes nothing, and a frame that is not written (its status said it did not fit) takes its share with it. The ring BORROWS
+ * both tables: they stay alive and unchanged until sfx_ring_destroy. SFX_E_INVALID: a ring that is not sized or not framed, a ring
+ * that has taken a frame already, a table that runs backwards or past `nbytes` — and, from the read that queues it, a frame beyond
+ * the table's `count`. sfx_ring_sizes keeps its meaning (video payloads); no stream, event or queue is added. */
+int sfx_ring_side_track(sfx_handle ring, const void* bytes, size_t nbytes, const uint64_t* ends, size_t count);
 
 /* Encoder hand-off, optional half (exporting.py:94-134): `frames` RGB8 frames (consecutive, width*height*3 bytes each) on
  * the device → planar yuv420p (I420: Y, U, V; width*height*3/2 bytes each) on the device, on the context's stream. BT.601 limited

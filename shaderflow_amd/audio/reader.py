@@ -20,6 +20,29 @@ import numpy as np
 from attrs import define
 
 
+def pcm_to_float(data: bytes, kind: int, bits: int, path) -> np.ndarray:
+    """The samples of a PCM stream (format tag 1: integers of 8/16/24/32 bits; 3: IEEE floats of 32/64) as flat float32"""
+    if kind == 3 and bits == 32:
+        return np.frombuffer(data, "<f4").astype(np.float32)
+    if kind == 3 and bits == 64:
+        return np.frombuffer(data, "<f8").astype(np.float32)
+    if kind == 1 and bits == 16:
+        return (np.frombuffer(data, "<i2").astype(np.float32)/np.float32(32768.0))
+    if kind == 1 and bits == 32:
+        return (np.frombuffer(data, "<i4").astype(np.float64)/2147483648.0).astype(np.float32)
+    if kind == 1 and bits == 24:
+        b = np.frombuffer(data[:len(data)//3*3], np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        v = np.where(v & 0x800000, v - 0x1000000, v)
+        return (v.astype(np.float64)/8388608.0).astype(np.float32)
+    if kind == 1 and bits == 8:
+        return ((np.frombuffer(data, np.uint8).astype(np.float32) - 128.0)/128.0).astype(np.float32)
+    raise ValueError(f"{path}: unsupported WAV format tag {kind} with {bits} bits")
+
+
+PCM_FORMATS = ((1, 8), (1, 16), (1, 24), (1, 32), (3, 32), (3, 64))
+
+
 def read_wav(path: Path) -> tuple[np.ndarray, int]:
     """Returns (samples float32 (n, channels), samplerate)"""
     raw = Path(path).read_bytes()
@@ -41,23 +64,7 @@ def read_wav(path: Path) -> tuple[np.ndarray, int]:
     if fmt is None or data is None:
         raise ValueError(f"{path}: missing fmt or data chunk")
     kind, channels, samplerate, _, _, bits = fmt
-    if kind == 3 and bits == 32:
-        pcm = np.frombuffer(data, "<f4").astype(np.float32)
-    elif kind == 3 and bits == 64:
-        pcm = np.frombuffer(data, "<f8").astype(np.float32)
-    elif kind == 1 and bits == 16:
-        pcm = (np.frombuffer(data, "<i2").astype(np.float32)/np.float32(32768.0))
-    elif kind == 1 and bits == 32:
-        pcm = (np.frombuffer(data, "<i4").astype(np.float64)/2147483648.0).astype(np.float32)
-    elif kind == 1 and bits == 24:
-        b = np.frombuffer(data[:len(data)//3*3], np.uint8).reshape(-1, 3).astype(np.int32)
-        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-        v = np.where(v & 0x800000, v - 0x1000000, v)
-        pcm = (v.astype(np.float64)/8388608.0).astype(np.float32)
-    elif kind == 1 and bits == 8:
-        pcm = ((np.frombuffer(data, np.uint8).astype(np.float32) - 128.0)/128.0).astype(np.float32)
-    else:
-        raise ValueError(f"{path}: unsupported WAV format tag {kind} with {bits} bits")
+    pcm = pcm_to_float(data, kind, bits, path)
     frames = pcm.size//channels
     return np.ascontiguousarray(pcm[:frames*channels].reshape(frames, channels)), int(samplerate)
 
@@ -88,9 +95,59 @@ def read_flac(path: Path) -> tuple[np.ndarray, int]:
     return out[:written.value], int(samplerate.value)
 
 
+def read_avi(path: Path) -> Optional[tuple[np.ndarray, int]]:
+    """The first `auds` stream of a RIFF AVI 1.0 file, if it is PCM (what `scene.main(sound_track=…)` writes beside its Motion-JPEG
+    frames, and many cameras): its `NNwb` chunks of `movi`, `rec ` lists included, in file order. None: no audio stream, or a
+    compressed one — the caller's other decoders may know it."""
+    raw = Path(path).read_bytes()
+
+    def chunks(pos: int, end: int):
+        while pos + 8 <= end:
+            tag, size = raw[pos:pos + 4], struct.unpack("<I", raw[pos + 4:pos + 8])[0]
+            yield tag, pos + 8, min(pos + 8 + size, end)
+            pos += 8 + size + (size & 1)
+
+    stream, fmt, movi = None, None, None
+    for tag, start, end in chunks(12, len(raw)):
+        if tag != b"LIST":
+            continue
+        if raw[start:start + 4] == b"hdrl":
+            number = 0
+            for inner, a, b in chunks(start + 4, end):
+                if inner != b"LIST" or raw[a:a + 4] != b"strl":
+                    continue
+                kind = None
+                for part, c, d in chunks(a + 4, b):
+                    if part == b"strh":
+                        kind = raw[c:c + 4]
+                    elif part == b"strf" and kind == b"auds" and stream is None and d - c >= 16:
+                        stream, fmt = number, struct.unpack("<HHIIHH", raw[c:c + 16])
+                        if fmt[0] == 0xFFFE and d - c >= 26:             # WAVE_FORMAT_EXTENSIBLE: sub-format GUID
+                            fmt = (struct.unpack("<H", raw[c + 24:c + 26])[0], *fmt[1:])
+                number += 1
+        elif raw[start:start + 4] == b"movi" and movi is None:
+            movi = (start + 4, end)
+    if stream is None or movi is None or (fmt[0], fmt[5]) not in PCM_FORMATS or fmt[1] < 1:
+        return None
+    wanted, parts = b"%02dwb" % stream, []
+
+    def walk(pos: int, end: int) -> None:
+        for tag, a, b in chunks(pos, end):
+            if tag == b"LIST" and raw[a:a + 4] == b"rec ":
+                walk(a + 4, b)
+            elif tag == wanted:
+                parts.append(raw[a:b])
+    walk(*movi)
+    kind, channels, samplerate, _, _, bits = fmt
+    pcm = pcm_to_float(b"".join(parts), kind, bits, path)
+    frames = pcm.size//channels
+    return np.ascontiguousarray(pcm[:frames*channels].reshape(frames, channels)), int(samplerate)
+
+
 def decode_audio(path: Path) -> tuple[np.ndarray, int]:
-    """(samples float32 (n, channels), samplerate) of any audio file: RIFF/WAVE and FLAC natively, other containers through an
-    `ffmpeg` binary as the reference does (pcm_f32le over a pipe, ffmpeg.py:1294-1301; samplerate and channels from ffprobe)"""
+    """(samples float32 (n, channels), samplerate) of any audio file: RIFF/WAVE and FLAC natively, and so the PCM stream of a RIFF AVI
+    file; other containers through an `ffmpeg` binary as the reference does (pcm_f32le over a pipe, ffmpeg.py:1294-1301; samplerate
+    and channels from ffprobe)"""
     raw = Path(path)
     with open(raw, "rb") as file:
         magic = file.read(12)
@@ -98,6 +155,10 @@ def decode_audio(path: Path) -> tuple[np.ndarray, int]:
         return read_wav(raw)
     if magic[:4] == b"fLaC":
         return read_flac(raw)
+    if magic[:4] == b"RIFF" and magic[8:12] == b"AVI ":
+        found = read_avi(raw)
+        if found is not None:
+            return found
     import shutil
     import subprocess
     if not (shutil.which("ffmpeg") and shutil.which("ffprobe")):

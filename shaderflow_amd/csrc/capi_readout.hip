@@ -15,6 +15,7 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#include <sys/uio.h>
 #include <unistd.h>
 
 using namespace sf;
@@ -526,6 +527,12 @@ struct Ring : Object {
     std::vector<uint32_t> payload;                  // per slot: bytes of the frame that landed (0: a failed frame, nothing is written)
     std::vector<uint32_t> sizes;                    // payload sizes in write order
     long frames_queued = 0, unfit_frame = -1;       // unfit_frame: a frame whose status said it did not fit (reported once by the next wait)
+    // side track (sfx_ring_side_track; `framing` 1): behind the ring's j-th frame the writer puts bytes [side_ends[j-1], side_ends[j]) of
+    // `side_bytes` as a "01wb" chunk. Both tables are the caller's, and stay the caller's.
+    const unsigned char* side_bytes = nullptr;
+    const uint64_t* side_ends = nullptr;
+    size_t side_count = 0;
+    std::vector<long> slot_frame;                   // per slot: the number of the frame read into it (counted from the ring's first)
 };
 constexpr uint32_t SINK_MAGIC = 0x504a4653u;        // jpeg_kernels.hpp JPEG_SINK_MAGIC
 constexpr size_t SINK_HEADER = 64;
@@ -607,28 +614,48 @@ static void ring_writer(Ring* r) {
             job = r->queue.front(); r->queue.pop_front();
             r->idle.wait(lock, [&] { return r->copying[job.first] == 0; });      // the frame has landed in the slot's host buffer
         }
-        const char* p = (const char*)r->host[job.first];
-        size_t left = r->frame_bytes;
+        // one run of bytes for write(): the frame, and behind it (a side track) the chunk header, the track's bytes and their pad byte
+        struct iovec run[4];
+        int parts = 1;
+        run[0].iov_base = r->host[job.first]; run[0].iov_len = r->frame_bytes;
+        char side_head[8];
+        static const char zero = 0;
         if (r->sized) {
-            // the framing goes into the header's last bytes, right in front of the payload: one run of bytes for write()
-            uint32_t size;
-            { std::lock_guard<std::mutex> lock(r->mutex); size = r->payload[job.first]; if (size) r->sizes.push_back(size); }
+            // the framing goes into the header's last bytes, right in front of the payload
+            uint32_t size; long frame;
+            { std::lock_guard<std::mutex> lock(r->mutex); size = r->payload[job.first]; frame = r->slot_frame[job.first]; if (size) r->sizes.push_back(size); }
             char* start = (char*)r->host[job.first] + SINK_HEADER;
-            left = size;
+            size_t left = size;
             if (size && r->framing == 1) {
                 start[size] = 0;                                       // the pad byte to an even length
                 left = size + (size & 1) + 8;
                 start -= 8;
                 memcpy(start, "00dc", 4);
                 for (int k = 0; k < 4; k++) start[4 + k] = (char)(size >> 8*k);
+                if (r->side_ends && (size_t)frame < r->side_count) {
+                    const uint64_t from = frame ? r->side_ends[frame - 1] : 0, side = r->side_ends[frame] - from;
+                    if (side) {
+                        memcpy(side_head, "01wb", 4);
+                        for (int k = 0; k < 4; k++) side_head[4 + k] = (char)(side >> 8*k);
+                        run[1].iov_base = side_head; run[1].iov_len = 8;
+                        run[2].iov_base = (void*)(r->side_bytes + from); run[2].iov_len = (size_t)side;
+                        run[3].iov_base = (void*)&zero; run[3].iov_len = (size_t)(side & 1);
+                        parts = 4;
+                    }
+                }
             }
-            p = start;
+            run[0].iov_base = start; run[0].iov_len = left;
         }
         int err = 0;
-        while (left > 0) {
-            ssize_t n = ::write(job.second, p, left);
+        for (int part = 0; part < parts && !err;) {
+            if (run[part].iov_len == 0) { part++; continue; }
+            ssize_t n = parts - part == 1 ? ::write(job.second, run[part].iov_base, run[part].iov_len) : ::writev(job.second, run + part, parts - part);
             if (n < 0) { if (errno == EINTR) continue; err = errno; break; }
-            p += n; left -= (size_t)n;
+            while (n > 0 && part < parts) {
+                const size_t took = std::min((size_t)n, run[part].iov_len);
+                run[part].iov_base = (char*)run[part].iov_base + took; run[part].iov_len -= took; n -= (ssize_t)took;
+                if (run[part].iov_len == 0) part++;
+            }
         }
         {
             std::lock_guard<std::mutex> lock(r->mutex);
@@ -646,7 +673,7 @@ static int ring_create(sfx_handle h, size_t frame_bytes, int slots, bool sized, 
     USE_DEVICE(c);
     Ring* r = new Ring();
     r->magic = MAGIC_RING; r->ctx = c; r->frame_bytes = frame_bytes; r->slots = slots;
-    r->sized = sized; r->framing = framing; r->payload.assign(slots, 0);
+    r->sized = sized; r->framing = framing; r->payload.assign(slots, 0); r->slot_frame.assign(slots, 0);
     r->host.resize(slots); r->ready.resize(slots); r->pending.assign(slots, 0); r->copying.assign(slots, 0);
     r->lane_count = std::min(EngineLanes::LANES, std::max(1, slots - 1));                             // (a slot is being filled or written while the others land)
     if (const char* n = getenv("SHADERFLOW_COPY_STREAMS")) r->lane_count = std::min(r->lane_count, std::max(1, atoi(n)));   // A/B switch for measurements
@@ -679,6 +706,25 @@ extern "C" int sfx_ring_sizes(sfx_handle h, uint32_t* out, size_t capacity, size
     return SFX_OK;
 }
 
+// A side track for a sized ring with `framing` 1 (an AVI file's second stream): `ends[j]` is where, in `bytes`, the share of the ring's
+// j-th frame ends (the first one's begins at 0). The writer thread owns the order of bytes on the sink's descriptor, so the share goes
+// out there — right behind its frame, in the same run of bytes — as "01wb", size, bytes, a pad byte to an even length; an empty share
+// writes nothing, and neither does the share of a frame that is not written. The tables are borrowed until sfx_ring_destroy.
+extern "C" int sfx_ring_side_track(sfx_handle h, const void* bytes, size_t nbytes, const uint64_t* ends, size_t count) {
+    Ring* r = get<Ring>(h, MAGIC_RING);
+    if (!r || !r->sized || r->framing != 1) return fail(SFX_E_INVALID, "a side track needs a sized ring with framing 1");
+    if ((!bytes && nbytes) || !ends || !count) return fail(SFX_E_INVALID, "side track: null table");
+    uint64_t from = 0;
+    for (size_t j = 0; j < count; j++) {
+        if (ends[j] < from || ends[j] > nbytes || ends[j] - from > 0xffffffffull) return fail(SFX_E_INVALID, "side track: entry %zu ends at %llu (the one before at %llu, %zu bytes in all)", j, (unsigned long long)ends[j], (unsigned long long)from, nbytes);
+        from = ends[j];
+    }
+    std::lock_guard<std::mutex> lock(r->mutex);
+    if (r->frames_queued) return fail(SFX_E_INVALID, "side track: the ring has taken %ld frame(s) already", r->frames_queued);
+    r->side_bytes = (const unsigned char*)bytes; r->side_ends = ends; r->side_count = count;
+    return SFX_OK;
+}
+
 // a frame of a sized ring whose status said it did not fit: reported once, by the wait that meets it; the ring goes on working
 static int ring_unfit(Ring* r) {
     const long frame = r->unfit_frame;
@@ -702,7 +748,9 @@ static int ring_wait_copy(Ring* r, int slot) {
 static int ring_queue_copy(Ring* r, const void* dptr, int slot, hipEvent_t ready) {
     {
         std::lock_guard<std::mutex> lock(r->mutex);
+        if (r->side_ends && (size_t)r->frames_queued >= r->side_count) return fail(SFX_E_INVALID, "frame %ld of a ring whose side track has %zu entries", r->frames_queued, r->side_count);
         r->copying[slot] = 1;
+        r->slot_frame[slot] = r->frames_queued;
         r->copy_queue.push_back({slot, dptr, ready, r->frames_queued++});
     }
     r->copy_wake.notify_one();

@@ -69,6 +69,12 @@ class ExportingHelper:
     _encoder: Optional[N.JpegEncoder] = None
     _avi: Optional[mjpeg.AviWriter] = None
     _sizes: list = Factory(list)          # payload sizes of the mjpeg frames written, in order (the AVI index)
+    sound_track: Any = False
+    """An mjpeg export to `.avi` carries the scene's sound (mjpeg.py states the stream): True — the scene's one ShaderAudio that holds a
+    loaded clip, from `file=` or `samples=` — or that module, or its name. The ring's writer thread puts each frame's share of the PCM
+    behind the frame (sfx_ring_side_track): it alone orders the bytes on the sink's descriptor, in all three loops."""
+    _track: Optional[mjpeg.SoundTrack] = None
+    _track_ends: Optional[np.ndarray] = None   # the ring borrows it (and the track's pcm) until it is destroyed
 
     # ring
     ring: Optional[N.Handle] = None
@@ -161,6 +167,34 @@ class ExportingHelper:
         self.ffmpeg.scale(width=width, height=height)
         self.ffmpeg.vflip()
 
+    @property
+    def wants_track(self) -> bool:
+        return self.sound_track is not False and self.sound_track is not None
+
+    def find_track(self) -> mjpeg.SoundTrack:
+        """The clip `sound_track` names, as the file will hold it; ValueError when the export cannot hold one or the scene has none"""
+        from shaderflow_amd.audio import ShaderAudio
+        rule = "sound_track goes into an '.avi' file of a Motion-JPEG export (output='clip.avi', pixel_format='mjpeg')"
+        if not self.mjpeg:
+            raise ValueError(f"{rule}, not pixel_format {self.pixel_format!r}: the ffmpeg branch already attaches the audio file through ShaderAudio.ffhook")
+        if self.kind == "pipe" or self.container != "avi":
+            raise ValueError(f"{rule}: {'a pipe' if self.kind == 'pipe' else repr(self.path.suffix)} delivers the bare JPEG images back to back")
+        loaded = [module for module in self.scene.modules if isinstance(module, ShaderAudio) and module._file_reader is not None]
+        wanted = self.sound_track
+        if wanted is True:
+            if len(loaded) > 1:
+                raise ValueError(f"sound_track=True: the scene has {len(loaded)} audio modules with a clip ({', '.join(repr(m.name) for m in loaded)}); name one")
+            chosen = loaded
+        elif isinstance(wanted, str):
+            chosen = [module for module in loaded if module.name == wanted][:1]
+        else:
+            chosen = [module for module in loaded if module is wanted]
+        if not chosen:
+            which = "no audio module" if wanted is True else f"no audio module {getattr(wanted, 'name', wanted)!r}"
+            raise ValueError(f"sound_track: the scene has {which} with a loaded clip (ShaderAudio file= or load(samples=…))")
+        reader = chosen[0]._file_reader
+        return mjpeg.SoundTrack(reader.samples, reader.samplerate)
+
     def ffmpeg_output(self, output) -> None:
         if self.mjpeg:
             if (output in ("pipe", "-", bytes)):
@@ -168,11 +202,16 @@ class ExportingHelper:
             else:
                 self.path = Path(output).expanduser().absolute()
                 self.container = mjpeg.container_of(self.path.suffix)
-                self.path.parent.mkdir(parents=True, exist_ok=True)
                 self.kind = "path-mjpeg"
+            if self.wants_track:
+                self._track = self.find_track()
+            if self.path is not None:
+                self.path.parent.mkdir(parents=True, exist_ok=True)
             if self.top_down is None:
                 self.top_down = False                         # the encoder reads the rows in the order it needs
             return
+        if self.wants_track:
+            self.find_track()
         if (output in ("pipe", "-", bytes)):
             self.kind = "pipe"
             self.ffmpeg.pipe_output()
@@ -215,7 +254,7 @@ class ExportingHelper:
             self.file = open(self.path, "wb", buffering=0)
             self.fileno = self.file.fileno()
             if self.container == "avi":
-                self._avi = mjpeg.AviWriter(self.fileno, self.scene.width, self.scene.height, self.scene.fps)
+                self._avi = mjpeg.AviWriter(self.fileno, self.scene.width, self.scene.height, self.scene.fps, track=self._track)
                 self._avi.begin()
         elif self.kind == "pipe":
             self.file = tempfile.TemporaryFile(mode="w+b")
@@ -231,6 +270,10 @@ class ExportingHelper:
         else:
             N.check(N.lib().sfx_ring_create(self.scene.context.handle, self.frame_bytes, max(1, n), C.byref(handle)))
         self.ring, self.slots = handle, max(1, n)
+        if self._track is not None:
+            self._track_ends = self._track.ends(self.total_frames, self.scene.fps)
+            N.check(N.lib().sfx_ring_side_track(handle, self._track.pcm.ctypes.data, self._track.pcm.nbytes,
+                                                N.as_ptr(self._track_ends, C.c_uint64), len(self._track_ends)))
         if self.staged:
             self._yuv_slots = [self.scene.context.alloc(self.frame_bytes) for _ in range(self.slots)]
 

@@ -317,6 +317,7 @@ class ShaderScene(ShaderModule):
         shard: Optional[tuple[int, int]] = None,
         pixel_format: Optional[str] = None,
         jpeg_quality: int = 90,
+        sound_track: Any = False,
     ) -> Optional[Union[Path, bytes]]:
         """Render the scene to `output` (scene.py:493-639). `output` may be a path (raw rgb24 frames, or a video
         when an `ffmpeg` binary exists), "pipe"/"-"/bytes (returns the raw frames), or None with freewheel=True
@@ -325,7 +326,9 @@ class ShaderScene(ShaderModule):
         `shard`: (rank, world) to run ONE rank's share of a sharded frame-loop export without a process group (tests,
         external launchers); with torch.distributed initialised the group's rank and size are used.
         `pixel_format`: "rgb24" (default: the reference's stream) or "yuv420p" — converted on the device (ExportingHelper.pixel_format) — or "mjpeg": baseline
-        JPEG frames encoded on the device at `jpeg_quality` (1…100) into `.avi`, `.mjpeg` or "pipe", no ffmpeg (ExportingHelper.jpeg_quality)."""
+        JPEG frames encoded on the device at `jpeg_quality` (1…100) into `.avi`, `.mjpeg` or "pipe", no ffmpeg (ExportingHelper.jpeg_quality).
+        `sound_track`: an mjpeg export to `.avi` carries the scene's sound as a PCM stream — True (the scene's one ShaderAudio with a loaded clip), that
+        module, or its name (ExportingHelper.sound_track; mjpeg.py states the stream)."""
         self.initialize()
         self.exporting = (bool(output))
         self.freewheel = (self.exporting or freewheel)
@@ -359,7 +362,9 @@ class ShaderScene(ShaderModule):
             self.ssaa = ssaa
 
         export = ExportingHelper(self, top_down=top_down, pixel_format=(pixel_format or os.environ.get("SHADERFLOW_PIXEL_FORMAT") or "rgb24"),
-                                 jpeg_quality=jpeg_quality)
+                                 jpeg_quality=jpeg_quality, sound_track=sound_track)
+        if export.wants_track and not self.exporting:
+            raise ValueError("sound_track goes into an '.avi' file of a Motion-JPEG export (output='clip.avi', pixel_format='mjpeg'): there is no output")
         if self.exporting and export.mjpeg and (is_sharded() or shard is not None):
             raise ValueError("pixel_format 'mjpeg' is not sharded: frames of their own length have no place in the ranks' fixed-stride gather")
         if (self.exporting):

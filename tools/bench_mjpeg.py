@@ -4,6 +4,10 @@ frame, and — from `rocprofv3 --kernel-trace --stats` over a short mjpeg export
 Writes profiles/mjpeg_bench.txt. GPU box only.
 
     python tools/bench_mjpeg.py [--frames 1800] [--no-profile]
+
+`--sound-track`: the sound-track leg alone — the same export at quality 90 to an `.avi` file (memory-backed where /dev/shm exists: an
+AVI is seeked and truncated, /dev/null will not do), with and without `sound_track=True`, taking turns, three runs each after one
+unmeasured run of both. Its lines are APPENDED to profiles/mjpeg_bench.txt.
 """
 import argparse
 import csv
@@ -27,10 +31,38 @@ def visualizer():
     return make(Visualizer, audio=(synth.sweep_clip(32.0, 44100), 44100), background=synth.background_image(1920, 1080, seed=0))
 
 
-def export(pixel_format: str, quality: int, frames: int, output) -> tuple[float, object]:
+def export(pixel_format: str, quality: int, frames: int, output, **options) -> tuple[float, object]:
     started = time.perf_counter()
-    result = visualizer().main(width=W, height=H, ssaa=SSAA, fps=FPS, time=frames/FPS, output=output, pixel_format=pixel_format, jpeg_quality=quality)
+    result = visualizer().main(width=W, height=H, ssaa=SSAA, fps=FPS, time=frames/FPS, output=output, pixel_format=pixel_format, jpeg_quality=quality, **options)
     return time.perf_counter() - started, result
+
+
+def sound_track_leg(frames: int) -> list[str]:
+    """frames/s of the `.avi` export with and without the track, run in turns in this process"""
+    from shaderflow_amd import _native as N
+    rates: dict = {False: [], True: []}
+    sizes: dict = {}
+    with tempfile.TemporaryDirectory(dir="/dev/shm" if os.path.isdir("/dev/shm") else None) as directory:
+        for run in range(4):                                            # the first of each is not measured
+            for track in (False, True):
+                path = Path(directory)/"clip.avi"
+                took, _ = export("mjpeg", 90, frames, path, sound_track=track)
+                sizes[track] = path.stat().st_size
+                path.unlink()
+                if run:
+                    rates[track].append(frames/took)
+                    print(f"run {run} {'with' if track else 'without'} the track: {frames/took:7.0f} frames/s", flush=True)
+    without, with_track = rates[False], rates[True]
+    spread = max(without) - min(without)
+    mean = (lambda values: sum(values)/len(values))
+    lines = [f"sound track: mjpeg q90 to an .avi file in {'/dev/shm' if os.path.isdir('/dev/shm') else 'the temporary directory'}, {frames} frames, "
+             f"three runs each in turns after one unmeasured run of both, kernel sources {N.source_fingerprint()}",
+             f"  without the track: {', '.join(f'{r:.0f}' for r in without)} frames/s (mean {mean(without):.0f}, spread {spread:.0f}), {sizes[False]} bytes",
+             f"  with the track   : {', '.join(f'{r:.0f}' for r in with_track)} frames/s (mean {mean(with_track):.0f}), {sizes[True]} bytes "
+             f"({(sizes[True] - sizes[False])/frames:.0f} more per frame)",
+             f"  mean with - mean without = {mean(with_track) - mean(without):+.0f} frames/s: "
+             + ("within" if mean(without) - mean(with_track) <= spread else "BELOW the no-track runs by more than") + " the spread among the no-track runs"]
+    return lines
 
 
 def kernel_times(quality: int, frames: int) -> list[str]:
@@ -60,7 +92,14 @@ def main() -> None:
     parser.add_argument("--frames", type=int, default=1800)
     parser.add_argument("--child", type=int, default=None, help="(internal) one mjpeg export at this quality, nothing else")
     parser.add_argument("--no-profile", action="store_true")
+    parser.add_argument("--sound-track", action="store_true", help="the sound-track leg alone, appended to profiles/mjpeg_bench.txt")
     args = parser.parse_args()
+    if args.sound_track:
+        lines = sound_track_leg(args.frames)
+        with open(ROOT/"profiles"/"mjpeg_bench.txt", "a") as file:
+            file.write("\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     if args.child is not None:
         with tempfile.TemporaryDirectory() as directory:
             os.symlink("/dev/null", Path(directory)/"null.mjpeg")
