@@ -2,6 +2,8 @@
 // uint). Expects SF_RT_T (scalar), SF_RT_V2/3/4 (the types defined here), SF_RT_O2/3/4 (the other integer family).
 // Same shape as the float vectors: a union of component names, an array and every GLSL swizzle.
 
+struct bvec2; struct bvec3; struct bvec4;      // defined after both integer families (jit_runtime.hpp)
+
 struct SF_RT_V2 {
     union {
         struct { SF_RT_T x, y; }; struct { SF_RT_T r, g; }; struct { SF_RT_T s, t; };
@@ -19,6 +21,7 @@ struct SF_RT_V2 {
     SF_HD SF_RT_V2(SF_RT_T a, SF_RT_T b) { x = a; y = b; }
     SF_HD explicit SF_RT_V2(const vec2& v);
     SF_HD explicit SF_RT_V2(const SF_RT_O2& v);
+    SF_HD explicit SF_RT_V2(const bvec2& v);
     SF_HD SF_RT_V2(const SF_RT_V2& o) { for (int k = 0; k < 2; k++) d[k] = o.d[k]; }
     SF_HD SF_RT_V2& operator=(const SF_RT_V2& o) { for (int k = 0; k < 2; k++) d[k] = o.d[k]; return *this; }
     SF_HD SF_RT_T& operator[](int k) { return d[k]; }
@@ -43,6 +46,7 @@ struct SF_RT_V3 {
     SF_HD SF_RT_V3(SF_RT_T a, const SF_RT_V2& b) { x = a; y = b.x; z = b.y; }
     SF_HD explicit SF_RT_V3(const vec3& v);
     SF_HD explicit SF_RT_V3(const SF_RT_O3& v);
+    SF_HD explicit SF_RT_V3(const bvec3& v);
     SF_HD SF_RT_V3(const SF_RT_V3& o) { for (int k = 0; k < 3; k++) d[k] = o.d[k]; }
     SF_HD SF_RT_V3& operator=(const SF_RT_V3& o) { for (int k = 0; k < 3; k++) d[k] = o.d[k]; return *this; }
     SF_HD SF_RT_T& operator[](int k) { return d[k]; }
@@ -68,6 +72,7 @@ struct SF_RT_V4 {
     SF_HD SF_RT_V4(const SF_RT_V2& u, SF_RT_T c, SF_RT_T e) { x = u.x; y = u.y; z = c; w = e; }
     SF_HD explicit SF_RT_V4(const vec4& v);
     SF_HD explicit SF_RT_V4(const SF_RT_O4& v);
+    SF_HD explicit SF_RT_V4(const bvec4& v);
     SF_HD SF_RT_V4(const SF_RT_V4& o) { for (int k = 0; k < 4; k++) d[k] = o.d[k]; }
     SF_HD SF_RT_V4& operator=(const SF_RT_V4& o) { for (int k = 0; k < 4; k++) d[k] = o.d[k]; return *this; }
     SF_HD SF_RT_T& operator[](int k) { return d[k]; }

@@ -94,9 +94,40 @@ struct ivec2; struct ivec3; struct ivec4; struct uvec2; struct uvec3; struct uve
 #undef SF_RT_O2
 #undef SF_RT_O3
 #undef SF_RT_O4
-struct bvec2 { bool x, y; };
-struct bvec3 { bool x, y, z; };
-struct bvec4 { bool x, y, z, w; };
+// boolean vectors: components by name; from a scalar, from components and from any other vector of the size (§5.4.1: != 0)
+struct bvec2 {
+    bool x, y;
+    SF_HD bvec2() : x(false), y(false) {}
+    SF_HD explicit bvec2(bool v) : x(v), y(v) {}
+    SF_HD bvec2(bool a, bool b) : x(a), y(b) {}
+    SF_HD explicit bvec2(const ivec2& v) : x(v.x != 0), y(v.y != 0) {}
+    SF_HD explicit bvec2(const uvec2& v) : x(v.x != 0u), y(v.y != 0u) {}
+    SF_HD explicit bvec2(const vec2& v);
+};
+struct bvec3 {
+    bool x, y, z;
+    SF_HD bvec3() : x(false), y(false), z(false) {}
+    SF_HD explicit bvec3(bool v) : x(v), y(v), z(v) {}
+    SF_HD bvec3(bool a, bool b, bool c) : x(a), y(b), z(c) {}
+    SF_HD explicit bvec3(const ivec3& v) : x(v.x != 0), y(v.y != 0), z(v.z != 0) {}
+    SF_HD explicit bvec3(const uvec3& v) : x(v.x != 0u), y(v.y != 0u), z(v.z != 0u) {}
+    SF_HD explicit bvec3(const vec3& v);
+};
+struct bvec4 {
+    bool x, y, z, w;
+    SF_HD bvec4() : x(false), y(false), z(false), w(false) {}
+    SF_HD explicit bvec4(bool v) : x(v), y(v), z(v), w(v) {}
+    SF_HD bvec4(bool a, bool b, bool c, bool e) : x(a), y(b), z(c), w(e) {}
+    SF_HD explicit bvec4(const ivec4& v) : x(v.x != 0), y(v.y != 0), z(v.z != 0), w(v.w != 0) {}
+    SF_HD explicit bvec4(const uvec4& v) : x(v.x != 0u), y(v.y != 0u), z(v.z != 0u), w(v.w != 0u) {}
+    SF_HD explicit bvec4(const vec4& v);
+};
+SF_HD ivec2::ivec2(const bvec2& v) { x = v.x ? 1 : 0; y = v.y ? 1 : 0; }
+SF_HD ivec3::ivec3(const bvec3& v) { x = v.x ? 1 : 0; y = v.y ? 1 : 0; z = v.z ? 1 : 0; }
+SF_HD ivec4::ivec4(const bvec4& v) { x = v.x ? 1 : 0; y = v.y ? 1 : 0; z = v.z ? 1 : 0; w = v.w ? 1 : 0; }
+SF_HD uvec2::uvec2(const bvec2& v) { x = v.x ? 1u : 0u; y = v.y ? 1u : 0u; }
+SF_HD uvec3::uvec3(const bvec3& v) { x = v.x ? 1u : 0u; y = v.y ? 1u : 0u; z = v.z ? 1u : 0u; }
+SF_HD uvec4::uvec4(const bvec4& v) { x = v.x ? 1u : 0u; y = v.y ? 1u : 0u; z = v.z ? 1u : 0u; w = v.w ? 1u : 0u; }
 
 struct vec2 {
     union {
@@ -178,6 +209,9 @@ struct vec4 {
 SF_HD vec2::vec2(const vec3& v) { x = v.x; y = v.y; }
 SF_HD vec2::vec2(const vec4& v) { x = v.x; y = v.y; }
 SF_HD vec3::vec3(const vec4& v) { x = v.x; y = v.y; z = v.z; }
+SF_HD bvec2::bvec2(const vec2& v) : x(v.x != 0.0f), y(v.y != 0.0f) {}
+SF_HD bvec3::bvec3(const vec3& v) : x(v.x != 0.0f), y(v.y != 0.0f), z(v.z != 0.0f) {}
+SF_HD bvec4::bvec4(const vec4& v) : x(v.x != 0.0f), y(v.y != 0.0f), z(v.z != 0.0f), w(v.w != 0.0f) {}
 
 // `.length()` of arrays and vectors (the translator writes length_of(name))
 template <class T, int N> SF_HD constexpr int length_of(const T (&)[N]) { return N; }
@@ -264,6 +298,16 @@ SF_RT_ARITH(vec4, 4)
 //     around zero (exp(x) - exp(-x))/2 cancels (sinh(x) = 0 for |x| <= 2^-25, sinh(1e-4) is 2281 ulp off, 2e-7 absolute at most):
 //     fine for a pixel, not fixed. tan 3.02, asin 3.12, acos 3.15, inversesqrt 1.39 ulp: bounds in tests/math_cases.py.
 //   * atan(y, x) with both operands infinite is NaN (inf/inf); round() takes exact halves towards +inf.
+// The vector, matrix and integer forms below, the swizzles above and the prelude further down are held by tests/vector_cases.py
+// (test_host_vector.py / test_gpu_vector.py), row by row, the same bits on host and device:
+//   * every vecN form is the scalar form at each component; dot, length … refract, the matrix operators, determinant and inverse
+//     are their formulas in the written order (left-to-right sums of rounded products, -ffp-contract=off), with float64 witnesses
+//     gamma_k * sum|terms| (dot, m*v, v*m, m*m: k = N; cross 2; reflect N + 2; determinant 2 / 5 / 10) and inverse(m)*m - I below
+//     2^-18 / 2^-17 / 2^-16 for mat2/3/4 of condition number <= 100.
+//   * pinned definitions: length and distance are sqrt(dot) (inf where the sum of squares overflows, 0 where it underflows),
+//     normalize(0) is NaN, the inverse of a singular matrix is inf/NaN, integer / and % are C's (truncation, the dividend's sign),
+//     abs(INT_MIN) is INT_MIN (-fwrapv), min/max/clamp on uint compare unsigned and return uint.
+//   * not here: non-square matrices.
 constexpr float SINCOS_REACH = 1048576.0f;
 SF_HD float within_reach(float x) { return (sf::abs(x) > SINCOS_REACH) ? ::fmodf(x, TAU) : x; }
 SF_HD float radians(float x) { return x*(PI/180.0f); }
@@ -307,6 +351,13 @@ SF_HD float length(float x) { return sf::abs(x); }
 SF_HD float distance(float a, float b) { return sf::abs(a - b); }
 SF_HD float dot(float a, float b) { return a*b; }
 SF_HD float normalize(float x) { return sf::sign(x); }
+SF_HD float reflect(float i, float n) { return i - (2.0f*dot(n, i))*n; }
+SF_HD float faceforward(float n, float i, float nref) { return (dot(nref, i) < 0.0f) ? n : -n; }
+SF_HD float refract(float i, float n, float eta) {
+    const float c = dot(n, i); const float k = 1.0f - eta*eta*(1.0f - c*c);
+    if (k < 0.0f) return 0.0f;
+    return eta*i - (eta*c + sf::sqrt(k))*n;
+}
 SF_HD int floatBitsToInt(float x) { return (int)f2u(x); }
 SF_HD uint floatBitsToUint(float x) { return f2u(x); }
 SF_HD float intBitsToFloat(int x) { return u2f((uint32_t)x); }
@@ -325,14 +376,39 @@ SF_HD vec2 uintBitsToFloat(const uvec2& v) { return vec2(u2f(v.x), u2f(v.y)); }
 SF_HD vec3 uintBitsToFloat(const uvec3& v) { return vec3(u2f(v.x), u2f(v.y), u2f(v.z)); }
 SF_HD vec4 uintBitsToFloat(const uvec4& v) { return vec4(u2f(v.x), u2f(v.y), u2f(v.z), u2f(v.w)); }
 
-// integer forms: exact-match templates, so that (float, int) arguments pick the float overloads like GLSL does
-#define SF_RT_INTS(A, B) typename std::enable_if<std::is_integral<A>::value && std::is_integral<B>::value && !std::is_same<A, bool>::value, int>::type
-template <class A, class B> SF_HD SF_RT_INTS(A, B) min(A a, B b) { return ((int)b < (int)a) ? (int)b : (int)a; }
-template <class A, class B> SF_HD SF_RT_INTS(A, B) max(A a, B b) { return ((int)a < (int)b) ? (int)b : (int)a; }
-template <class A, class B, class C> SF_HD typename std::enable_if<std::is_integral<A>::value && std::is_integral<B>::value && std::is_integral<C>::value, int>::type
-clamp(A x, B lo, C hi) { const int v = ((int)x < (int)lo) ? (int)lo : (int)x; return (v > (int)hi) ? (int)hi : v; }
+// integer forms: exact-match templates, so that (float, int) arguments pick the float overloads like GLSL does. Operands that are
+// all uint compare unsigned and give a uint (genUType, §8.3); every other mix of integers is the int form
+template <class... T> struct int_result { typedef int type; };
+template <> struct int_result<uint, uint> { typedef uint type; };
+template <> struct int_result<uint, uint, uint> { typedef uint type; };
+#define SF_RT_INTS(A, B) typename std::enable_if<std::is_integral<A>::value && std::is_integral<B>::value && !std::is_same<A, bool>::value, typename int_result<A, B>::type>::type
+template <class A, class B> SF_HD SF_RT_INTS(A, B) min(A a, B b) { typedef typename int_result<A, B>::type R; return ((R)b < (R)a) ? (R)b : (R)a; }
+template <class A, class B> SF_HD SF_RT_INTS(A, B) max(A a, B b) { typedef typename int_result<A, B>::type R; return ((R)a < (R)b) ? (R)b : (R)a; }
+template <class A, class B, class C> SF_HD typename std::enable_if<std::is_integral<A>::value && std::is_integral<B>::value && std::is_integral<C>::value, typename int_result<A, B, C>::type>::type
+clamp(A x, B lo, C hi) { typedef typename int_result<A, B, C>::type R; const R v = ((R)x < (R)lo) ? (R)lo : (R)x; return (v > (R)hi) ? (R)hi : v; }
 SF_HD int abs(int x) { return (x < 0) ? -x : x; }
 SF_HD int sign(int x) { return (x > 0) - (x < 0); }
+// … and their vector forms (genIType, genUType), with vector and with scalar bounds; abs(INT_MIN) wraps to INT_MIN (-fwrapv)
+#define SF_RT_IMAP(V, T, N) \
+    SF_HD V min(const V& a, const V& b) { V r; for (int k = 0; k < N; k++) r.d[k] = min(a.d[k], b.d[k]); return r; } \
+    SF_HD V min(const V& a, T b) { V r; for (int k = 0; k < N; k++) r.d[k] = min(a.d[k], b); return r; } \
+    SF_HD V max(const V& a, const V& b) { V r; for (int k = 0; k < N; k++) r.d[k] = max(a.d[k], b.d[k]); return r; } \
+    SF_HD V max(const V& a, T b) { V r; for (int k = 0; k < N; k++) r.d[k] = max(a.d[k], b); return r; } \
+    SF_HD V clamp(const V& x, const V& lo, const V& hi) { V r; for (int k = 0; k < N; k++) r.d[k] = clamp(x.d[k], lo.d[k], hi.d[k]); return r; } \
+    SF_HD V clamp(const V& x, T lo, T hi) { V r; for (int k = 0; k < N; k++) r.d[k] = clamp(x.d[k], lo, hi); return r; }
+SF_RT_IMAP(ivec2, int, 2) SF_RT_IMAP(ivec3, int, 3) SF_RT_IMAP(ivec4, int, 4)
+SF_RT_IMAP(uvec2, uint, 2) SF_RT_IMAP(uvec3, uint, 3) SF_RT_IMAP(uvec4, uint, 4)
+#define SF_RT_IMAP1(name) \
+    SF_HD ivec2 name(const ivec2& a) { return ivec2(name(a.x), name(a.y)); } \
+    SF_HD ivec3 name(const ivec3& a) { return ivec3(name(a.x), name(a.y), name(a.z)); } \
+    SF_HD ivec4 name(const ivec4& a) { return ivec4(name(a.x), name(a.y), name(a.z), name(a.w)); }
+SF_RT_IMAP1(abs) SF_RT_IMAP1(sign)
+SF_HD bvec2 isnan(const vec2& a) { return {isnan(a.x), isnan(a.y)}; }
+SF_HD bvec3 isnan(const vec3& a) { return {isnan(a.x), isnan(a.y), isnan(a.z)}; }
+SF_HD bvec4 isnan(const vec4& a) { return {isnan(a.x), isnan(a.y), isnan(a.z), isnan(a.w)}; }
+SF_HD bvec2 isinf(const vec2& a) { return {isinf(a.x), isinf(a.y)}; }
+SF_HD bvec3 isinf(const vec3& a) { return {isinf(a.x), isinf(a.y), isinf(a.z)}; }
+SF_HD bvec4 isinf(const vec4& a) { return {isinf(a.x), isinf(a.y), isinf(a.z), isinf(a.w)}; }
 
 #define SF_RT_MAP1(name) \
     SF_HD vec2 name(const vec2& a) { return vec2(name(a.x), name(a.y)); } \
@@ -414,6 +490,7 @@ SF_HD vec4 modf(const vec4& x, vec4& whole) { whole = trunc(x); return x - whole
 #define SF_RT_REL(name, op) SF_RT_REL3(name, op, vec2, vec3, vec4) SF_RT_REL3(name, op, ivec2, ivec3, ivec4) SF_RT_REL3(name, op, uvec2, uvec3, uvec4)
 SF_RT_REL(lessThan, <) SF_RT_REL(lessThanEqual, <=) SF_RT_REL(greaterThan, >) SF_RT_REL(greaterThanEqual, >=)
 SF_RT_REL(equal, ==) SF_RT_REL(notEqual, !=)
+SF_RT_REL3(equal, ==, bvec2, bvec3, bvec4) SF_RT_REL3(notEqual, !=, bvec2, bvec3, bvec4)
 SF_HD bool any(bvec2 b) { return b.x || b.y; }
 SF_HD bool any(bvec3 b) { return b.x || b.y || b.z; }
 SF_HD bool any(bvec4 b) { return b.x || b.y || b.z || b.w; }
@@ -443,6 +520,12 @@ struct matn {
     SF_HD const V& operator[](int j) const { return c[j]; }
     SF_HD matn& operator*=(const matn& o) { *this = *this*o; return *this; }
     SF_HD matn& operator*=(float s) { for (int j = 0; j < N; j++) c[j] *= s; return *this; }
+    SF_HD matn& operator/=(float s) { for (int j = 0; j < N; j++) c[j] /= s; return *this; }
+    SF_HD matn& operator+=(float s) { for (int j = 0; j < N; j++) c[j] += s; return *this; }
+    SF_HD matn& operator-=(float s) { for (int j = 0; j < N; j++) c[j] -= s; return *this; }
+    SF_HD matn& operator+=(const matn& o) { for (int j = 0; j < N; j++) c[j] += o.c[j]; return *this; }      // component-wise, like + - / of two matrices
+    SF_HD matn& operator-=(const matn& o) { for (int j = 0; j < N; j++) c[j] -= o.c[j]; return *this; }
+    SF_HD matn& operator/=(const matn& o) { for (int j = 0; j < N; j++) c[j] /= o.c[j]; return *this; }
 };
 typedef matn<vec2, 2> mat2; typedef matn<vec3, 3> mat3; typedef matn<vec4, 4> mat4;
 typedef mat2 mat2x2; typedef mat3 mat3x3; typedef mat4 mat4x4;
@@ -463,6 +546,14 @@ template <class V, int N> SF_HD matn<V, N> operator*(float s, const matn<V, N>& 
 template <class V, int N> SF_HD matn<V, N> operator/(const matn<V, N>& a, float s) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = a.c[j]/s; return r; }
 template <class V, int N> SF_HD matn<V, N> operator+(const matn<V, N>& a, const matn<V, N>& b) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = a.c[j] + b.c[j]; return r; }
 template <class V, int N> SF_HD matn<V, N> operator-(const matn<V, N>& a, const matn<V, N>& b) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = a.c[j] - b.c[j]; return r; }
+template <class V, int N> SF_HD matn<V, N> operator/(const matn<V, N>& a, const matn<V, N>& b) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = a.c[j]/b.c[j]; return r; }
+template <class V, int N> SF_HD matn<V, N> operator/(float s, const matn<V, N>& a) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = s/a.c[j]; return r; }
+template <class V, int N> SF_HD matn<V, N> operator+(const matn<V, N>& a, float s) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = a.c[j] + s; return r; }
+template <class V, int N> SF_HD matn<V, N> operator+(float s, const matn<V, N>& a) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = s + a.c[j]; return r; }
+template <class V, int N> SF_HD matn<V, N> operator-(const matn<V, N>& a, float s) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = a.c[j] - s; return r; }
+template <class V, int N> SF_HD matn<V, N> operator-(float s, const matn<V, N>& a) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = s - a.c[j]; return r; }
+template <class V, int N> SF_HD bool operator==(const matn<V, N>& a, const matn<V, N>& b) { bool e = true; for (int j = 0; j < N; j++) e = e && (a.c[j] == b.c[j]); return e; }
+template <class V, int N> SF_HD bool operator!=(const matn<V, N>& a, const matn<V, N>& b) { return !(a == b); }
 template <class V, int N> SF_HD matn<V, N> operator-(const matn<V, N>& a) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = -a.c[j]; return r; }
 template <class V, int N> SF_HD matn<V, N> matrixCompMult(const matn<V, N>& a, const matn<V, N>& b) { matn<V, N> r; for (int j = 0; j < N; j++) r.c[j] = a.c[j]*b.c[j]; return r; }
 template <class V, int N> SF_HD matn<V, N> transpose(const matn<V, N>& a) { matn<V, N> r; for (int j = 0; j < N; j++) for (int i = 0; i < N; i++) r.c[j].d[i] = a.c[i].d[j]; return r; }
@@ -478,6 +569,7 @@ SF_HD vec3& operator*=(vec3& v, const mat3& m) { v = v*m; return v; }
 SF_HD vec4& operator*=(vec4& v, const mat4& m) { v = v*m; return v; }
 SF_HD mat2 outerProduct(const vec2& c, const vec2& r) { return mat2(c*r.x, c*r.y); }
 SF_HD mat3 outerProduct(const vec3& c, const vec3& r) { return mat3(c*r.x, c*r.y, c*r.z); }
+SF_HD mat4 outerProduct(const vec4& c, const vec4& r) { return mat4(c*r.x, c*r.y, c*r.z, c*r.w); }
 
 SF_HD float determinant(const mat2& m) { return m.c[0].x*m.c[1].y - m.c[1].x*m.c[0].y; }
 SF_HD float determinant(const mat3& m) {
