@@ -233,6 +233,25 @@ int sfx_jpeg_encode(sfx_handle encoder, const void* rgb, void* sink, int frames,
 int sfx_jpeg_header(sfx_handle encoder, void* buffer, size_t* count);
 int sfx_jpeg_coefficients(sfx_handle encoder, int16_t* out);
 
+/* Lossless PNG on the device (no reference equivalent; csrc/png_kernels.hpp defines the stream): 8-bit RGB, the
+ * specification's per-row filter heuristic, one IDAT chunk and one deflate block per stripe of 8 rows, literals and distance-1 matches
+ * (what zlib's Z_RLE takes), the stripe's own Huffman codes or the fixed ones where those are not longer. An encoder belongs to one
+ * context and one picture size and is destroyed before it.
+ * capacity: the payload bytes of a sink frame, from the fixed codes' bound — no picture exceeds it (no reference equivalent).
+ * encode: `frames` RGB8 frames on the device (consecutive, width*height*3 bytes each; `bottom_up` non-zero: their rows are stored
+ * bottom-up) become sink frames on the device, 64 + capacity bytes apart, laid out as a sized ring reads them ([magic, payload bytes,
+ * status 0] then a complete PNG file); on the context's stream, three launches per batch (no reference equivalent).
+ * filtered: the last encoded frame's filtered stream, height rows of 1 + 3*width bytes; synchronous, for tests (no reference
+ * equivalent). code_lengths: the code-length step on a histogram of the caller's (286 literal/length counts, then 30 distance
+ * counts, 2^28 - 1 in all at the most) → the dynamic code's 316 lengths and whether such a block would take the fixed codes;
+ * synchronous, for tests (no reference equivalent). */
+int sfx_png_create(sfx_handle ctx, int width, int height, sfx_handle* encoder);
+int sfx_png_destroy(sfx_handle encoder);
+int sfx_png_encode(sfx_handle encoder, const void* rgb, void* sink, int frames, int bottom_up);
+int sfx_png_capacity(int width, int height, size_t* bytes);
+int sfx_png_filtered(sfx_handle encoder, uint8_t* out);
+int sfx_png_code_lengths(sfx_handle ctx, const uint32_t* histogram, uint8_t* lengths, int* fixed);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* Cross-process frame queue of a sharded export (one process per GPU; no reference equivalent). The sink takes
  * one byte stream, so one process owns it (rank 0) — but every rank reads its finished frames out over its OWN PCIe link into a

@@ -159,6 +159,12 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_jpeg_encode": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "sfx_jpeg_header": (C.c_int, [Handle, C.c_void_p, P(C.c_size_t)]),
     "sfx_jpeg_coefficients": (C.c_int, [Handle, P(C.c_int16)]),
+    "sfx_png_create": (C.c_int, [Handle, C.c_int, C.c_int, P(Handle)]),
+    "sfx_png_destroy": (C.c_int, [Handle]),
+    "sfx_png_encode": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "sfx_png_capacity": (C.c_int, [C.c_int, C.c_int, P(C.c_size_t)]),
+    "sfx_png_filtered": (C.c_int, [Handle, P(C.c_uint8)]),
+    "sfx_png_code_lengths": (C.c_int, [Handle, P(C.c_uint32), P(C.c_uint8), P(C.c_int)]),
     "sfx_rgb_to_yuv420": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sfx_peer_export": (C.c_int, [Handle, C.c_void_p, C.c_void_p]),
     "sfx_peer_open": (C.c_int, [Handle, C.c_void_p, P(C.c_void_p)]),
@@ -397,6 +403,47 @@ class JpegEncoder:
     def destroy(self) -> None:
         if self.handle.value:
             lib().sfx_jpeg_destroy(self.handle)
+            self.handle = Handle()
+
+
+class PngEncoder:
+    """PNG encoder of one context and one picture size (sfx_png_*): RGB8 frames on the device → sink frames on the device, each a complete PNG file"""
+    SINK_HEADER = 64
+
+    def __init__(self, context: Context, width: int, height: int):
+        self.context, self.width, self.height = context, width, height
+        self.sink_bytes = self.SINK_HEADER + self.capacity(width, height)
+        self.handle = Handle()
+        check(lib().sfx_png_create(context.handle, width, height, C.byref(self.handle)))
+
+    @staticmethod
+    def capacity(width: int, height: int) -> int:
+        """Payload bytes of a sink frame: no picture of this size encodes to more (sfx_png_capacity)"""
+        count = C.c_size_t()
+        check(lib().sfx_png_capacity(width, height, C.byref(count)))
+        return count.value
+
+    def encode(self, rgb: int, sink: int, frames: int = 1, bottom_up: bool = False) -> None:
+        check(lib().sfx_png_encode(self.handle, C.c_void_p(rgb), C.c_void_p(sink), frames, 1 if bottom_up else 0))
+
+    def filtered(self) -> np.ndarray:
+        out = np.empty((self.height, 1 + 3*self.width), np.uint8)
+        check(lib().sfx_png_filtered(self.handle, as_ptr(out, C.c_uint8)))
+        return out
+
+    @staticmethod
+    def code_lengths(context: Context, histogram) -> tuple[np.ndarray, bool]:
+        """The code-length step on a 316-entry histogram → (the dynamic code's 316 lengths, whether the block takes the fixed codes)"""
+        counts = np.ascontiguousarray(histogram, np.uint32)
+        if counts.shape != (316,):
+            raise ValueError(f"a histogram has 286 + 30 counts, not {counts.shape}")
+        lengths, fixed = np.empty(316, np.uint8), C.c_int()
+        check(lib().sfx_png_code_lengths(context.handle, as_ptr(counts, C.c_uint32), as_ptr(lengths, C.c_uint8), C.byref(fixed)))
+        return lengths, bool(fixed.value)
+
+    def destroy(self) -> None:
+        if self.handle.value:
+            lib().sfx_png_destroy(self.handle)
             self.handle = Handle()
 
 

@@ -221,7 +221,7 @@ class ClockLoop:
         progress relay (a relay wants a python call per frame), every program compiled. SHADERFLOW_CLOCK_SEQUENCE=0 keeps the python loop
         (A/B measurements, and the byte-equality test of the two)."""
         import os
-        if os.environ.get("SHADERFLOW_CLOCK_SEQUENCE", "1") == "0" or not turbo or export.relay is not None or export.mjpeg:
+        if os.environ.get("SHADERFLOW_CLOCK_SEQUENCE", "1") == "0" or not turbo or export.relay is not None or export.sized:
             return False
         return all(program.program is not None for program in self.programs)
 

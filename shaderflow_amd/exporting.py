@@ -50,7 +50,7 @@ class ExportingHelper:
     took: Optional[float] = None
 
     # sink
-    kind: Optional[str] = None            # "path-raw", "path-ffmpeg", "path-mjpeg", "pipe"
+    kind: Optional[str] = None            # "path-raw", "path-ffmpeg", "path-mjpeg" (a file of sized frames: mjpeg or png), "pipe"
     path: Optional[Path] = None
     process: Optional[subprocess.Popen] = None
     file: Any = None
@@ -65,12 +65,12 @@ class ExportingHelper:
     jpeg_quality: int = 90
     """`pixel_format="mjpeg"`: baseline JPEG frames encoded on the device (csrc/jpeg_kernels.hpp; mjpeg.py has the containers). The sink
     frames are of fixed capacity on the device and say how long they are; a sized ring reads out exactly their payload. No ffmpeg process."""
-    container: Optional[str] = None       # of an mjpeg export to a path: "avi" or "raw" (mjpeg.container_of)
-    _encoder: Optional[N.JpegEncoder] = None
+    container: Optional[str] = None       # of an mjpeg or png export to a path: "avi" or "raw" (mjpeg.container_of)
+    _encoder: Any = None                  # N.JpegEncoder or N.PngEncoder
     _avi: Optional[mjpeg.AviWriter] = None
-    _sizes: list = Factory(list)          # payload sizes of the mjpeg frames written, in order (the AVI index)
+    _sizes: list = Factory(list)          # payload sizes of the mjpeg or png frames written, in order (the AVI index)
     sound_track: Any = False
-    """An mjpeg export to `.avi` carries the scene's sound (mjpeg.py states the stream): True — the scene's one ShaderAudio that holds a
+    """An mjpeg or png export to `.avi` carries the scene's sound (mjpeg.py states the stream): True — the scene's one ShaderAudio that holds a
     loaded clip, from `file=` or `samples=` — or that module, or its name. The ring's writer thread puts each frame's share of the PCM
     behind the frame (sfx_ring_side_track): it alone orders the bytes on the sink's descriptor, in all three loops."""
     _track: Optional[mjpeg.SoundTrack] = None
@@ -93,20 +93,36 @@ class ExportingHelper:
         return self.pixel_format == "mjpeg"
 
     @property
+    def png(self) -> bool:
+        """`pixel_format="png"`: lossless — every frame a complete PNG file encoded on the device (csrc/png_kernels.hpp) — as the `00dc`
+        chunks of an `.avi` file (fourcc `MPNG`) or back to back on a "pipe". A sink frame's capacity is the encoder's own bound
+        (sfx_png_capacity): no frame can fail to fit. No ffmpeg process."""
+        return self.pixel_format == "png"
+
+    @property
+    def sized(self) -> bool:
+        """A sized-frame format: the sink frames say how long they are, a sized ring reads out their payload (mjpeg, png)"""
+        return self.mjpeg or self.png
+
+    @property
     def staged(self) -> bool:
         """Sink frames are made from the RGB8 frames by a kernel: into a batch buffer, or a staging frame of the ring slot"""
-        return self.planar or self.mjpeg
+        return self.planar or self.sized
 
     @property
     def frame_bytes(self) -> int:
-        """Bytes of one frame as the sink receives it (mjpeg: the fixed capacity of a sink frame on the device, its 64-byte header included)"""
+        """Bytes of one frame as the sink receives it (mjpeg, png: the fixed capacity of a sink frame on the device, its 64-byte header included)"""
         pixels = self.scene.width*self.scene.height
+        if self.png:
+            return N.PngEncoder.SINK_HEADER + N.PngEncoder.capacity(self.scene.width, self.scene.height)
         if self.mjpeg:
             return N.JpegEncoder.SINK_HEADER + ((self.scene.width + 15)//16)*((self.scene.height + 15)//16)*768
         return pixels*3//2 if self.planar else pixels*3
 
     @property
-    def encoder(self) -> N.JpegEncoder:
+    def encoder(self):
+        if self._encoder is None and self.png:
+            self._encoder = N.PngEncoder(self.scene.context, self.scene.width, self.scene.height)
         if self._encoder is None:
             self._encoder = N.JpegEncoder(self.scene.context, self.scene.width, self.scene.height, self.jpeg_quality)
         return self._encoder
@@ -128,7 +144,7 @@ class ExportingHelper:
         """`frames` RGB8 frames on the device → sink frames at `target`, on the context's stream"""
         if self.planar:
             self.to_yuv(rgb, target, frames)
-        elif self.mjpeg:
+        elif self.sized:
             self.encoder.encode(rgb, target, frames, bottom_up=not self.top_down)
         else:
             self.scene.context.copy(target, rgb, frames*self.frame_bytes)
@@ -156,10 +172,12 @@ class ExportingHelper:
 
     def ffmpeg_sizes(self, width: int, height: int) -> None:
         self.ffmpeg.time = self.scene.runtime
-        if self.pixel_format not in ("rgb24", "yuv420p", "mjpeg"):
-            raise ValueError(f"pixel_format {self.pixel_format!r}: 'rgb24' (the reference's stream), 'yuv420p' (converted on the device) or 'mjpeg' (encoded on the device)")
-        if self.mjpeg:
-            mjpeg.check_quality(self.jpeg_quality)
+        if self.pixel_format not in ("rgb24", "yuv420p", "mjpeg", "png"):
+            raise ValueError(f"pixel_format {self.pixel_format!r}: 'rgb24' (the reference's stream), 'yuv420p' (converted on the device), 'mjpeg' (encoded on the device) "
+                             f"or 'png' (lossless, encoded on the device)")
+        if self.sized:
+            if self.mjpeg:
+                mjpeg.check_quality(self.jpeg_quality)
             return                                            # no encoder process: nothing to configure
         if self.planar and (self.scene.width % 2 or self.scene.height % 2):
             raise ValueError(f"yuv420p needs even extents, the scene is {self.scene.width}x{self.scene.height}")
@@ -174,11 +192,11 @@ class ExportingHelper:
     def find_track(self) -> mjpeg.SoundTrack:
         """The clip `sound_track` names, as the file will hold it; ValueError when the export cannot hold one or the scene has none"""
         from shaderflow_amd.audio import ShaderAudio
-        rule = "sound_track goes into an '.avi' file of a Motion-JPEG export (output='clip.avi', pixel_format='mjpeg')"
-        if not self.mjpeg:
+        rule = "sound_track goes into an '.avi' file of a Motion-JPEG or PNG export (output='clip.avi', pixel_format='mjpeg' or 'png')"
+        if not self.sized:
             raise ValueError(f"{rule}, not pixel_format {self.pixel_format!r}: the ffmpeg branch already attaches the audio file through ShaderAudio.ffhook")
         if self.kind == "pipe" or self.container != "avi":
-            raise ValueError(f"{rule}: {'a pipe' if self.kind == 'pipe' else repr(self.path.suffix)} delivers the bare JPEG images back to back")
+            raise ValueError(f"{rule}: {'a pipe' if self.kind == 'pipe' else repr(self.path.suffix)} delivers the bare {'PNG' if self.png else 'JPEG'} images back to back")
         loaded = [module for module in self.scene.modules if isinstance(module, ShaderAudio) and module._file_reader is not None]
         wanted = self.sound_track
         if wanted is True:
@@ -196,12 +214,12 @@ class ExportingHelper:
         return mjpeg.SoundTrack(reader.samples, reader.samplerate)
 
     def ffmpeg_output(self, output) -> None:
-        if self.mjpeg:
+        if self.sized:
             if (output in ("pipe", "-", bytes)):
                 self.kind = "pipe"
             else:
                 self.path = Path(output).expanduser().absolute()
-                self.container = mjpeg.container_of(self.path.suffix)
+                self.container = mjpeg.container_of(self.path.suffix, self.pixel_format)
                 self.kind = "path-mjpeg"
             if self.wants_track:
                 self._track = self.find_track()
@@ -254,7 +272,8 @@ class ExportingHelper:
             self.file = open(self.path, "wb", buffering=0)
             self.fileno = self.file.fileno()
             if self.container == "avi":
-                self._avi = mjpeg.AviWriter(self.fileno, self.scene.width, self.scene.height, self.scene.fps, track=self._track)
+                self._avi = mjpeg.AviWriter(self.fileno, self.scene.width, self.scene.height, self.scene.fps, track=self._track,
+                                            fourcc=b"MPNG" if self.png else b"MJPG")
                 self._avi.begin()
         elif self.kind == "pipe":
             self.file = tempfile.TemporaryFile(mode="w+b")
@@ -265,7 +284,7 @@ class ExportingHelper:
     def make_buffers(self, n: int = 2) -> None:
         self.release_buffers()
         handle = N.Handle()
-        if self.mjpeg:
+        if self.sized:
             N.check(N.lib().sfx_ring_create_sized(self.scene.context.handle, self.frame_bytes, max(1, n), 1 if self.container == "avi" else 0, C.byref(handle)))
         else:
             N.check(N.lib().sfx_ring_create(self.scene.context.handle, self.frame_bytes, max(1, n), C.byref(handle)))
@@ -283,7 +302,7 @@ class ExportingHelper:
                 self.check(N.lib().sfx_ring_pipe_sync(self.ring, -1))
         finally:
             if self.ring is not None and self.ring.value:
-                if self.mjpeg:
+                if self.sized:
                     N.lib().sfx_ring_pipe_sync(self.ring, -1)
                     count = C.c_size_t()
                     N.check(N.lib().sfx_ring_sizes(self.ring, None, 0, C.byref(count)))
@@ -422,7 +441,7 @@ class ExportingHelper:
 
 class SinkBatches:
     """`count` device buffers of `batch` sink frames, and the rule that fills them: a batch is rendered straight into place as rgb24, or
-    into one RGB8 scratch of a batch and converted right behind as yuv420p or mjpeg — both on the context's stream, so one scratch serves every
+    into one RGB8 scratch of a batch and converted right behind as yuv420p, mjpeg or png — both on the context's stream, so one scratch serves every
     buffer (allocated by the first batch rendered through it)."""
 
     def __init__(self, export: ExportingHelper, batch: int, count: int = 2):

@@ -4,8 +4,9 @@ Containers of a Motion-JPEG export (`scene.main(output="clip.avi", pixel_format=
 images back to back (`.mjpeg`, `.mjpg`, "pipe"), or as the `00dc` chunks of a RIFF AVI 1.0 file (`.avi`). `AviWriter` is the rest of
 that file: the headers in front of the chunks, written with placeholders, and behind them the `idx1` index and the patched sizes.
 
-One `vids` stream, fourcc `MJPG`. AVI 1.0 holds 4 GiB: an export that would pass it is closed, valid, at the last frame that fits and
-raises (OpenDML is not written; `.mjpeg` has no such limit).
+One `vids` stream, fourcc `MJPG` — or `MPNG` (`pixel_format="png"`: every `00dc` chunk a complete PNG file made by csrc/png_kernels.hpp; the
+same file otherwise, sound track included; ffmpeg and VLC map that fourcc to their PNG decoders). AVI 1.0 holds 4 GiB: an export that
+would pass it is closed, valid, at the last frame that fits and raises (OpenDML is not written; `.mjpeg` has no such limit).
 
 With a `SoundTrack` (`scene.main(..., sound_track=True)`) the file has a second stream, `auds`, and this is its definition:
 
@@ -34,11 +35,13 @@ SUFFIXES_RAW = (".mjpeg", ".mjpg")
 RIFF_LIMIT = (1 << 32) - 1
 
 
-def container_of(suffix: str) -> str:
-    """"avi" or "raw" by the output's suffix; anything else cannot hold an mjpeg export"""
+def container_of(suffix: str, pixel_format: str = "mjpeg") -> str:
+    """"avi" or "raw" by the output's suffix; anything else cannot hold an mjpeg export. A png export has the one container"""
     suffix = suffix.lower()
     if suffix in SUFFIXES_AVI:
         return "avi"
+    if pixel_format == "png":
+        raise ValueError(f"pixel_format 'png' writes '.avi' (RIFF AVI, fourcc MPNG: every frame a PNG file) or \"pipe\" (the PNG files back to back), not {suffix!r}")
     if suffix in SUFFIXES_RAW:
         return "raw"
     raise ValueError(f"pixel_format 'mjpeg' writes '.avi' (RIFF AVI, fourcc MJPG) or '.mjpeg' / '.mjpg' (the JPEG images back to back), not {suffix!r}")
@@ -105,8 +108,10 @@ class AviWriter:
     writer, or `add()`); `finish(sizes)` appends `idx1` and patches the frame count and the sizes. With a `track`, the `01wb` chunk of
     frame k follows its `00dc` chunk (the ring's writer has the schedule as a table: SoundTrack.ends)."""
 
-    def __init__(self, fileno: int, width: int, height: int, fps: float, limit: int = RIFF_LIMIT, track: Optional[SoundTrack] = None):
+    def __init__(self, fileno: int, width: int, height: int, fps: float, limit: int = RIFF_LIMIT, track: Optional[SoundTrack] = None,
+                 fourcc: bytes = b"MJPG", bit_count: int = 24):
         self.fileno, self.width, self.height, self.limit, self.track = fileno, width, height, limit, track
+        self.fourcc, self.bit_count = fourcc, bit_count                # of the video stream: strh's handler, strf's biCompression / biBitCount
         rate = fps_fraction(fps)
         self.rate, self.scale = rate.numerator, rate.denominator
         self.sizes: list[int] = []
@@ -121,9 +126,9 @@ class AviWriter:
         pixels, track = self.width*self.height*3, self.track
         avih = struct.pack("<14I", round(1e6*self.scale/self.rate), 0, 0, 0x110 if track else 0x10, frames, 0, 2 if track else 1, largest,
                            self.width, self.height, 0, 0, 0, 0)
-        strh = struct.pack("<4s4sIHHIIIIIIII4H", b"vids", b"MJPG", 0, 0, 0, 0, self.scale, self.rate, 0, frames, largest, 0xffffffff, 0,
+        strh = struct.pack("<4s4sIHHIIIIIIII4H", b"vids", self.fourcc, 0, 0, 0, 0, self.scale, self.rate, 0, frames, largest, 0xffffffff, 0,
                            0, 0, self.width, self.height)
-        strf = struct.pack("<IiiHH4sIiiII", 40, self.width, self.height, 1, 24, b"MJPG", pixels, 0, 0, 0, 0)
+        strf = struct.pack("<IiiHH4sIiiII", 40, self.width, self.height, 1, self.bit_count, self.fourcc, pixels, 0, 0, 0, 0)
         strl = b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + struct.pack("<I", len(strf)) + strf
         streams = b"LIST" + struct.pack("<I", len(strl)) + strl
         if track:
@@ -169,4 +174,5 @@ class AviWriter:
         riff = self.start - 8 + chunks + 8 + len(index)
         os.pwrite(self.fileno, self.headers(fit, 4 + chunks, riff, max(sizes[:fit], default=0), max(audio[:fit], default=0)), 0)
         if fit < len(sizes):
-            raise RuntimeError(f"an AVI 1.0 file holds 4 GiB: closed at frame {fit} of {len(sizes)}; write '.mjpeg' (no container, no limit) for the whole export")
+            advice = "write '.mjpeg' (no container, no limit)" if self.fourcc == b"MJPG" else "take \"pipe\" (the frames back to back, no limit) or shorter clips"
+            raise RuntimeError(f"an AVI 1.0 file holds 4 GiB: closed at frame {fit} of {len(sizes)}; {advice} for the whole export")

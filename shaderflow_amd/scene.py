@@ -326,8 +326,9 @@ class ShaderScene(ShaderModule):
         `shard`: (rank, world) to run ONE rank's share of a sharded frame-loop export without a process group (tests,
         external launchers); with torch.distributed initialised the group's rank and size are used.
         `pixel_format`: "rgb24" (default: the reference's stream) or "yuv420p" — converted on the device (ExportingHelper.pixel_format) — or "mjpeg": baseline
-        JPEG frames encoded on the device at `jpeg_quality` (1…100) into `.avi`, `.mjpeg` or "pipe", no ffmpeg (ExportingHelper.jpeg_quality).
-        `sound_track`: an mjpeg export to `.avi` carries the scene's sound as a PCM stream — True (the scene's one ShaderAudio with a loaded clip), that
+        JPEG frames encoded on the device at `jpeg_quality` (1…100) into `.avi`, `.mjpeg` or "pipe", no ffmpeg (ExportingHelper.jpeg_quality) — or "png":
+        lossless, every frame a complete PNG file encoded on the device, into `.avi` (fourcc MPNG) or "pipe", no ffmpeg (ExportingHelper.png).
+        `sound_track`: an mjpeg or png export to `.avi` carries the scene's sound as a PCM stream — True (the scene's one ShaderAudio with a loaded clip), that
         module, or its name (ExportingHelper.sound_track; mjpeg.py states the stream)."""
         self.initialize()
         self.exporting = (bool(output))
@@ -365,8 +366,8 @@ class ShaderScene(ShaderModule):
                                  jpeg_quality=jpeg_quality, sound_track=sound_track)
         if export.wants_track and not self.exporting:
             raise ValueError("sound_track goes into an '.avi' file of a Motion-JPEG export (output='clip.avi', pixel_format='mjpeg'): there is no output")
-        if self.exporting and export.mjpeg and (is_sharded() or shard is not None):
-            raise ValueError("pixel_format 'mjpeg' is not sharded: frames of their own length have no place in the ranks' fixed-stride gather")
+        if self.exporting and export.sized and (is_sharded() or shard is not None):
+            raise ValueError(f"pixel_format {export.pixel_format!r} is not sharded: frames of their own length have no place in the ranks' fixed-stride gather")
         if (self.exporting):
             # Every rank of a sharded export resolves the sink the same way — its kind decides the row order the kernels write
             # (exporting.py:94-118) — but only rank 0 opens it and owns the read-out ring (tape.py, _sharded_frame_loop)

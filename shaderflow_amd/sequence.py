@@ -93,7 +93,7 @@ def sequence_gate(scene: "ShaderScene", export: "Optional[ExportingHelper]", tur
     other module type"""
     if not scene.freewheel or is_sharded():
         return False
-    if export is not None and export.mjpeg:                         # sfx_sequence_run's own sink knows rgb24 and yuv420p: the loop from before the sequences draws
+    if export is not None and export.sized:                         # a sized-frame format (mjpeg, png). sfx_sequence_run's own sink knows rgb24 and yuv420p: the loop from before the sequences draws
         return False
     if chunked and (not turbo or (export is not None and export.relay is not None)):
         return False
