@@ -520,6 +520,53 @@ int sfx_jpeg_decode_sync(sfx_handle ctx, const void* staged, size_t nbytes, int 
                          int subsequence_bytes, int round_budget, int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status, uint32_t* info /* [3] */);
 /* How many landed Motion-JPEG frames of the handle took the subsequence path, and how many the lane-per-interval kernel alone */
 int sfx_video_jpeg_paths(sfx_handle video, uint64_t* subsequence_frames, uint64_t* interval_frames);
+/* PNG sources: the frames of an `MPNG` AVI stream, or PNG files as bytes — what pixel_format="png" exports, read back, and the same
+ * from other writers. 8-bit RGB, no interlace. csrc/png_decode_kernels.hpp defines the decode: inflate (RFC 1951, complete), the
+ * Adler-32 over the inflated stream, and the five row filters undone into the RGB8 texture, rows flipped. The host strips the chunks
+ * (shaderflow_amd/pngsource.py) and stages the record below; chunk CRC-32s are NOT checked, the Adler-32 is, on the device.
+ * Behind the record: one word per segment — where each IDAT chunk's bytes start in the payload — padded to 16 bytes; then, at
+ * `payload_offset`, the payload: the IDAT data concatenated, without the 2-byte zlib header and the 4-byte Adler-32 trailer. */
+enum { SFX_VIDEO_PNG = 3 /* a staged PNG frame of its own length: sfx_video_create_png */ };
+enum { SFX_PNG_FRAME_MAGIC = 0x4e504653 /* "SFPN" */ };
+typedef struct sfx_png_frame {
+    uint32_t magic;                 /* SFX_PNG_FRAME_MAGIC */
+    uint32_t width, height;
+    uint32_t segments;              /* IDAT chunks; at least 1 */
+    uint32_t payload_bytes;
+    uint32_t payload_offset;        /* where the payload starts in the staged frame: 32 + the segment table, a multiple of 16 */
+    uint32_t adler;                 /* the stream's trailer, as a number */
+    uint32_t reserved;
+} sfx_png_frame;
+SFX_STATIC_ASSERT(sizeof(sfx_png_frame) == 32, "the segment table starts at byte 32");
+SFX_STATIC_ASSERT(offsetof(sfx_png_frame, segments) == 12 && offsetof(sfx_png_frame, payload_bytes) == 16 && offsetof(sfx_png_frame, payload_offset) == 20
+                  && offsetof(sfx_png_frame, adler) == 24, "the staged PNG frame's layout");
+/* bits of a PNG frame's status word (sfx_video_status, sfx_png_decode) */
+enum { SFX_PNG_BAD_BLOCK = 1,       /* block type 3 */
+       SFX_PNG_BAD_STORED = 2,      /* a stored block whose LEN and NLEN do not match */
+       SFX_PNG_BAD_LENGTHS = 4,     /* a bad code-length set: over-subscribed, too many symbols, a repeat without or past its place, no end-of-block code */
+       SFX_PNG_BAD_CODE = 8,        /* a code that matches none, or a length or distance symbol the format reserves */
+       SFX_PNG_BAD_DISTANCE = 16,   /* a distance in front of the stream's first byte */
+       SFX_PNG_OUT_OF_BITS = 32,    /* the payload ran out of bits */
+       SFX_PNG_BAD_SIZE = 64,       /* the stream does not inflate to height x (1 + 3 width) bytes */
+       SFX_PNG_BAD_FILTER = 128,    /* a row's filter type above 4 */
+       SFX_PNG_BAD_ADLER = 256,     /* the Adler-32 of the inflated stream is not the trailer's (or bytes stand between the last block and the trailer) */
+       SFX_PNG_BAD_DESCRIPTOR = 512 /* a staged frame the kernels refuse */ };
+/* sfx_video_create_mjpeg's counterpart: slots of `capacity` bytes, the frame's inflated stream as scratch. sfx_video_submit_bytes
+ * validates a staged frame's words (the magic, the segment table inside the frame and ascending, the payload inside the frame, the
+ * geometry against the handle's); sfx_video_step and a landing frame of sfx_sequence_run launch the PNG kernels; sfx_video_status
+ * answers with SFX_PNG_* bits. sfx_video_create itself keeps refusing format 3. */
+int sfx_video_create_png(sfx_handle ctx, const sfx_handle* boxes, int temporal, int width, int height, size_t capacity, int slots, sfx_handle* video);
+/* How many landed PNG frames took the segment path (a wave per IDAT chunk, every chunk validated), and how many the serial path
+ * (chosen up front, or fallen back to) */
+int sfx_video_png_paths(sfx_handle video, uint64_t* segment_frames, uint64_t* serial_frames);
+/* Test entry: one staged frame from host memory through the PNG kernels. `mode` 0: the serial path; 1: the segment path (with the
+ * serial path behind it when a segment does not validate); -1: what a video handle would choose (at least two segments, every one but
+ * the last ending in 00 00 FF FF; SHADERFLOW_PNG_SEGMENTS=0 / 1 force either). Any output may be null: `filtered_out` height x
+ * (1 + 3 width) bytes, the inflated stream; `rgb_out` height x width x 3, top row first (zeros when the status is not 0: such a frame is not drawn). 64 guard bytes
+ * behind either on the device are checked afterwards: SFX_E_HIP when a kernel wrote there.
+ * `info`: {segments, 1 when the segment path decoded the frame, 1 when it fell back to the serial path}. Synchronous. */
+int sfx_png_decode(sfx_handle ctx, const void* staged, size_t nbytes, int width, int height, int mode, uint8_t* filtered_out, uint8_t* rgb_out,
+                   uint32_t* status, uint32_t* info /* [3] */);
 /* video.py:57-66 has no counterpart: stops the copy stream, then frees the staging */
 int sfx_video_destroy(sfx_handle video);
 

@@ -67,7 +67,7 @@ class ClockTick(C.Structure):
 
 
 PASS_LAYERS, PASS_FUSED, PASS_RESOLVE = 0, 1, 2
-VIDEO_RGB24, VIDEO_I420, VIDEO_MJPEG = 0, 1, 2
+VIDEO_RGB24, VIDEO_I420, VIDEO_MJPEG, VIDEO_PNG = 0, 1, 2, 3
 
 
 class PianoParams(C.Structure):
@@ -225,6 +225,9 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_jpeg_decode_sync": (C.c_int, [Handle, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        P(C.c_uint32), P(C.c_uint32)]),
     "sfx_video_jpeg_paths": (C.c_int, [Handle, P(C.c_uint64), P(C.c_uint64)]),
+    "sfx_video_create_png": (C.c_int, [Handle, P(Handle), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, P(Handle)]),
+    "sfx_video_png_paths": (C.c_int, [Handle, P(C.c_uint64), P(C.c_uint64)]),
+    "sfx_png_decode": (C.c_int, [Handle, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
     "sfx_sequence_run": (C.c_int, [Handle, P(Sequence)]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),
     "sfx_device_free": (C.c_int, [Handle, C.c_void_p]),

@@ -13,6 +13,7 @@
 #include "host_state.hpp"
 #include "video_kernels.hpp"
 #include "jpeg_decode_kernels.hpp"
+#include "png_decode_kernels.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -43,6 +44,11 @@ struct Video : Object {
     float* basis = nullptr; uint32_t* status = nullptr; int16_t* coefficients = nullptr; uint8_t* planes = nullptr;
     uint32_t* first_bad = nullptr;          // pinned: {status, serial} of the first landed frame with a bad status since sfx_video_status last asked
     uint32_t serial = 0;                    // frames landed so far
+    // SFX_VIDEO_PNG: staged frames as above; `scratch` is [status: a word per slot][control][segment records][the inflated stream]
+    PngScratch png{};
+    std::vector<uint32_t> staged_bytes, segments;    // of the frame each slot holds
+    std::vector<uint8_t> segment_path;               // whether that frame takes the segment path (png_segments_chosen, at submit)
+    uint64_t png_serial_frames = 0;                  // landed frames that took the serial path up front (the others count themselves: first_bad[4], [5])
 };
 enum { SLOT_NEW = 0, SLOT_SUBMITTED = 1, SLOT_CONSUMED = 2 };
 
@@ -128,11 +134,94 @@ static bool jpeg_sync_chosen(uint32_t scan_bytes, uint32_t intervals, uint32_t s
     return intervals > 0 && scan_bytes/intervals >= (unsigned long long)JPEG_SYNC_RULE*subsequence;
 }
 
+// ---- PNG (png_decode_kernels.hpp) ------------------------------------------------------------------------------------------------------
+
+static int png_geometry(int width, int height, size_t capacity) {
+    if (width < 1 || height < 1 || (unsigned long long)height*(1ull + 3ull*(unsigned long long)width) > PNG_MAX_OUTPUT)
+        return fail(SFX_E_INVALID, "png decode: %d x %d (extents from 1, height x (1 + 3 width) below 2^31)", width, height);
+    if (capacity < (size_t)PNG_FRAME_FIXED + 16 || capacity > ((size_t)1 << 30)) return fail(SFX_E_INVALID, "png decode: a staged frame of at most %zu bytes (%d … 2^30)", capacity, PNG_FRAME_FIXED + 16);
+    return SFX_OK;
+}
+
+// [status words][control: 64 bytes][records: one per segment a staged frame of `capacity` bytes can name, 65 536 at the most][the inflated stream + 64], each part 256-byte aligned
+static int png_scratch(int width, int height, size_t capacity, int slots, void** block, uint32_t** status, PngScratch* out) {
+    const size_t expected = (size_t)height*(1 + 3*(size_t)width), status_bytes = ((size_t)slots*4 + 255) & ~(size_t)255;
+    const size_t records = std::min(capacity/4 + 1, (size_t)65536), record_bytes = (records*sizeof(PngSegmentRecord) + 255) & ~(size_t)255;
+    const size_t total = status_bytes + 256 + record_bytes + expected + 64;
+    if (hipMalloc(block, total) != hipSuccess) { (void)hipGetLastError(); *block = nullptr; return SFX_E_HIP; }
+    if (hipMemset(*block, 0, total) != hipSuccess) { (void)hipGetLastError(); hipFree(*block); *block = nullptr; return SFX_E_HIP; }
+    char* base = (char*)*block;
+    *status = (uint32_t*)base;
+    out->control = (uint32_t*)(base + status_bytes); out->records = (PngSegmentRecord*)(base + status_bytes + 256); out->capacity = (uint32_t)records;
+    out->filtered = (uint8_t*)(base + status_bytes + 256 + record_bytes);
+    return SFX_OK;
+}
+
+// why a staged PNG frame of `nbytes` bytes is not one the kernels may be given (null: it is)
+static const char* png_frame_fault(const void* frame, size_t nbytes, int width, int height, size_t capacity, sfx_png_frame* out) {
+    if (nbytes < sizeof(sfx_png_frame) || nbytes > capacity) return "its length is outside the record … the slot's capacity";
+    sfx_png_frame f;
+    memcpy(&f, frame, sizeof f);
+    if (f.magic != SFX_PNG_FRAME_MAGIC) return "no SFPN magic";
+    if (f.width != (uint32_t)width || f.height != (uint32_t)height) return "another width or height than the video's";
+    if (f.segments < 1 || f.payload_offset < sizeof f || (f.payload_offset & 15u) || f.payload_offset > nbytes || f.segments > (f.payload_offset - sizeof f)/4)
+        return "the segment table does not lie behind the record and in front of the payload";
+    if (f.payload_bytes > nbytes - f.payload_offset) return "the payload does not lie inside the frame";
+    uint32_t before = 0;
+    for (uint32_t k = 0; k < f.segments; k++) {
+        uint32_t start;
+        memcpy(&start, (const char*)frame + sizeof f + 4*(size_t)k, 4);
+        if ((k == 0 && start != 0) || start < before || start > f.payload_bytes) return "the segment table does not ascend from 0 inside the payload";
+        before = start;
+    }
+    *out = f;
+    return nullptr;
+}
+
+// Which path a frame takes: SHADERFLOW_PNG_SEGMENTS=0 / 1 force the serial / the segment path; else the segment path when the frame
+// has at least two segments and every one but the last ends in 00 00 FF FF (an empty stored block: a flush point). The segment path
+// needs a record per segment. (Read per frame: tests switch it.)
+static bool png_segments_chosen(const void* frame, const sfx_png_frame& f, uint32_t records, int mode = -1) {
+    if (f.segments > records) return false;
+    const char* forced = getenv("SHADERFLOW_PNG_SEGMENTS");
+    if (mode < 0 && forced && !forced[1] && (forced[0] == '0' || forced[0] == '1')) mode = forced[0] - '0';
+    if (mode >= 0) return mode == 1;
+    if (f.segments < 2) return false;
+    const uint8_t* payload = (const uint8_t*)frame + f.payload_offset;
+    static const uint8_t flush[4] = {0x00, 0x00, 0xff, 0xff};
+    for (uint32_t k = 1; k < f.segments; k++) {
+        uint32_t end;
+        memcpy(&end, (const char*)frame + sizeof f + 4*(size_t)k, 4);
+        if (end < 4 || memcmp(payload + end - 4, flush, 4)) return false;
+    }
+    return true;
+}
+
+// The decode launches of one staged frame of `nbytes` bytes on `stream` → `rgb`. `status`: the frame's word, cleared in front of them.
+// The launch sizes follow from the words sfx_video_submit_bytes validated; the launches run in stream order, so one frame's scratch serves every frame.
+static void png_launch_decode(hipStream_t stream, const uint8_t* frame, uint32_t nbytes, uint32_t segments, bool segment_path, const PngScratch& scratch, uint32_t* status,
+                              uint32_t* first_bad, uint32_t serial, uint8_t* rgb, int width, int height, int bottom_up) {
+    const uint32_t expected = (uint32_t)height*(1u + 3u*(uint32_t)width);
+    hipMemsetAsync(status, 0, sizeof(uint32_t), stream);
+    hipMemsetAsync(scratch.control, 0, 64, stream);
+    if (segment_path) {
+        hipLaunchKernelGGL(k_png_inflate_count, dim3(segments), dim3(64), 0, stream, frame, scratch, width, height, nbytes, expected);
+        hipLaunchKernelGGL(k_png_inflate_scan, dim3(1), dim3(64), 0, stream, scratch, segments, expected, (volatile uint32_t*)(first_bad ? first_bad + 4 : nullptr));
+        hipLaunchKernelGGL(k_png_inflate_write, dim3(segments), dim3(64), 0, stream, frame, scratch);
+    }
+    hipLaunchKernelGGL(k_png_inflate_serial, dim3(1), dim3(64), 0, stream, frame, scratch, status, width, height, nbytes, expected);
+    const unsigned pieces = PNG_ADLER_THREADS*PNG_ADLER_PIECES*16;
+    hipLaunchKernelGGL(k_png_adler, dim3((expected + pieces - 1)/pieces), dim3(PNG_ADLER_THREADS), 0, stream, scratch, (const uint32_t*)status, expected);
+    hipLaunchKernelGGL(k_png_check, dim3(1), dim3(256), 0, stream, frame, scratch, status, (volatile uint32_t*)first_bad, serial, width, height, expected);
+    hipLaunchKernelGGL(k_png_unfilter, dim3(1), dim3(PNG_UNFILTER_WAVES*64), 0, stream, (const uint8_t*)scratch.filtered, rgb, (const uint32_t*)status, width, height, bottom_up);
+}
+
 // The handle of either entry below: `slots` pinned frames of `frame_bytes` bytes, their device staging, an event each and the copy
 // stream. `jpeg` (SFX_VIDEO_MJPEG): the staging is one block and the decoder's scratch comes with it. Else every staging frame is an
 // allocation of its own with 16 bytes behind it: k_video_frame's 16-byte loads may reach past a frame's last row (video_kernels.hpp).
 static int video_create(Context* c, const sfx_handle* boxes, int temporal, int width, int height, int format, size_t frame_bytes, int slots,
                         const JpegDecodeGeometry* jpeg, sfx_handle* out) {
+    const bool png = format == SFX_VIDEO_PNG, staged = jpeg || png;
     if (!boxes || !out || temporal < 1 || width < 1 || height < 1 || slots < 1 || slots > 256)
         return fail(SFX_E_INVALID, "video: null boxes or output, or %d x %d, temporal %d, %d slots (1…256)", width, height, temporal, slots);
     USE_DEVICE(c);
@@ -144,20 +233,22 @@ static int video_create(Context* c, const sfx_handle* boxes, int temporal, int w
     for (int d = 0; d < temporal; d++)
         if (!video_texture(v->boxes[d], v)) { delete v; return fail(SFX_E_INVALID, "video: box %d is not a %d x %d RGB8 texture of this context (layers must be 1)", d, width, height); }
     v->host.assign(slots, nullptr); v->staging.assign(slots, nullptr); v->events.assign(slots, nullptr); v->state.assign(slots, SLOT_NEW); v->intervals.assign(slots, 0); v->scan_bytes.assign(slots, 0);
+    v->staged_bytes.assign(slots, 0); v->segments.assign(slots, 0); v->segment_path.assign(slots, 0);
     bool ok = hipStreamCreateWithFlags(&v->copy, hipStreamNonBlocking) == hipSuccess;
+    if (ok && staged) ok = hipMalloc(&v->staging_block, frame_bytes*slots) == hipSuccess && hipHostMalloc((void**)&v->first_bad, 64, hipHostMallocDefault) == hipSuccess;
+    if (ok && png) ok = png_scratch(width, height, frame_bytes, slots, &v->scratch, &v->status, &v->png) == SFX_OK;
     if (ok && jpeg)
-        ok = hipMalloc(&v->staging_block, frame_bytes*slots) == hipSuccess && hipHostMalloc((void**)&v->first_bad, 64, hipHostMallocDefault) == hipSuccess
-             && jpeg_scratch(*jpeg, slots, &v->scratch, &v->basis, &v->status, &v->coefficients, &v->planes) == SFX_OK
+        ok = jpeg_scratch(*jpeg, slots, &v->scratch, &v->basis, &v->status, &v->coefficients, &v->planes) == SFX_OK
              && jpeg_sync_scratch(*jpeg, frame_bytes, v->sync_bytes, &v->sync_block, &v->sync) == SFX_OK;
     for (int k = 0; ok && k < slots; k++) {
-        if (jpeg) v->staging[k] = (char*)v->staging_block + (size_t)k*frame_bytes;
+        if (staged) v->staging[k] = (char*)v->staging_block + (size_t)k*frame_bytes;
         else ok = hipMalloc(&v->staging[k], frame_bytes + 16) == hipSuccess;
         ok = ok && hipHostMalloc(&v->host[k], frame_bytes, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&v->events[k], hipEventDisableTiming) == hipSuccess;
     }
     if (!ok) {
         (void)hipGetLastError();
         video_release(v);
-        return fail(SFX_E_HIP, "video: %d staging frames of %zu bytes (pinned and device)%s could not be allocated", slots, frame_bytes, jpeg ? " and the decoder's scratch" : "");
+        return fail(SFX_E_HIP, "video: %d staging frames of %zu bytes (pinned and device)%s could not be allocated", slots, frame_bytes, staged ? " and the decoder's scratch" : "");
     }
     if (v->first_bad) memset(v->first_bad, 0, 64);
     *out = handle_of(v);
@@ -177,6 +268,12 @@ extern "C" int sfx_video_create_mjpeg(sfx_handle hc, const sfx_handle* boxes, in
     JpegDecodeGeometry g;
     if (const int rc = jpeg_decode_geometry(width, height, components, h_sampling, v_sampling, capacity, &g)) return rc;
     return video_create(c, boxes, temporal, width, height, SFX_VIDEO_MJPEG, (size_t)g.capacity, slots, &g, out);
+}
+
+extern "C" int sfx_video_create_png(sfx_handle hc, const sfx_handle* boxes, int temporal, int width, int height, size_t capacity, int slots, sfx_handle* out) {
+    CTX_OR_FAIL(c, hc);
+    if (const int rc = png_geometry(width, height, capacity)) return rc;
+    return video_create(c, boxes, temporal, width, height, SFX_VIDEO_PNG, (capacity + 15) & ~(size_t)15, slots, nullptr, out);
 }
 
 extern "C" int sfx_video_slot(sfx_handle h, int slot, void** host, size_t* nbytes) {
@@ -219,7 +316,13 @@ static const char* jpeg_frame_fault(const void* frame, size_t nbytes, const Jpeg
 static int video_submit(Video* v, int slot, size_t nbytes, bool staged = false) {
     std::lock_guard<std::mutex> lock(v->guard);
     if (v->state[slot] == SLOT_SUBMITTED) return fail(SFX_E_INVALID, "video: slot %d holds a submitted frame that was not consumed yet", slot);
-    if (staged) {
+    if (staged && v->format == SFX_VIDEO_PNG) {
+        sfx_png_frame f;
+        if (const char* fault = png_frame_fault(v->host[slot], nbytes, v->width, v->height, v->frame_bytes, &f)) return fail(SFX_E_INVALID, "video: the staged PNG frame of %zu bytes in slot %d: %s", nbytes, slot, fault);
+        v->staged_bytes[slot] = (uint32_t)nbytes; v->segments[slot] = f.segments;
+        v->segment_path[slot] = png_segments_chosen(v->host[slot], f, v->png.capacity) ? 1 : 0;
+        nbytes = (nbytes + 15) & ~(size_t)15;
+    } else if (staged) {
         if (const char* fault = jpeg_frame_fault(v->host[slot], nbytes, v->jpeg, &v->intervals[slot], &v->scan_bytes[slot])) return fail(SFX_E_INVALID, "video: the staged Motion-JPEG frame of %zu bytes in slot %d: %s", nbytes, slot, fault);
         nbytes = (nbytes + 15) & ~(size_t)15;
     }
@@ -234,14 +337,14 @@ static int video_submit(Video* v, int slot, size_t nbytes, bool staged = false) 
 extern "C" int sfx_video_submit(sfx_handle h, int slot) {
     Video* v = get<Video>(h, MAGIC_VIDEO);
     if (!v || slot < 0 || slot >= v->slots) return fail(SFX_E_INVALID, "invalid video handle or slot %d", slot);
-    if (v->format == SFX_VIDEO_MJPEG) return fail(SFX_E_INVALID, "video: a Motion-JPEG frame has a length of its own: sfx_video_submit_bytes");
+    if (v->format == SFX_VIDEO_MJPEG || v->format == SFX_VIDEO_PNG) return fail(SFX_E_INVALID, "video: a Motion-JPEG or PNG frame has a length of its own: sfx_video_submit_bytes");
     return video_submit(v, slot, v->frame_bytes);
 }
 
 extern "C" int sfx_video_submit_bytes(sfx_handle h, int slot, size_t nbytes) {
     Video* v = get<Video>(h, MAGIC_VIDEO);
     if (!v || slot < 0 || slot >= v->slots) return fail(SFX_E_INVALID, "invalid video handle or slot %d", slot);
-    if (v->format != SFX_VIDEO_MJPEG) {
+    if (v->format != SFX_VIDEO_MJPEG && v->format != SFX_VIDEO_PNG) {
         if (nbytes != v->frame_bytes) return fail(SFX_E_INVALID, "video: a frame of this format has %zu bytes, not %zu", v->frame_bytes, nbytes);
         return video_submit(v, slot, nbytes);
     }
@@ -301,6 +404,10 @@ int video_launch_frame(sfx_handle h, Context* c, int slot) {
         (sync ? v->sync_frames : v->serial_frames)++;
         jpeg_launch_decode(v->ctx->stream, (const uint8_t*)v->staging[slot], v->intervals[slot], v->scan_bytes[slot], sync ? &v->sync : nullptr, v->sync_bytes, JPEG_SYNC_ROUNDS,
                            v->coefficients, v->planes, v->basis, v->status + slot, v->first_bad, v->serial++, (uint8_t*)front->data, v->jpeg, 1);
+    } else if (v->format == SFX_VIDEO_PNG) {
+        if (!v->segment_path[slot]) v->png_serial_frames++;
+        png_launch_decode(v->ctx->stream, (const uint8_t*)v->staging[slot], v->staged_bytes[slot], v->segments[slot], v->segment_path[slot] != 0, v->png, v->status + slot,
+                          v->first_bad, v->serial++, (uint8_t*)front->data, v->width, v->height, 1);
     } else if (v->format == SFX_VIDEO_I420) hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_I420>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     else hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_RGB24>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     const int rc = launch_status();
@@ -340,7 +447,7 @@ extern "C" int sfx_video_status(sfx_handle h, int wait, int64_t* frame, uint32_t
     Video* v = get<Video>(h, MAGIC_VIDEO);
     if (!v || !frame || !status) return fail(SFX_E_INVALID, "invalid video handle or null pointer");
     *frame = -1; *status = 0;
-    if (v->format != SFX_VIDEO_MJPEG) return SFX_OK;                  // (uncompressed frames have nothing to go wrong)
+    if (v->format != SFX_VIDEO_MJPEG && v->format != SFX_VIDEO_PNG) return SFX_OK;      // (uncompressed frames have nothing to go wrong)
     volatile uint32_t* note = v->first_bad;
     if (!wait && note[0] == 0u) return SFX_OK;
     USE_DEVICE(v->ctx);
@@ -417,4 +524,68 @@ extern "C" int sfx_jpeg_decode_sync(sfx_handle hc, const void* staged, size_t nb
                                     int subsequence_bytes, int round_budget, int16_t* coefficients, uint8_t* planes, uint8_t* rgb, uint32_t* status, uint32_t* info) {
     if (subsequence_bytes < 0) return fail(SFX_E_INVALID, "jpeg decode: subsequences of %d bytes (0: the production rule; 2 … 2^20)", subsequence_bytes);
     return jpeg_decode_once(hc, staged, nbytes, width, height, components, h_sampling, v_sampling, subsequence_bytes, round_budget, coefficients, planes, rgb, status, info);
+}
+
+// ---- PNG sources -------------------------------------------------------------------------------------------------------------------------
+
+extern "C" int sfx_video_png_paths(sfx_handle h, uint64_t* segment_frames, uint64_t* serial_frames) {
+    Video* v = get<Video>(h, MAGIC_VIDEO);
+    if (!v || !segment_frames || !serial_frames) return fail(SFX_E_INVALID, "invalid video handle or null pointer");
+    *segment_frames = *serial_frames = 0;
+    if (v->format != SFX_VIDEO_PNG) return SFX_OK;
+    USE_DEVICE(v->ctx);
+    HIP_TRY(hipStreamSynchronize(v->ctx->stream));                   // (the scan kernel of a frame says which way it went)
+    std::lock_guard<std::mutex> lock(v->guard);
+    volatile uint32_t* counted = v->first_bad + 4;
+    *segment_frames = counted[0]; *serial_frames = v->png_serial_frames + counted[1];
+    return SFX_OK;
+}
+
+extern "C" int sfx_png_decode(sfx_handle hc, const void* staged, size_t nbytes, int width, int height, int mode, uint8_t* filtered_out, uint8_t* rgb_out,
+                              uint32_t* status, uint32_t* info) {
+    CTX_OR_FAIL(c, hc);
+    if (!staged || !status) return fail(SFX_E_INVALID, "png decode: null frame or status");
+    if (mode < -1 || mode > 1) return fail(SFX_E_INVALID, "png decode: mode %d (0: serial, 1: segments, -1: as a video handle chooses)", mode);
+    const size_t capacity = (std::max(nbytes, (size_t)PNG_FRAME_FIXED + 16) + 15) & ~(size_t)15;
+    if (const int rc = png_geometry(width, height, capacity)) return rc;
+    sfx_png_frame f;
+    if (const char* fault = png_frame_fault(staged, nbytes, width, height, capacity, &f)) return fail(SFX_E_INVALID, "png decode: the staged frame of %zu bytes: %s", nbytes, fault);
+    if (info) info[0] = info[1] = info[2] = 0u;
+    USE_DEVICE(c);
+    void *block = nullptr, *frame = nullptr, *pixels = nullptr;
+    uint32_t* device_status = nullptr;
+    PngScratch scratch{};
+    const size_t rgb_bytes = (size_t)width*height*3, filtered_bytes = (size_t)height*(1 + 3*(size_t)width);
+    int rc = png_scratch(width, height, capacity, 1, &block, &device_status, &scratch);
+    if (rc == SFX_OK && (hipMalloc(&frame, capacity) != hipSuccess || hipMalloc(&pixels, rgb_bytes + 64) != hipSuccess)) rc = SFX_E_HIP;
+    if (rc == SFX_OK) {
+        const bool segment_path = png_segments_chosen(staged, f, scratch.capacity, mode);
+        // 64 guard bytes behind the inflated stream and behind the pixels: whatever the stream says, the kernels leave them alone
+        bool ok = hipMemsetAsync(frame, 0, capacity, c->stream) == hipSuccess && hipMemsetAsync(pixels, 0, rgb_bytes, c->stream) == hipSuccess
+                  && hipMemsetAsync((char*)pixels + rgb_bytes, 0xa5, 64, c->stream) == hipSuccess && hipMemsetAsync(scratch.filtered + filtered_bytes, 0xa5, 64, c->stream) == hipSuccess
+                  && hipMemcpyAsync(frame, staged, nbytes, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+        if (ok) {
+            png_launch_decode(c->stream, (const uint8_t*)frame, (uint32_t)nbytes, f.segments, segment_path, scratch, device_status, nullptr, 0, (uint8_t*)pixels, width, height, 0);
+            ok = hipGetLastError() == hipSuccess;
+        }
+        uint32_t control[2] = {0u, 0u};
+        uint8_t guards[128];
+        if (ok) ok = hipMemcpyAsync(guards, scratch.filtered + filtered_bytes, 64, hipMemcpyDeviceToHost, c->stream) == hipSuccess
+                     && hipMemcpyAsync(guards + 64, (char*)pixels + rgb_bytes, 64, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (ok && filtered_out) ok = hipMemcpyAsync(filtered_out, scratch.filtered, filtered_bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (ok && rgb_out) ok = hipMemcpyAsync(rgb_out, pixels, rgb_bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(status, device_status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) == hipSuccess
+                     && hipMemcpyAsync(control, scratch.control, sizeof control, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        const hipError_t synced = hipStreamSynchronize(c->stream);
+        if (!ok || synced != hipSuccess) rc = fail(SFX_E_HIP, "png decode: %s", hipGetErrorString(synced != hipSuccess ? synced : hipGetLastError()));
+        else if (std::any_of(guards, guards + 128, [](uint8_t v) { return v != 0xa5; })) rc = fail(SFX_E_HIP, "png decode: the kernels wrote behind the inflated stream or behind the pixels");
+        else if (info) { info[0] = f.segments; info[1] = control[0]; info[2] = segment_path ? control[1] : 0u; }
+    } else {
+        (void)hipGetLastError();
+        fail(rc, "png decode: the scratch of a %d x %d frame could not be allocated", width, height);
+    }
+    if (block) hipFree(block);
+    if (frame) hipFree(frame);
+    if (pixels) hipFree(pixels);
+    return rc;
 }

@@ -342,7 +342,7 @@ class RawReader(MjpegClip):
 
 class AviReader(MjpegClip):
     """RIFF AVI 1.0: `hdrl` (`strl`: `strh`, `strf`) and the `movi` list's `NNdc` / `NNdb` chunks of the first `vids` stream whose
-    handler or compression is MJPG; `idx1` when it is there (and consistent), else a walk over `movi`. Audio and every other chunk are
+    handler or compression is one of `fourccs` (MJPG; pngsource.py asks for MPNG), in either case; `idx1` when it is there (and consistent), else a walk over `movi`. Audio and every other chunk are
     skipped. A chunk of this stream without bytes is a dropped frame: the picture in front of it again, so the frames behind it keep
     their times (nothing, in front of the first picture). Frames in OpenDML `AVIX` extensions are not read: a warning says so."""
 
@@ -352,7 +352,7 @@ class AviReader(MjpegClip):
         elif self.index:
             self.index.append(self.index[-1])                         # a dropped frame
 
-    def __init__(self, path: Path):
+    def __init__(self, path: Path, fourccs: tuple = (b"MJPG",)):
         super().__init__(path)
         data = self.map
         if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"AVI ":
@@ -381,7 +381,7 @@ class AviReader(MjpegClip):
                             scale, rate = struct.unpack("<II", data[leaf_at + 20:leaf_at + 28])
                         elif leaf == b"strf" and leaf_size >= 20:
                             compression = bytes(data[leaf_at + 16:leaf_at + 20])
-                    if self.stream is None and kind == b"vids" and b"MJPG" in ((handler or b"").upper(), (compression or b"").upper()):
+                    if self.stream is None and kind == b"vids" and {(handler or b"").upper(), (compression or b"").upper()} & set(fourccs):
                         self.stream = streams
                         self.fps = rate/scale if scale and rate else None
                     streams += 1
@@ -390,7 +390,8 @@ class AviReader(MjpegClip):
             elif fourcc == b"idx1":
                 idx1 = (at, size)
         if self.stream is None:
-            raise LookupError(f"{self.path}: no video stream with handler or compression MJPG")
+            self.close()                                              # (the caller may try another reader on the file)
+            raise LookupError(f"{self.path}: no video stream with handler or compression {' or '.join(name.decode() for name in fourccs)}")
         if movi is None:
             raise ValueError(f"{self.path}: no movi list")
         if not self.fps:

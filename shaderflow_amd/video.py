@@ -22,6 +22,12 @@ Where frames come from: the reference pipes the file through an `ffmpeg` subproc
     4:2:2 / 4:4:4 / grey; anything else raises ValueError naming the marker or field). With `format="mjpeg"`, `frames=` yields such
     streams as `bytes`. A frame whose entropy-coded data is damaged raises RuntimeError naming the source frame; it is not drawn. A
     stream without restart markers is cut into subsequences that decode in parallel (DESIGN.md §7c): entropy decoding on the host is out of scope;
+  * `path=` an `.avi` file with a PNG video stream (fourcc `MPNG`: what `pixel_format="png"` exports), read natively (pngsource.py): the
+    PNG files stay compressed in pinned memory and over the link and are inflated and unfiltered on the device into the texture,
+    bit-exactly (csrc/png_decode_kernels.hpp: 8-bit RGB without interlace; anything else raises ValueError naming the IHDR field; chunk
+    CRC-32s are not checked, the Adler-32 is, on the device). With `format="png"`, `frames=` yields PNG files as `bytes` — numbered
+    files are `frames=(p.read_bytes() for p in sorted(folder.glob("*.png")))`. A damaged frame raises RuntimeError naming the source
+    frame; it is not drawn (DESIGN.md §7e);
   * any other `path` (an `.avi` with another codec included) is decoded by an `ffmpeg` binary on PATH when there is one (rawvideo rgb24 over a pipe),
     otherwise construction raises — there is no silent fallback.
 A source shorter than the scene keeps its last frame on screen (the reference's generator would raise
@@ -173,11 +179,15 @@ class VideoStage:
             raise ValueError("a staged video needs an RGB8 texture with layers = 1")
         boxes = [box.texture for (_, _, box) in texture.boxes]
         self.serials = tuple(box.serial for box in boxes)              # which device textures the handle writes into
-        self.planar, self.compressed = video.format == "i420", video.format == "mjpeg"
+        self.planar, self.compressed, self.png = video.format == "i420", video.format in ("mjpeg", "png"), video.format == "png"
         self.width, self.height, self.jpeg = video.width, video.height, video.jpeg
         self.frame_bytes = video.capacity if self.compressed else video.width*video.height*3//(2 if self.planar else 1)   # what a slot holds
         self.slots, self.handle = slots(self.frame_bytes) if callable(slots) else slots, N.Handle()
         handles = (N.Handle*len(boxes))(*[box.handle for box in boxes])
+        if self.png:
+            N.check(N.lib().sfx_video_create_png(video.scene.context.handle, handles, texture.temporal, video.width, video.height, video.capacity, self.slots,
+                                                 C.byref(self.handle)))
+            return
         if self.compressed:
             jpeg = video.jpeg
             N.check(N.lib().sfx_video_create_mjpeg(video.scene.context.handle, handles, texture.temporal, video.width, video.height, jpeg.components,
@@ -195,9 +205,9 @@ class VideoStage:
     def fill(self, view: np.ndarray, frame, label: str) -> Optional[int]:
         """One source frame — an rgb array, an i420 array or a JPEG stream, as the video's format says — into the pinned `view`; returns
         the bytes to `submit` (None: the format's fixed size). `label` names the frame in an error."""
-        if self.compressed:                                           # the stream's tables, interval starts and scan; only they are copied
-            from shaderflow_amd.mjpegsource import stage
-            return stage(frame, self.jpeg, view, label)
+        if self.compressed:                                           # the stream's tables, interval starts and scan (a PNG file's IDAT data); only they are copied
+            from shaderflow_amd import mjpegsource, pngsource
+            return (pngsource if self.png else mjpegsource).stage(frame, self.jpeg, view, label)
         frame = np.asarray(frame, np.uint8)
         if frame.size != self.frame_bytes:
             raise ValueError(f"{label}: {'an i420' if self.planar else 'an rgb'} frame of {self.width} x {self.height} has {self.frame_bytes} bytes, the source gave {frame.size}")
@@ -229,6 +239,16 @@ class VideoStage:
         N.check(N.lib().sfx_video_jpeg_paths(self.handle, C.byref(sync), C.byref(serial)))
         return sync.value, serial.value
 
+    def png_paths(self) -> tuple[int, int]:
+        """Landed PNG frames by inflate path: (a wave per segment, one wave for the stream — chosen so or fallen back to)"""
+        parallel, serial = C.c_uint64(0), C.c_uint64(0)
+        N.check(N.lib().sfx_video_png_paths(self.handle, C.byref(parallel), C.byref(serial)))
+        return parallel.value, serial.value
+
+    def describe_status(self, status: int) -> str:
+        from shaderflow_amd import mjpegsource, pngsource
+        return (pngsource if self.png else mjpegsource).describe_status(status)
+
     def step(self, slot: int) -> None:
         N.check(N.lib().sfx_video_step(self.handle, slot))
 
@@ -255,11 +275,11 @@ class ShaderVideo(ShaderModule):
     fps: Optional[float] = None
     format: Optional[str] = None
     """None: the source yields rgb arrays; "i420": planar 4:2:0 frames of width*height*3//2 bytes (set by the planar file sources);
-    "mjpeg": baseline JPEG streams as `bytes` (set by the Motion-JPEG file sources)"""
+    "mjpeg": baseline JPEG streams as `bytes` (set by the Motion-JPEG file sources); "png": PNG files as `bytes` (set by an MPNG `.avi`)"""
     jpeg: Optional[object] = None
-    """format "mjpeg": the first frame's header (mjpegsource.JpegHeader): the geometry and sampling every frame must have"""
+    """format "mjpeg" / "png": the first frame's header (mjpegsource.JpegHeader / pngsource.PngHeader): the geometry every frame must have"""
     capacity: int = 0
-    """format "mjpeg": bytes of a staged frame at the most (from the container's largest chunk; for `frames=` a raw picture's worth)"""
+    """format "mjpeg" / "png": bytes of a staged frame at the most (from the container's largest chunk; for `frames=` a raw picture's worth)"""
     _stage: Optional[VideoStage] = None
     _clip: Optional[object] = None
     _reader: Optional[Iterator] = None
@@ -268,8 +288,8 @@ class ShaderVideo(ShaderModule):
 
     def __attrs_post_init__(self):
         ShaderModule.__attrs_post_init__(self)
-        if self.format not in (None, "i420", "mjpeg"):
-            raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays), 'i420' or 'mjpeg'")
+        if self.format not in (None, "i420", "mjpeg", "png"):
+            raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays), 'i420', 'mjpeg' or 'png'")
         self._reader = self._open()
         if not all((self.width, self.height, self.fps)):
             raise ValueError("ShaderVideo needs width, height and fps (give them, or a source they can be read from)")
@@ -282,7 +302,7 @@ class ShaderVideo(ShaderModule):
         if self.frames is not None:
             if isinstance(self.frames, np.ndarray) and self.format is None:
                 self.height, self.width = self.height or self.frames.shape[1], self.width or self.frames.shape[2]
-            if self.format == "mjpeg":
+            if self.format in ("mjpeg", "png"):
                 return self._open_compressed(iter(self.frames), None)
             return iter(self.frames)
         if self.path is None:
@@ -309,13 +329,16 @@ class ShaderVideo(ShaderModule):
             self._clip = clip = RawReader(self.path, self.fps)
             return self._open_compressed(clip, clip.largest)
         if suffix == ".avi":
-            from shaderflow_amd.mjpegsource import AviReader
-            try:
-                clip = AviReader(self.path)
-            except LookupError:                                       # an AVI file with another codec: ffmpeg's, as before
-                clip = None
+            from shaderflow_amd import mjpegsource, pngsource
+            clip = None
+            for reader in (mjpegsource.AviReader, pngsource.AviReader):   # MJPG, then MPNG; an AVI file with another codec: ffmpeg's, as before
+                try:
+                    clip = reader(self.path)
+                    break
+                except LookupError:
+                    continue
             if clip is not None:
-                self._clip, self.fps = clip, self.fps or clip.fps
+                self._clip, self.fps, self.format = clip, self.fps or clip.fps, clip.format
                 return self._open_compressed(clip, clip.largest)
         if not (shutil.which("ffmpeg") and shutil.which("ffprobe")):
             raise RuntimeError(f"{self.path}: decoding this container needs the ffmpeg and ffprobe binaries; "
@@ -325,16 +348,19 @@ class ShaderVideo(ShaderModule):
         return iter_video_frames(self.path, self.width, self.height)
 
     def _open_compressed(self, source: Iterator, largest: Optional[int]) -> Iterator:
-        """A source of JPEG streams: the clip's geometry and sampling are its first frame's"""
+        """A source of JPEG streams, or of PNG files (`format`): the clip's geometry and sampling are its first frame's"""
         import itertools
-        from shaderflow_amd.mjpegsource import capacity_for, parse_header
+        if self.format == "png":
+            from shaderflow_amd.pngsource import capacity_for, parse_header
+        else:
+            from shaderflow_amd.mjpegsource import capacity_for, parse_header
         first = next(source, None)
         if first is None:
-            raise ValueError(f"{self.name}: a Motion-JPEG source without a frame")
+            raise ValueError(f"{self.name}: a {'PNG' if self.format == 'png' else 'Motion-JPEG'} source without a frame")
         self.jpeg = parse_header(first)
         if (self.width and self.width != self.jpeg.width) or (self.height and self.height != self.jpeg.height):
             raise ValueError(f"{self.name}: the frames are {self.jpeg.width} x {self.jpeg.height}, not {self.width} x {self.height}")
-        self.width, self.height, self.format = self.jpeg.width, self.jpeg.height, "mjpeg"
+        self.width, self.height, self.format = self.jpeg.width, self.jpeg.height, self.format or "mjpeg"
         self.capacity = capacity_for(self.jpeg, largest)
         return itertools.chain([first], source)
 
@@ -347,7 +373,7 @@ class ShaderVideo(ShaderModule):
             self._exhausted = True
             logger.warning(f"{self.name}: source ended after {self._read} frames, holding the last one")
             return
-        if self.format == "mjpeg":
+        if self.format in ("mjpeg", "png"):
             self._read += 1                                             # (a damaged frame is passed over: the next update() shows the next one)
             self._show_staged(frame, self._read - 1)
             return
@@ -375,8 +401,7 @@ class ShaderVideo(ShaderModule):
         self.texture.roll()                                           # (the device rolled its matrix even when it left a bad frame's box alone)
         stage.serials = tuple(box.texture.serial for (_, _, box) in self.texture.boxes)
         if bad is not None:
-            from shaderflow_amd.mjpegsource import describe_status
-            raise RuntimeError(f"{self.name}: source frame {source} could not be decoded: {describe_status(bad[1])}")
+            raise RuntimeError(f"{self.name}: source frame {source} could not be decoded: {stage.describe_status(bad[1])}")
         self.texture.refresh_host_copy()
 
     def destroy(self) -> None:

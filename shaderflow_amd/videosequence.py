@@ -30,6 +30,7 @@ Motion-JPEG sources (`video.format == "mjpeg"`: mjpegsource.py) stay compressed 
 (csrc/jpeg_decode_kernels.hpp) instead of `k_video_frame`. `slot_count` works from the slots' capacity; frames taken ahead go back in
 front of the source as the `bytes` they came as; a frame the device could not decode fails the export with RuntimeError naming the
 source frame (`undecoded`; found behind the last chunk, it is raised once the export is finished), and the context stays usable.
+PNG sources (`video.format == "png"`: pngsource.py) go the same way, with `pngsource.stage` and the PNG kernels (csrc/png_decode_kernels.hpp).
 """
 from __future__ import annotations
 
@@ -172,8 +173,7 @@ class VideoSequence(FrameSource):
         bad = self.stage.bad_frame(wait) if self.stage is not None else None      # (an uncompressed frame is never bad, and nothing waits for one)
         if bad is None:
             return None
-        from shaderflow_amd.mjpegsource import describe_status
-        return RuntimeError(f"{self.video.name}: source frame {self.first_read + bad[0]} could not be decoded: {describe_status(bad[1])}")
+        return RuntimeError(f"{self.video.name}: source frame {self.first_read + bad[0]} could not be decoded: {self.stage.describe_status(bad[1])}")
 
     def raise_undecoded(self) -> None:
         """Behind `run_source`: a damaged frame that only `settle`'s waiting check found. The run drew every frame, so the clock is
