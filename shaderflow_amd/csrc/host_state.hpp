@@ -1,5 +1,5 @@
 // host_state.hpp — what the translation units of libshaderflow_hip.so share on the HOST side: error reporting, handles, the context and
-// texture objects, and the few calls the C-ABI units (capi.hip, capi_readout.hip, capi_audio.hip, capi_piano.hip, capi_video.hip) make into each other. capi.hip owns the
+// texture objects, and the few calls the C-ABI units (capi.hip, capi_readout.hip, capi_audio.hip, capi_piano.hip, capi_video.hip) make into each other (capi_video.hip and the decoders of compressed sources: video_decoder.hpp). capi.hip owns the
 // definitions of the thread-local state; the launch units (launch_*.hip) only read it.
 #pragma once
 

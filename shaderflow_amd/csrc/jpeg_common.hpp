@@ -1,4 +1,4 @@
-// jpeg_common.hpp — what the Motion-JPEG encoder (jpeg_kernels.hpp, capi_jpeg.hip) and decoder (jpeg_decode_kernels.hpp, capi_video.hip)
+// jpeg_common.hpp — what the Motion-JPEG encoder (jpeg_kernels.hpp, capi_jpeg.hip) and decoder (jpeg_decode_kernels.hpp, capi_video_jpeg.hip)
 // share, each stated once: the zigzag order, the DCT basis, the standard's Annex K tables, and the test a staged frame's descriptor
 // (include/shaderflow_hip.h: sfx_jpeg_frame) must pass before a kernel indexes anything with it.
 #pragma once

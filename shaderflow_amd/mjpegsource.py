@@ -14,7 +14,10 @@ decode, `sfx_jpeg_frame` of include/shaderflow_hip.h the layout of a staged fram
     in cache anyway (it copies them into the slot), and its result sizes the entropy kernel's launch — a kernel that searched would
     need a second launch, or a read-back, to learn how many lanes the first one wants.
   * `AviReader(path)`, `RawReader(path, fps)`: iterators of `bytes`, one JPEG stream per frame, with `width`, `height`, `fps`,
-    `sampling` and `largest` (the largest frame's bytes: the slots' capacity).
+    `sampling` and `largest` (the largest frame's bytes: the slots' capacity). The map and the RIFF walk are clips.py's.
+  * `create(...)`, `paths(handle)`: the video handle of such a source (sfx_video_create_mjpeg) and its landed frames by entropy path.
+
+The module is the codec video.py and clips.py speak to: `FORMAT`, `TITLE`, `FOURCC` and the functions above.
 
 Entropy decoding runs on the device alone. A frame whose restart intervals are short takes a lane per interval; a frame with long
 intervals — a stream without restart markers is ONE interval per frame — is cut into subsequences of `SYNC_SUBSEQUENCE` bytes, a lane
@@ -23,15 +26,19 @@ files on the host is out of scope.
 """
 from __future__ import annotations
 
-import mmap
+import ctypes as C
 import struct
-import warnings
+import sys
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Iterator, Optional
+from typing import Optional
 
 import numpy as np
 
+from shaderflow_amd import _native as N
+from shaderflow_amd.clips import AviClip, Clip
+
+FORMAT, TITLE, FOURCC = "mjpeg", "Motion-JPEG", b"MJPG"
 # include/shaderflow_hip.h: sfx_jpeg_frame, the fixed part of a staged frame (the interval table starts behind it), and SFX_JPEG_*
 FRAME_MAGIC = 0x444a4653                                              # "SFJD"
 STAGED = np.dtype([("magic", "<u4"), ("scan_bytes", "<u4"), ("restart", "<u4"), ("intervals", "<u4"), ("scan_offset", "<u4"), ("components", "<u4"),
@@ -40,7 +47,7 @@ STAGED = np.dtype([("magic", "<u4"), ("scan_bytes", "<u4"), ("restart", "<u4"), 
 assert STAGED.itemsize == 1536
 FRAME_FIXED = STAGED.itemsize
 BAD_CODE, BAD_RUN, BAD_RESTART, OUT_OF_BITS, BAD_DESCRIPTOR = 1, 2, 4, 8, 16
-# csrc/capi_video.hip: the subsequence path's production values — a subsequence's bytes, rounds per phase, and how many subsequences a
+# csrc/capi_video_jpeg.hip: the subsequence path's production values — a subsequence's bytes, rounds per phase, and how many subsequences a
 # frame's mean restart interval (scan bytes / intervals) must hold for the frame to take the path
 SYNC_SUBSEQUENCE, SYNC_ROUNDS, SYNC_RULE = 64, 255, 4
 STATUS_BITS = {BAD_CODE: "a code that matches no Huffman code", BAD_RUN: "a zero run past the block's 63rd term", BAD_RESTART: "a missing or wrong RSTn marker",
@@ -267,61 +274,14 @@ def describe_status(status: int) -> str:
     return "; ".join(text for bit, text in STATUS_BITS.items() if status & bit) or f"status {status}"
 
 
-# ---- containers ----------------------------------------------------------------------------------------------------------------------
+# ---- containers (clips.py has the map and the RIFF walk; this module is their codec) ---------------------------------------------------
 
-class MjpegClip:
-    """Frames of a Motion-JPEG file as `bytes`, in order, through a read-only memory map. `index`: (offset, size) of every frame. The
-    file is closed behind the last frame, or by `close()`."""
-    format = "mjpeg"
-
-    def __init__(self, path: Path):
-        self.path = Path(path)
-        self.file = open(self.path, "rb")
-        self.map = mmap.mmap(self.file.fileno(), 0, access=mmap.ACCESS_READ) if self.path.stat().st_size else b""
-        self.data = np.frombuffer(self.map, np.uint8)
-        self.index: list[tuple[int, int]] = []
-        self.fps: Optional[float] = None
-        self.next = 0
-
-    def describe(self) -> None:
-        """width, height, sampling, components from the first frame; `largest` from the index"""
-        if not self.index:
-            raise ValueError(f"{self.path}: no Motion-JPEG frame")
-        offset, size = self.index[0]
-        self.header = parse_header(bytes(self.map[offset:offset + size]))
-        self.width, self.height, self.sampling, self.components = self.header.width, self.header.height, self.header.sampling, self.header.components
-        self.largest = max(size for _, size in self.index)
-
-    def __len__(self) -> int:
-        return len(self.index)
-
-    def __iter__(self) -> Iterator[bytes]:
-        return self
-
-    def __next__(self) -> bytes:
-        if self.map is None or self.next >= len(self.index):
-            self.close()
-            raise StopIteration
-        offset, size = self.index[self.next]
-        self.next += 1
-        return bytes(self.map[offset:offset + size])
-
-
-    def close(self) -> None:
-        if self.map is not None:
-            self.data = None                                          # (the array is a view of the map)
-            if self.map:
-                self.map.close()
-            self.file.close()
-            self.map = None
-
-
-class RawReader(MjpegClip):
+class RawReader(Clip):
     """`.mjpeg` / `.mjpg`: JPEG images back to back, split by walking each one's marker segments to SOS and then to the marker that
     ends its scan. A truncated last image ends the clip. The rate is not in the file: `fps=`."""
 
     def __init__(self, path: Path, fps: Optional[float]):
-        super().__init__(path)
+        super().__init__(path, sys.modules[__name__])
         if not fps:
             raise ValueError(f"{self.path}: a bare Motion-JPEG stream does not say its rate: give fps=")
         self.fps = float(fps)
@@ -340,82 +300,26 @@ class RawReader(MjpegClip):
         self.describe()
 
 
-class AviReader(MjpegClip):
-    """RIFF AVI 1.0: `hdrl` (`strl`: `strh`, `strf`) and the `movi` list's `NNdc` / `NNdb` chunks of the first `vids` stream whose
-    handler or compression is one of `fourccs` (MJPG; pngsource.py asks for MPNG), in either case; `idx1` when it is there (and consistent), else a walk over `movi`. Audio and every other chunk are
-    skipped. A chunk of this stream without bytes is a dropped frame: the picture in front of it again, so the frames behind it keep
-    their times (nothing, in front of the first picture). Frames in OpenDML `AVIX` extensions are not read: a warning says so."""
+class AviReader(AviClip):
+    """RIFF AVI 1.0 with an `MJPG` video stream (handler or compression, in either case): one JPEG stream per chunk"""
 
-    def add(self, offset: int, size: int) -> None:
-        if size:
-            self.index.append((offset, size))
-        elif self.index:
-            self.index.append(self.index[-1])                         # a dropped frame
+    def __init__(self, path: Path):
+        super().__init__(path, (sys.modules[__name__],))
 
-    def __init__(self, path: Path, fourccs: tuple = (b"MJPG",)):
-        super().__init__(path)
-        data = self.map
-        if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"AVI ":
-            raise ValueError(f"{self.path}: not a RIFF AVI file")
-        self.stream, streams, movi, idx1 = None, 0, None, None
-        end = min(len(data), 8 + struct.unpack("<I", data[4:8])[0])
-        if len(data) > end + 12 and data[end + (end & 1):end + (end & 1) + 4] == b"RIFF":
-            warnings.warn(f"{self.path}: frames in OpenDML extensions (RIFF AVIX) are not read: the clip ends with the first RIFF chunk", stacklevel=3)
 
-        def chunks(first: int, last: int):
-            pos = first
-            while pos + 8 <= last:
-                fourcc, size = bytes(data[pos:pos + 4]), struct.unpack("<I", data[pos + 4:pos + 8])[0]
-                yield fourcc, pos + 8, min(size, last - pos - 8)
-                pos += 8 + size + (size & 1)
+def create(context_handle, boxes, temporal: int, header: JpegHeader, capacity: int, slots: int) -> N.Handle:
+    """The video handle of a source whose frames have `header`'s geometry: `boxes`, the texture matrix' handles as a ctypes array"""
+    handle = N.Handle()
+    N.check(N.lib().sfx_video_create_mjpeg(context_handle, boxes, temporal, header.width, header.height, header.components, header.sampling[0], header.sampling[1],
+                                           capacity, slots, C.byref(handle)))
+    return handle
 
-        for fourcc, at, size in chunks(12, end):
-            if fourcc == b"LIST" and data[at:at + 4] == b"hdrl":
-                for inner, inner_at, inner_size in chunks(at + 4, at + size):
-                    if inner != b"LIST" or data[inner_at:inner_at + 4] != b"strl":
-                        continue
-                    kind = handler = compression = None
-                    for leaf, leaf_at, leaf_size in chunks(inner_at + 4, inner_at + inner_size):
-                        if leaf == b"strh" and leaf_size >= 28:
-                            kind, handler = bytes(data[leaf_at:leaf_at + 4]), bytes(data[leaf_at + 4:leaf_at + 8])
-                            scale, rate = struct.unpack("<II", data[leaf_at + 20:leaf_at + 28])
-                        elif leaf == b"strf" and leaf_size >= 20:
-                            compression = bytes(data[leaf_at + 16:leaf_at + 20])
-                    if self.stream is None and kind == b"vids" and {(handler or b"").upper(), (compression or b"").upper()} & set(fourccs):
-                        self.stream = streams
-                        self.fps = rate/scale if scale and rate else None
-                    streams += 1
-            elif fourcc == b"LIST" and data[at:at + 4] == b"movi":
-                movi = (at, size)
-            elif fourcc == b"idx1":
-                idx1 = (at, size)
-        if self.stream is None:
-            self.close()                                              # (the caller may try another reader on the file)
-            raise LookupError(f"{self.path}: no video stream with handler or compression {' or '.join(name.decode() for name in fourccs)}")
-        if movi is None:
-            raise ValueError(f"{self.path}: no movi list")
-        if not self.fps:
-            raise ValueError(f"{self.path}: strh gives no rate (dwRate / dwScale)")
-        names = (b"%02ddc" % self.stream, b"%02ddb" % self.stream)
-        if idx1 is not None:
-            entries = np.frombuffer(data, np.dtype([("id", "S4"), ("flags", "<u4"), ("offset", "<u4"), ("size", "<u4")]), idx1[1]//16, idx1[0])
-            mine = entries[np.isin(entries["id"], names)]
-            if mine.size:
-                # the offsets count from the movi fourcc, or (some writers) from the file's start: the first entry tells which
-                base = movi[0] if bytes(data[movi[0] + int(mine["offset"][0]):movi[0] + int(mine["offset"][0]) + 4]) in names else 0
-                found = [(base + int(offset) + 8, int(size)) for offset, size in zip(mine["offset"], mine["size"])]
-                if all(offset + size <= len(data) and bytes(data[offset - 8:offset - 4]) in names for offset, size in found):
-                    for entry in found:                               # (else the index does not point at this stream's chunks: walk instead)
-                        self.add(*entry)
-        if not self.index:
-            def walk(first, last):
-                for fourcc, at, size in chunks(first, last):
-                    if fourcc == b"LIST" and data[at:at + 4] == b"rec ":
-                        walk(at + 4, at + size)
-                    elif fourcc in names:
-                        self.add(at, size)
-            walk(movi[0] + 4, movi[0] + movi[1])
-        self.describe()
+
+def paths(handle) -> tuple[int, int]:
+    """Landed frames by entropy path: (a lane per subsequence, a lane per restart interval)"""
+    sync, serial = C.c_uint64(0), C.c_uint64(0)
+    N.check(N.lib().sfx_video_jpeg_paths(handle, C.byref(sync), C.byref(serial)))
+    return sync.value, serial.value
 
 
 def device_decode(stream, context=None, sync=None, subsequence_bytes=None, round_budget=None) -> dict:
@@ -426,9 +330,6 @@ def device_decode(stream, context=None, sync=None, subsequence_bytes=None, round
     `round_budget` rounds per phase (None: the production values); `sync="auto"`: whichever path a video handle would choose for this
     frame (SHADERFLOW_JPEG_SYNC is honoured); `sync=False`: the lane-per-interval kernel. "sync" is then the info record
     {"subsequences" (0: the lane-per-interval kernel ran alone), "rounds_used", "fell_back"}."""
-    import ctypes as C
-
-    from shaderflow_amd import _native as N
     context = context or N.default_context()
     header = parse_header(stream)
     view = np.zeros(capacity_for(header, len(stream)), np.uint8)
@@ -457,6 +358,3 @@ def device_decode(stream, context=None, sync=None, subsequence_bytes=None, round
                                              C.byref(status), words))
         info = {"subsequences": int(words[0]), "rounds_used": int(words[1]), "fell_back": int(words[2])}
     return {"status": status.value, "coefficients": coefficients, "planes": planes, "rgb": rgb, "header": header, "sync": info}
-
-
-decode_on_device = device_decode

@@ -14,7 +14,10 @@ link; the device inflates and unfilters them where the texture lives (csrc/png_d
   * `stage(stream, expected, view, name)`: the staged frame into a pinned slot: the record, one word per segment (IDAT chunk) saying
     where its bytes start in the payload, and the payload: the IDAT data concatenated, the 2-byte zlib header and the 4-byte Adler-32
     stripped (the Adler-32 goes into the record).
-  * `AviReader(path)` finds the `MPNG` stream (mjpegsource.AviReader's RIFF walk, with this FourCC).
+  * `AviReader(path)` finds the `MPNG` stream (clips.py's RIFF walk, with this FourCC).
+  * `create(...)`, `paths(handle)`: the video handle of such a source (sfx_video_create_png) and its landed frames by inflate path.
+
+The module is the codec video.py and clips.py speak to: `FORMAT`, `TITLE`, `FOURCC` and the functions above.
 
 The device decodes a frame on one of two paths, both exact (csrc/png_decode_kernels.hpp): a wave per segment when the frame has at
 least two segments and every one but the last ends in `00 00 FF FF` (`segment_path`: what this package's encoder writes — a stripe of
@@ -24,15 +27,20 @@ SHADERFLOW_PNG_SEGMENTS=0 / 1 forces either. Numbered-file patterns, APNG and 16
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 import struct
+import sys
 from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Optional
 
 import numpy as np
 
-from shaderflow_amd import mjpegsource
+from shaderflow_amd import _native as N
+from shaderflow_amd.clips import AviClip
+
+FORMAT, TITLE, FOURCC = "png", "PNG", b"MPNG"
 
 # include/shaderflow_hip.h: sfx_png_frame, the record at the start of a staged frame (the segment table starts behind it), and SFX_PNG_*
 FRAME_MAGIC = 0x4e504653                                              # "SFPN"
@@ -124,7 +132,7 @@ def parse_header(stream) -> PngHeader:
 
 
 def segment_path(header: PngHeader) -> bool:
-    """Whether the device's production rule sends this frame down the segment path (csrc/capi_video.hip: png_segments_chosen): at
+    """Whether the device's production rule sends this frame down the segment path (csrc/capi_video_png.hip: png_segments_chosen): at
     least two segments, every one but the last ending in 00 00 FF FF. (The first segment loses the zlib header and the last one the
     Adler-32 when they are staged: neither touches a segment's end but the last's.)"""
     forced = os.environ.get("SHADERFLOW_PNG_SEGMENTS")
@@ -187,20 +195,25 @@ def describe_status(status: int) -> str:
     return "; ".join(text for bit, text in STATUS_BITS.items() if status & bit) or f"status {status}"
 
 
-class AviReader(mjpegsource.AviReader):
+class AviReader(AviClip):
     """RIFF AVI 1.0 with an `MPNG` video stream (handler or compression, in either case): one PNG file per chunk"""
-    format = "png"
 
     def __init__(self, path: Path):
-        super().__init__(path, fourccs=(b"MPNG",))
+        super().__init__(path, (sys.modules[__name__],))
 
-    def describe(self) -> None:
-        if not self.index:
-            raise ValueError(f"{self.path}: no PNG frame")
-        offset, size = self.index[0]
-        self.header = parse_header(bytes(self.map[offset:offset + size]))
-        self.width, self.height = self.header.width, self.header.height
-        self.largest = max(size for _, size in self.index)
+
+def create(context_handle, boxes, temporal: int, header: PngHeader, capacity: int, slots: int) -> N.Handle:
+    """The video handle of a source whose frames have `header`'s geometry: `boxes`, the texture matrix' handles as a ctypes array"""
+    handle = N.Handle()
+    N.check(N.lib().sfx_video_create_png(context_handle, boxes, temporal, header.width, header.height, capacity, slots, C.byref(handle)))
+    return handle
+
+
+def paths(handle) -> tuple[int, int]:
+    """Landed frames by inflate path: (a wave per segment, one wave for the stream — chosen so or fallen back to)"""
+    parallel, serial = C.c_uint64(0), C.c_uint64(0)
+    N.check(N.lib().sfx_video_png_paths(handle, C.byref(parallel), C.byref(serial)))
+    return parallel.value, serial.value
 
 
 def device_decode(stream, context=None, segments=None) -> dict:
@@ -208,9 +221,6 @@ def device_decode(stream, context=None, segments=None) -> dict:
     1 + 3 width) uint8: the inflated stream, "rgb" (height, width, 3) top row first (zeros when the status is bad), "header", "info":
     {"segments", "parallel", "fell_back"}}. `segments=False`: the serial path; `True`: the segment path (the serial path behind it
     when a segment does not validate); "auto" or None: what a video handle would choose (SHADERFLOW_PNG_SEGMENTS is honoured)."""
-    import ctypes as C
-
-    from shaderflow_amd import _native as N
     if segments not in (None, False, True, "auto"):
         raise ValueError(f"segments={segments!r}: None, False, True or \"auto\"")
     context = context or N.default_context()

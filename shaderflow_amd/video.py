@@ -52,9 +52,12 @@ import numpy as np
 from attrs import define
 
 from shaderflow_amd import _native as N
+from shaderflow_amd import mjpegsource, pngsource
+from shaderflow_amd.clips import AviClip
 from shaderflow_amd.module import ShaderModule, logger
 from shaderflow_amd.texture import ShaderTexture
 
+CODECS = {"mjpeg": mjpegsource, "png": pngsource}                    # a compressed `format` → the module that reads, stages and decodes it
 MJPEG_SUFFIXES = (".mjpeg", ".mjpg")
 Y4M_CHROMA = ("420", "420jpeg", "420mpeg2", "420paldv")              # all read as the same 8-bit 4:2:0 bytes (the siting is not interpolated)
 PLANAR_SUFFIXES = (".yuv", ".i420")                                   # raw planar frames: the suffixes exporting.py's yuv420p sink writes
@@ -179,19 +182,13 @@ class VideoStage:
             raise ValueError("a staged video needs an RGB8 texture with layers = 1")
         boxes = [box.texture for (_, _, box) in texture.boxes]
         self.serials = tuple(box.serial for box in boxes)              # which device textures the handle writes into
-        self.planar, self.compressed, self.png = video.format == "i420", video.format in ("mjpeg", "png"), video.format == "png"
-        self.width, self.height, self.jpeg = video.width, video.height, video.jpeg
-        self.frame_bytes = video.capacity if self.compressed else video.width*video.height*3//(2 if self.planar else 1)   # what a slot holds
+        self.planar, self.codec = video.format == "i420", CODECS.get(video.format)
+        self.width, self.height, self.header = video.width, video.height, video.header
+        self.frame_bytes = video.capacity if self.codec else video.width*video.height*3//(2 if self.planar else 1)   # what a slot holds
         self.slots, self.handle = slots(self.frame_bytes) if callable(slots) else slots, N.Handle()
         handles = (N.Handle*len(boxes))(*[box.handle for box in boxes])
-        if self.png:
-            N.check(N.lib().sfx_video_create_png(video.scene.context.handle, handles, texture.temporal, video.width, video.height, video.capacity, self.slots,
-                                                 C.byref(self.handle)))
-            return
-        if self.compressed:
-            jpeg = video.jpeg
-            N.check(N.lib().sfx_video_create_mjpeg(video.scene.context.handle, handles, texture.temporal, video.width, video.height, jpeg.components,
-                                                   jpeg.sampling[0], jpeg.sampling[1], video.capacity, self.slots, C.byref(self.handle)))
+        if self.codec:
+            self.handle = self.codec.create(video.scene.context.handle, handles, texture.temporal, video.header, video.capacity, self.slots)
             return
         N.check(N.lib().sfx_video_create(video.scene.context.handle, handles, texture.temporal, video.width, video.height,
                                          N.VIDEO_I420 if self.planar else N.VIDEO_RGB24, self.slots, C.byref(self.handle)))
@@ -205,9 +202,8 @@ class VideoStage:
     def fill(self, view: np.ndarray, frame, label: str) -> Optional[int]:
         """One source frame — an rgb array, an i420 array or a JPEG stream, as the video's format says — into the pinned `view`; returns
         the bytes to `submit` (None: the format's fixed size). `label` names the frame in an error."""
-        if self.compressed:                                           # the stream's tables, interval starts and scan (a PNG file's IDAT data); only they are copied
-            from shaderflow_amd import mjpegsource, pngsource
-            return (pngsource if self.png else mjpegsource).stage(frame, self.jpeg, view, label)
+        if self.codec:                                                # the stream's tables, interval starts and scan (a PNG file's IDAT data); only they are copied
+            return self.codec.stage(frame, self.header, view, label)
         frame = np.asarray(frame, np.uint8)
         if frame.size != self.frame_bytes:
             raise ValueError(f"{label}: {'an i420' if self.planar else 'an rgb'} frame of {self.width} x {self.height} has {self.frame_bytes} bytes, the source gave {frame.size}")
@@ -217,7 +213,7 @@ class VideoStage:
     def put_back(self, held):
         """What goes back in front of the source for a frame that was taken from it and not drawn: `held` is the stream a compressed
         frame came as, or the pinned view an uncompressed one was copied into — a copy of it, shaped as the source yields frames"""
-        return held if self.compressed else held.copy().reshape((-1,) if self.planar else (self.height, self.width, 3))
+        return held if self.codec else held.copy().reshape((-1,) if self.planar else (self.height, self.width, 3))
 
     def submit(self, slot: int, nbytes: Optional[int] = None) -> None:
         """`nbytes`: the bytes the frame has (a compressed frame: only they are copied)"""
@@ -233,21 +229,13 @@ class VideoStage:
         N.check(N.lib().sfx_video_status(self.handle, 1 if wait else 0, C.byref(frame), C.byref(status)))
         return None if frame.value < 0 else (frame.value, status.value)
 
-    def jpeg_paths(self) -> tuple[int, int]:
-        """Landed Motion-JPEG frames by entropy path: (a lane per subsequence, a lane per restart interval)"""
-        sync, serial = C.c_uint64(0), C.c_uint64(0)
-        N.check(N.lib().sfx_video_jpeg_paths(self.handle, C.byref(sync), C.byref(serial)))
-        return sync.value, serial.value
-
-    def png_paths(self) -> tuple[int, int]:
-        """Landed PNG frames by inflate path: (a wave per segment, one wave for the stream — chosen so or fallen back to)"""
-        parallel, serial = C.c_uint64(0), C.c_uint64(0)
-        N.check(N.lib().sfx_video_png_paths(self.handle, C.byref(parallel), C.byref(serial)))
-        return parallel.value, serial.value
+    def paths(self) -> tuple[int, int]:
+        """Landed compressed frames by the codec's two decode paths: (the parallel one, the serial one) — Motion-JPEG: a lane per
+        subsequence / per restart interval; PNG: a wave per segment / one wave for the stream, chosen so or fallen back to"""
+        return self.codec.paths(self.handle)
 
     def describe_status(self, status: int) -> str:
-        from shaderflow_amd import mjpegsource, pngsource
-        return (pngsource if self.png else mjpegsource).describe_status(status)
+        return self.codec.describe_status(status)
 
     def step(self, slot: int) -> None:
         N.check(N.lib().sfx_video_step(self.handle, slot))
@@ -276,7 +264,7 @@ class ShaderVideo(ShaderModule):
     format: Optional[str] = None
     """None: the source yields rgb arrays; "i420": planar 4:2:0 frames of width*height*3//2 bytes (set by the planar file sources);
     "mjpeg": baseline JPEG streams as `bytes` (set by the Motion-JPEG file sources); "png": PNG files as `bytes` (set by an MPNG `.avi`)"""
-    jpeg: Optional[object] = None
+    header: Optional[object] = None
     """format "mjpeg" / "png": the first frame's header (mjpegsource.JpegHeader / pngsource.PngHeader): the geometry every frame must have"""
     capacity: int = 0
     """format "mjpeg" / "png": bytes of a staged frame at the most (from the container's largest chunk; for `frames=` a raw picture's worth)"""
@@ -288,7 +276,7 @@ class ShaderVideo(ShaderModule):
 
     def __attrs_post_init__(self):
         ShaderModule.__attrs_post_init__(self)
-        if self.format not in (None, "i420", "mjpeg", "png"):
+        if self.format not in (None, "i420", *CODECS):
             raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays), 'i420', 'mjpeg' or 'png'")
         self._reader = self._open()
         if not all((self.width, self.height, self.fps)):
@@ -302,7 +290,7 @@ class ShaderVideo(ShaderModule):
         if self.frames is not None:
             if isinstance(self.frames, np.ndarray) and self.format is None:
                 self.height, self.width = self.height or self.frames.shape[1], self.width or self.frames.shape[2]
-            if self.format in ("mjpeg", "png"):
+            if self.format in CODECS:
                 return self._open_compressed(iter(self.frames), None)
             return iter(self.frames)
         if self.path is None:
@@ -325,19 +313,14 @@ class ShaderVideo(ShaderModule):
             self.width, self.height, self.fps, self.format = clip.width, clip.height, self.fps or clip.fps, "i420"
             return clip
         if suffix in MJPEG_SUFFIXES:
-            from shaderflow_amd.mjpegsource import RawReader
-            self._clip = clip = RawReader(self.path, self.fps)
+            self._clip = clip = mjpegsource.RawReader(self.path, self.fps)
             return self._open_compressed(clip, clip.largest)
         if suffix == ".avi":
-            from shaderflow_amd import mjpegsource, pngsource
-            clip = None
-            for reader in (mjpegsource.AviReader, pngsource.AviReader):   # MJPG, then MPNG; an AVI file with another codec: ffmpeg's, as before
-                try:
-                    clip = reader(self.path)
-                    break
-                except LookupError:
-                    continue
-            if clip is not None:
+            try:
+                clip = AviClip(self.path, CODECS.values())
+            except LookupError:                                       # an AVI file with another codec: ffmpeg's, as before
+                pass
+            else:
                 self._clip, self.fps, self.format = clip, self.fps or clip.fps, clip.format
                 return self._open_compressed(clip, clip.largest)
         if not (shutil.which("ffmpeg") and shutil.which("ffprobe")):
@@ -350,18 +333,16 @@ class ShaderVideo(ShaderModule):
     def _open_compressed(self, source: Iterator, largest: Optional[int]) -> Iterator:
         """A source of JPEG streams, or of PNG files (`format`): the clip's geometry and sampling are its first frame's"""
         import itertools
-        if self.format == "png":
-            from shaderflow_amd.pngsource import capacity_for, parse_header
-        else:
-            from shaderflow_amd.mjpegsource import capacity_for, parse_header
+        self.format = self.format or "mjpeg"
+        codec = CODECS[self.format]
         first = next(source, None)
         if first is None:
-            raise ValueError(f"{self.name}: a {'PNG' if self.format == 'png' else 'Motion-JPEG'} source without a frame")
-        self.jpeg = parse_header(first)
-        if (self.width and self.width != self.jpeg.width) or (self.height and self.height != self.jpeg.height):
-            raise ValueError(f"{self.name}: the frames are {self.jpeg.width} x {self.jpeg.height}, not {self.width} x {self.height}")
-        self.width, self.height, self.format = self.jpeg.width, self.jpeg.height, self.format or "mjpeg"
-        self.capacity = capacity_for(self.jpeg, largest)
+            raise ValueError(f"{self.name}: a {codec.TITLE} source without a frame")
+        self.header = codec.parse_header(first)
+        if (self.width and self.width != self.header.width) or (self.height and self.height != self.header.height):
+            raise ValueError(f"{self.name}: the frames are {self.header.width} x {self.header.height}, not {self.width} x {self.height}")
+        self.width, self.height = self.header.width, self.header.height
+        self.capacity = codec.capacity_for(self.header, largest)
         return itertools.chain([first], source)
 
     def update(self) -> None:
@@ -373,7 +354,7 @@ class ShaderVideo(ShaderModule):
             self._exhausted = True
             logger.warning(f"{self.name}: source ended after {self._read} frames, holding the last one")
             return
-        if self.format in ("mjpeg", "png"):
+        if self.format in CODECS:
             self._read += 1                                             # (a damaged frame is passed over: the next update() shows the next one)
             self._show_staged(frame, self._read - 1)
             return

@@ -1,5 +1,5 @@
 """
-Motion-JPEG sources on the device (csrc/jpeg_decode_kernels.hpp, csrc/capi_video.hip, shaderflow_amd/mjpegsource.py):
+Motion-JPEG sources on the device (csrc/jpeg_decode_kernels.hpp, csrc/capi_video_jpeg.hip, shaderflow_amd/mjpegsource.py):
 
   1. the kernels through sfx_jpeg_decode on every stored stream: the coefficients are tests/jpeg_ref.py's exactly; the planes are the
      float64 restatement's wherever the value in front of the rounding is more than 1e-3 from a tie, within 1 elsewhere; the RGB bytes

@@ -1,5 +1,5 @@
 """
-Motion-JPEG entropy decoding with a lane per subsequence (csrc/jpeg_decode_kernels.hpp, 1b; csrc/capi_video.hip) through the test entry
+Motion-JPEG entropy decoding with a lane per subsequence (csrc/jpeg_decode_kernels.hpp, 1b; csrc/capi_video_jpeg.hip) through the test entry
 sfx_jpeg_decode_sync (`mjpegsource.device_decode(sync=…)`), against the lane-per-interval kernel (`sfx_jpeg_decode`), value for value:
 
   1. every stored stream and a Pillow-written one without restart markers, at subsequences of 8, 16 and 64 bytes with the production
@@ -153,7 +153,7 @@ def test_an_avi_without_restart_markers_plays_the_same_on_both_paths(monkeypatch
             exports[sequence, path] = T.render(scene, 12)
             assert (scene.video_sequence is not None) == (sequence == "1")
             if sequence == "0":
-                sync, interval = scene.video._stage.jpeg_paths()
+                sync, interval = scene.video._stage.paths()
                 assert (sync > 0, interval > 0) == (path == "1", path == "0")
     assert len({frame.tobytes() for frame in exports["0", "0"]}) >= 10
     assert np.array_equal(exports["0", "1"], exports["0", "0"]) and np.array_equal(exports["1", "1"], exports["1", "0"])

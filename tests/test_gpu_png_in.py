@@ -1,5 +1,5 @@
 """
-PNG sources on the device (csrc/png_decode_kernels.hpp, csrc/capi_video.hip, shaderflow_amd/pngsource.py):
+PNG sources on the device (csrc/png_decode_kernels.hpp, csrc/capi_video_png.hip, shaderflow_amd/pngsource.py):
 
   1. the kernels through sfx_png_decode on every case of tests/png_decode_ref.py's table, on the serial path and, where the case
      allows, the segment path: the inflated stream is zlib.decompress's byte for byte, the pixels are Pillow's;
@@ -12,7 +12,8 @@ PNG sources on the device (csrc/png_decode_kernels.hpp, csrc/capi_video.hip, sha
   4. in the texture: a frame lands bottom-up, a temporal matrix rolls, a damaged frame is passed over, the three loops give the same
      bytes from `clip.avi` and from `bytes`, a short clip holds its last frame;
   5. the round trip: a scene exported with pixel_format="png" and its sound track, played back through a second scene, is the first
-     scene's frames exactly, every frame on the segment path.
+     scene's frames exactly, every frame on the segment path;
+  6. a PNG handle beside a Motion-JPEG handle: each decoder counts, reports and frees what is its own.
 """
 from __future__ import annotations
 
@@ -144,20 +145,19 @@ def test_a_staged_frame_is_validated_before_the_kernels_see_it():
 # ---- 4. in the texture -----------------------------------------------------------------------------------------------------------------
 
 class Stage:
-    """sfx_video_* with SFX_VIDEO_PNG over `temporal` bare RGB8 textures of the default context"""
+    """sfx_video_* with SFX_VIDEO_PNG (`codec`: another source module's format) over `temporal` bare RGB8 textures of the default context"""
 
-    def __init__(self, header, capacity, temporal=1, slots=2):
+    def __init__(self, header, capacity, temporal=1, slots=2, codec=None):
         from shaderflow_amd import _native as N
-        self.N, self.lib, self.header = N, N.lib(), header
+        from shaderflow_amd import pngsource
+        self.N, self.lib, self.header, self.codec = N, N.lib(), header, codec or pngsource
         self.context = N.default_context()
         self.textures = []
         for _ in range(temporal):
             handle = N.Handle()
             N.check(self.lib.sfx_texture_create(self.context.handle, header.width, header.height, 3, N.U8, C.byref(handle)))
             self.textures.append(handle)
-        self.handle = N.Handle()
-        boxes = (N.Handle*temporal)(*self.textures)
-        N.check(self.lib.sfx_video_create_png(self.context.handle, boxes, temporal, header.width, header.height, capacity, slots, C.byref(self.handle)))
+        self.handle = self.codec.create(self.context.handle, (N.Handle*temporal)(*self.textures), temporal, header, capacity, slots)
 
     def view(self, slot):
         pointer, nbytes = C.c_void_p(), C.c_size_t()
@@ -165,8 +165,7 @@ class Stage:
         return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(C.c_uint8)), shape=(nbytes.value,))
 
     def show(self, stream, slot=0):
-        from shaderflow_amd.pngsource import stage
-        self.N.check(self.lib.sfx_video_submit_bytes(self.handle, slot, stage(stream, self.header, self.view(slot))))
+        self.N.check(self.lib.sfx_video_submit_bytes(self.handle, slot, self.codec.stage(stream, self.header, self.view(slot))))
         self.N.check(self.lib.sfx_video_step(self.handle, slot))
 
     def bad(self, wait=True):
@@ -174,9 +173,9 @@ class Stage:
         self.N.check(self.lib.sfx_video_status(self.handle, 1 if wait else 0, C.byref(frame), C.byref(status)))
         return frame.value, status.value
 
-    def paths(self):
-        parallel, serial = C.c_uint64(), C.c_uint64()
-        self.N.check(self.lib.sfx_video_png_paths(self.handle, C.byref(parallel), C.byref(serial)))
+    def paths(self, entry="sfx_video_png_paths"):
+        parallel, serial = C.c_uint64(7), C.c_uint64(7)
+        self.N.check(getattr(self.lib, entry)(self.handle, C.byref(parallel), C.byref(serial)))
         return parallel.value, serial.value
 
     def read(self, index=0):
@@ -391,4 +390,40 @@ def test_an_exported_clip_played_back_is_the_first_scene(width, height, monkeypa
         scene.video.update()
         assert scene.video._read == k + 1
         assert np.array_equal(np.flipud(scene.video.texture.get_box().texture.read()), want[k]), f"source frame {k}"
-    assert scene.video._stage.png_paths() == (count, 0)               # every frame on the segment path, none fell back
+    assert scene.video._stage.paths() == (count, 0)               # every frame on the segment path, none fell back
+
+
+# ---- 6. two formats side by side ---------------------------------------------------------------------------------------------------------
+
+def test_a_png_and_a_motion_jpeg_handle_keep_to_their_own(monkeypatch):
+    """Each handle owns one decoder: frames landed alternately on a Motion-JPEG and a PNG handle are exact, each decoder counts its own
+    frames only, the other format's paths entry answers (0, 0), and destroying one handle frees only its decoder's scratch"""
+    import jpeg_ref as J
+    from shaderflow_amd import mjpegsource, pngsource
+    monkeypatch.delenv("SHADERFLOW_JPEG_SYNC", raising=False)
+    monkeypatch.delenv("SHADERFLOW_PNG_SEGMENTS", raising=False)
+    pictures = [D.mixed(37, 21, seed) for seed in range(4)]
+    pngs = [P.encode(picture) for picture in pictures]
+    assert pngs[0] == CASES["own-37x21"]["stream"]
+    jpegs = [J.encode(J.picture("noise", 48, 32, seed), 90) for seed in range(3)]
+    decoded = [mjpegsource.device_decode(stream, sync="auto") for stream in jpegs]      # the path a handle chooses, and its pixels
+    subsequence = sum(1 for got in decoded if got["sync"]["subsequences"])
+    headers = mjpegsource.parse_header(jpegs[0]), pngsource.parse_header(pngs[0])
+    jpeg = Stage(headers[0], mjpegsource.capacity_for(headers[0], max(map(len, jpegs))), slots=1, codec=mjpegsource)
+    png = Stage(headers[1], pngsource.capacity_for(headers[1], max(map(len, pngs))), slots=1)
+    try:
+        for k in range(3):
+            jpeg.show(jpegs[k])
+            png.show(pngs[k])
+            assert np.array_equal(jpeg.read(), np.flipud(decoded[k]["rgb"])) and np.array_equal(png.read(), np.flipud(pictures[k])), k
+        assert jpeg.paths("sfx_video_jpeg_paths") == (subsequence, 3 - subsequence) and png.paths() == (3, 0)
+        assert jpeg.paths("sfx_video_png_paths") == (0, 0) and png.paths("sfx_video_jpeg_paths") == (0, 0)
+        assert jpeg.bad() == (-1, 0) and png.bad() == (-1, 0)
+    finally:
+        jpeg.close()
+    try:
+        png.show(pngs[3])
+        assert np.array_equal(png.read(), np.flipud(pictures[3]))
+        assert png.bad() == (-1, 0) and png.paths() == (4, 0)
+    finally:
+        png.close()

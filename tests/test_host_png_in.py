@@ -170,6 +170,32 @@ def test_the_avi_reader_still_finds_mjpg(tmp_path):
         S.AviReader(tmp_path/"clip.avi")
 
 
+def test_one_walk_opens_an_avi_for_either_codec(tmp_path):
+    import jpeg_ref as J
+    from shaderflow_amd import mjpegsource
+    from shaderflow_amd.clips import AviClip
+    pngs = [P.encode(D.mixed(37, 21, seed)) for seed in range(4)]
+    jpegs = [J.encode(J.picture("noise", 48, 32, seed), 90) for seed in range(3)]
+    write_avi(tmp_path/"jpeg.avi", jpegs, 48, 32, 25.0, fourcc=b"MJPG")
+    write_avi(tmp_path/"png.avi", pngs, 37, 21, 30.0)
+    write_avi(tmp_path/"other.avi", pngs, 37, 21, 30.0, fourcc=b"H264")
+    codecs = (mjpegsource, S)
+    clip = AviClip(tmp_path/"jpeg.avi", codecs)
+    assert (clip.format, clip.width, clip.height, clip.fps, clip.sampling, clip.components) == ("mjpeg", 48, 32, 25.0, (2, 2), 3) and list(clip) == jpegs
+    clip = AviClip(tmp_path/"png.avi", codecs)
+    assert (clip.format, clip.width, clip.height, clip.fps, clip.largest) == ("png", 37, 21, 30.0, max(map(len, pngs))) and list(clip) == pngs
+    assert not hasattr(clip, "sampling")
+    descriptors = len(os.listdir("/proc/self/fd"))
+    with pytest.raises(LookupError, match="MJPG.*MPNG"):
+        AviClip(tmp_path/"other.avi", codecs)
+    assert len(os.listdir("/proc/self/fd")) == descriptors
+    # the failed open closed its file and its map: the path opens again, and may be written over
+    with pytest.raises(LookupError, match="MPNG"):
+        S.AviReader(tmp_path/"other.avi")
+    write_avi(tmp_path/"other.avi", pngs, 37, 21, 30.0)
+    assert list(AviClip(tmp_path/"other.avi", codecs)) == pngs
+
+
 def test_the_rule_that_chooses_the_segment_path(monkeypatch):
     monkeypatch.delenv("SHADERFLOW_PNG_SEGMENTS", raising=False)
     for name, case in CASES.items():
