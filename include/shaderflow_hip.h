@@ -209,6 +209,16 @@ int sfx_ring_sizes(sfx_handle ring, uint32_t* out, size_t capacity, size_t* coun
  * that has taken a frame already, a table that runs backwards or past `nbytes` — and, from the read that queues it, a frame beyond
  * the table's `count`. sfx_ring_sizes keeps its meaning (video payloads); no stream, event or queue is added. */
 int sfx_ring_side_track(sfx_handle ring, const void* bytes, size_t nbytes, const uint64_t* ends, size_t count);
+/* Segments for a sized ring with `framing` 1 (the RIFF chunks of an OpenDML AVI file): the ring's first chunk goes to byte `start` of
+ * the file, and no RIFF chunk of it is to span more than `budget` bytes. The writer asks the rule of csrc/ring_segments.hpp once per
+ * frame it writes, with the bytes the frame puts into the file (its chunk, and its side-track share's): where they would take the
+ * current segment past the budget, `gap_bytes` zero bytes go in front of the frame's chunk, in the same run of bytes — the place of
+ * `RIFF size AVIX LIST size movi`, which the file's writer patches when the sizes are known — and the next segment begins at the
+ * gap. A segment always takes at least one frame; a frame that is not written does not count. SFX_E_INVALID: a ring that is not sized
+ * or not framed, a ring that has taken a frame already, `budget` 0, `gap_bytes` above 64. No stream, event or queue is added. */
+int sfx_ring_segments(sfx_handle ring, uint64_t start, uint64_t budget, uint32_t gap_bytes);
+/* the frames in front of which a gap was written, in write order (indexes into sfx_ring_sizes' list); `out` may be null to ask for the count */
+int sfx_ring_segment_cuts(sfx_handle ring, uint32_t* out, size_t capacity, size_t* count);
 
 /* Encoder hand-off, optional half (exporting.py:94-134): `frames` RGB8 frames (consecutive, width*height*3 bytes each) on
  * the device → planar yuv420p (I420: Y, U, V; width*height*3/2 bytes each) on the device, on the context's stream. BT.601 limited

@@ -154,6 +154,8 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_ring_create_sized": (C.c_int, [Handle, C.c_size_t, C.c_int, C.c_int, P(Handle)]),
     "sfx_ring_sizes": (C.c_int, [Handle, P(C.c_uint32), C.c_size_t, P(C.c_size_t)]),
     "sfx_ring_side_track": (C.c_int, [Handle, C.c_void_p, C.c_size_t, P(C.c_uint64), C.c_size_t]),
+    "sfx_ring_segments": (C.c_int, [Handle, C.c_uint64, C.c_uint64, C.c_uint32]),
+    "sfx_ring_segment_cuts": (C.c_int, [Handle, P(C.c_uint32), C.c_size_t, P(C.c_size_t)]),
     "sfx_jpeg_create": (C.c_int, [Handle, C.c_int, C.c_int, C.c_int, P(Handle)]),
     "sfx_jpeg_destroy": (C.c_int, [Handle]),
     "sfx_jpeg_encode": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),

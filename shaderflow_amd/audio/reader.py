@@ -97,9 +97,15 @@ def read_flac(path: Path) -> tuple[np.ndarray, int]:
 
 def read_avi(path: Path) -> Optional[tuple[np.ndarray, int]]:
     """The first `auds` stream of a RIFF AVI 1.0 file, if it is PCM (what `scene.main(sound_track=…)` writes beside its Motion-JPEG
-    frames, and many cameras): its `NNwb` chunks of `movi`, `rec ` lists included, in file order. None: no audio stream, or a
-    compressed one — the caller's other decoders may know it."""
-    raw = Path(path).read_bytes()
+    frames, and many cameras): its `NNwb` chunks of `movi`, `rec ` lists included, in file order — and behind them those of the `movi`
+    lists of OpenDML `RIFF 'AVIX'` chunks, the same way. The file is read through a memory map: a file of gigabytes is not pulled
+    into memory for its few megabytes of PCM. None: no audio stream, or a compressed one — the caller's other decoders may know it."""
+    import mmap
+    with open(path, "rb") as file, mmap.mmap(file.fileno(), 0, access=mmap.ACCESS_READ) as raw:
+        return read_avi_map(raw, path)
+
+
+def read_avi_map(raw, path: Path) -> Optional[tuple[np.ndarray, int]]:
 
     def chunks(pos: int, end: int):
         while pos + 8 <= end:
@@ -107,8 +113,10 @@ def read_avi(path: Path) -> Optional[tuple[np.ndarray, int]]:
             yield tag, pos + 8, min(pos + 8 + size, end)
             pos += 8 + size + (size & 1)
 
-    stream, fmt, movi = None, None, None
+    stream, fmt, movi, extensions = None, None, None, []
     for tag, start, end in chunks(12, len(raw)):
+        if tag == b"RIFF" and raw[start:start + 4] == b"AVIX":
+            extensions += [(a + 4, b) for inner, a, b in chunks(start + 4, end) if inner == b"LIST" and raw[a:a + 4] == b"movi"]
         if tag != b"LIST":
             continue
         if raw[start:start + 4] == b"hdrl":
@@ -138,6 +146,8 @@ def read_avi(path: Path) -> Optional[tuple[np.ndarray, int]]:
             elif tag == wanted:
                 parts.append(raw[a:b])
     walk(*movi)
+    for extension in extensions:
+        walk(*extension)
     kind, channels, samplerate, _, _, bits = fmt
     pcm = pcm_to_float(b"".join(parts), kind, bits, path)
     frames = pcm.size//channels

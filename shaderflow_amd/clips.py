@@ -5,7 +5,8 @@ are is a codec's business — a module (mjpegsource.py, pngsource.py) with `FORM
 
   * `Clip`: frames as `bytes`, in order, with `width`, `height`, `fps`, `format`, `largest` (the largest frame's bytes: the slots'
     capacity), `index`, and `sampling` / `components` where the codec's header has them.
-  * `AviClip(path, codecs)`: RIFF AVI 1.0, walked once for whichever of the codecs the file holds.
+  * `AviClip(path, codecs)`: RIFF AVI 1.0 and its OpenDML extension (further `RIFF 'AVIX'` chunks: files past 4 GiB), walked once for
+    whichever of the codecs the file holds.
 """
 from __future__ import annotations
 
@@ -74,8 +75,12 @@ class AviClip(Clip):
     """RIFF AVI 1.0: `hdrl` (`strl`: `strh`, `strf`) and the `movi` list's `NNdc` / `NNdb` chunks of the first `vids` stream whose
     handler or compression is the FourCC of one of `codecs`, in either case — that codec is the clip's; `idx1` when it is there (and
     consistent), else a walk over `movi`. Audio and every other chunk are skipped. A chunk of this stream without bytes is a dropped
-    frame: the picture in front of it again, so the frames behind it keep their times (nothing, in front of the first picture). Frames
-    in OpenDML `AVIX` extensions are not read: a warning says so. No such stream: LookupError, the file closed."""
+    frame: the picture in front of it again, so the frames behind it keep their times (nothing, in front of the first picture).
+    OpenDML (what `opendml=` exports, ffmpeg and cameras write past a gigabyte or two): behind the first RIFF chunk every further
+    top-level `RIFF … 'AVIX'` chunk is read too — its `LIST 'movi'` walked for the stream's chunks, `rec ` lists included; `ix##`, `JUNK`
+    and everything else skipped; a last chunk cut short gives the frames that are whole; an `AVIX` chunk without a `movi` list is skipped
+    with a warning. The `indx` / `ix##` indexes are not consulted: a walk touches only chunk headers, and offsets are Python integers,
+    so a file past 4 GiB needs nothing special from the memory map. No such stream: LookupError, the file closed."""
 
     def add(self, offset: int, size: int) -> None:
         if size:
@@ -91,8 +96,6 @@ class AviClip(Clip):
         self.stream, streams, movi, idx1 = None, 0, None, None
         by_fourcc = {codec.FOURCC: codec for codec in codecs}
         end = min(len(data), 8 + struct.unpack("<I", data[4:8])[0])
-        if len(data) > end + 12 and data[end + (end & 1):end + (end & 1) + 4] == b"RIFF":
-            warnings.warn(f"{self.path}: frames in OpenDML extensions (RIFF AVIX) are not read: the clip ends with the first RIFF chunk", stacklevel=3)
 
         def chunks(first: int, last: int):
             pos = first
@@ -122,6 +125,15 @@ class AviClip(Clip):
                 movi = (at, size)
             elif fourcc == b"idx1":
                 idx1 = (at, size)
+        extensions, pos = [], end + (end & 1)                         # the `movi` lists of the OpenDML `RIFF 'AVIX'` chunks behind the first
+        while pos + 12 <= len(data) and data[pos:pos + 4] == b"RIFF":
+            stop = min(len(data), pos + 8 + struct.unpack("<I", data[pos + 4:pos + 8])[0])
+            if data[pos + 8:pos + 12] == b"AVIX":
+                found = [(at, size) for fourcc, at, size in chunks(pos + 12, stop) if fourcc == b"LIST" and data[at:at + 4] == b"movi"]
+                if not found:
+                    warnings.warn(f"{self.path}: the RIFF AVIX chunk at byte {pos} has no movi list: skipped", stacklevel=3)
+                extensions += found
+            pos = stop + (stop & 1)
         if self.stream is None:
             self.close()                                              # (the caller may open the file again, for other codecs)
             raise LookupError(f"{self.path}: no video stream with handler or compression {' or '.join(name.decode() for name in by_fourcc)}")
@@ -140,12 +152,15 @@ class AviClip(Clip):
                 if all(offset + size <= len(data) and bytes(data[offset - 8:offset - 4]) in names for offset, size in found):
                     for entry in found:                               # (else the index does not point at this stream's chunks: walk instead)
                         self.add(*entry)
+
+        def walk(first, last, whole=False):
+            for fourcc, at, size in chunks(first, last):
+                if fourcc == b"LIST" and data[at:at + 4] == b"rec ":
+                    walk(at + 4, at + size, whole)
+                elif fourcc in names and (not whole or size == struct.unpack("<I", data[at - 4:at])[0]):
+                    self.add(at, size)
         if not self.index:
-            def walk(first, last):
-                for fourcc, at, size in chunks(first, last):
-                    if fourcc == b"LIST" and data[at:at + 4] == b"rec ":
-                        walk(at + 4, at + size)
-                    elif fourcc in names:
-                        self.add(at, size)
             walk(movi[0] + 4, movi[0] + movi[1])
+        for at, size in extensions:                                   # (a chunk the file's end cuts short is no frame)
+            walk(at + 4, at + size, True)
         self.describe()

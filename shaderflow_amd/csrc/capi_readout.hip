@@ -4,6 +4,7 @@
 // textures, programs and the render dispatch, capi_audio.hip the audio plans and the tape.)
 
 #include "host_state.hpp"
+#include "ring_segments.hpp"
 
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -533,9 +534,14 @@ struct Ring : Object {
     const uint64_t* side_ends = nullptr;
     size_t side_count = 0;
     std::vector<long> slot_frame;                   // per slot: the number of the frame read into it (counted from the ring's first)
+    // segments (sfx_ring_segments; `framing` 1): the rule of ring_segments.hpp, asked once per written frame; at a cut the writer puts
+    // `segments.gap` zero bytes in front of the frame's chunk (the `RIFF AVIX LIST movi` header an OpenDML file's writer patches later)
+    RingSegments segments;
+    std::vector<uint32_t> cuts;                     // the written frames (counted as `sizes` counts them) in front of which a gap went
 };
 constexpr uint32_t SINK_MAGIC = 0x504a4653u;        // jpeg_kernels.hpp JPEG_SINK_MAGIC
 constexpr size_t SINK_HEADER = 64;
+constexpr uint32_t RING_GAP_MAX = 64;               // sfx_ring_segments: the most bytes of a gap
 
 static void ring_copier(Ring* r) {
     hipSetDevice(r->ctx->device);
@@ -614,16 +620,18 @@ static void ring_writer(Ring* r) {
             job = r->queue.front(); r->queue.pop_front();
             r->idle.wait(lock, [&] { return r->copying[job.first] == 0; });      // the frame has landed in the slot's host buffer
         }
-        // one run of bytes for write(): the frame, and behind it (a side track) the chunk header, the track's bytes and their pad byte
-        struct iovec run[4];
-        int parts = 1;
+        // one run of bytes for write(): in front (a segment cut) the gap, the frame, and behind it (a side track) the chunk header, the
+        // track's bytes and their pad byte
+        struct iovec gapped[5];
+        struct iovec* run = gapped + 1;
+        int parts = 1, part = 0;
         run[0].iov_base = r->host[job.first]; run[0].iov_len = r->frame_bytes;
         char side_head[8];
-        static const char zero = 0;
+        static const char zero = 0, gap_zeros[RING_GAP_MAX] = {0};
         if (r->sized) {
             // the framing goes into the header's last bytes, right in front of the payload
             uint32_t size; long frame;
-            { std::lock_guard<std::mutex> lock(r->mutex); size = r->payload[job.first]; frame = r->slot_frame[job.first]; if (size) r->sizes.push_back(size); }
+            { std::lock_guard<std::mutex> lock(r->mutex); size = r->payload[job.first]; frame = r->slot_frame[job.first]; }
             char* start = (char*)r->host[job.first] + SINK_HEADER;
             size_t left = size;
             if (size && r->framing == 1) {
@@ -643,11 +651,22 @@ static void ring_writer(Ring* r) {
                         parts = 4;
                     }
                 }
+                if (r->segments.budget) {
+                    uint64_t bytes = left;
+                    for (int k = 1; k < parts; k++) bytes += run[k].iov_len;
+                    if (r->segments.cut(bytes)) {
+                        std::lock_guard<std::mutex> lock(r->mutex);
+                        r->cuts.push_back((uint32_t)r->sizes.size());
+                        run[-1].iov_base = (void*)gap_zeros; run[-1].iov_len = (size_t)r->segments.gap;
+                        part = -1;
+                    }
+                }
             }
+            if (size) { std::lock_guard<std::mutex> lock(r->mutex); r->sizes.push_back(size); }
             run[0].iov_base = start; run[0].iov_len = left;
         }
         int err = 0;
-        for (int part = 0; part < parts && !err;) {
+        for (; part < parts && !err;) {
             if (run[part].iov_len == 0) { part++; continue; }
             ssize_t n = parts - part == 1 ? ::write(job.second, run[part].iov_base, run[part].iov_len) : ::writev(job.second, run + part, parts - part);
             if (n < 0) { if (errno == EINTR) continue; err = errno; break; }
@@ -722,6 +741,30 @@ extern "C" int sfx_ring_side_track(sfx_handle h, const void* bytes, size_t nbyte
     std::lock_guard<std::mutex> lock(r->mutex);
     if (r->frames_queued) return fail(SFX_E_INVALID, "side track: the ring has taken %ld frame(s) already", r->frames_queued);
     r->side_bytes = (const unsigned char*)bytes; r->side_ends = ends; r->side_count = count;
+    return SFX_OK;
+}
+
+// Segments for a sized ring with `framing` 1 (an OpenDML AVI file's RIFF chunks): the first chunk goes to byte `start` of the file, and
+// the writer thread, which alone knows what it has written, asks the rule of ring_segments.hpp once per frame it writes: where the
+// frame (with its side-track share) would take the current RIFF chunk past `budget` bytes it puts `gap_bytes` zero bytes in front of
+// the frame's chunk, in the same run of bytes. A frame that is not written does not count.
+extern "C" int sfx_ring_segments(sfx_handle h, uint64_t start, uint64_t budget, uint32_t gap_bytes) {
+    Ring* r = get<Ring>(h, MAGIC_RING);
+    if (!r || !r->sized || r->framing != 1) return fail(SFX_E_INVALID, "segments need a sized ring with framing 1");
+    if (!budget || gap_bytes > RING_GAP_MAX) return fail(SFX_E_INVALID, "segments of %llu bytes with gaps of %u (a budget above 0, gaps of %u bytes at the most)", (unsigned long long)budget, gap_bytes, RING_GAP_MAX);
+    std::lock_guard<std::mutex> lock(r->mutex);
+    if (r->frames_queued) return fail(SFX_E_INVALID, "segments: the ring has taken %ld frame(s) already", r->frames_queued);
+    r->segments.begin(start, budget, gap_bytes);
+    return SFX_OK;
+}
+
+// the written frames in front of which a gap went, in write order: indexes into sfx_ring_sizes' list
+extern "C" int sfx_ring_segment_cuts(sfx_handle h, uint32_t* out, size_t capacity, size_t* count) {
+    Ring* r = get<Ring>(h, MAGIC_RING);
+    if (!r || !r->sized || !count) return fail(SFX_E_INVALID, "invalid ring handle, not a sized ring, or null count");
+    std::lock_guard<std::mutex> lock(r->mutex);
+    *count = r->cuts.size();
+    if (out) memcpy(out, r->cuts.data(), sizeof(uint32_t)*std::min(capacity, r->cuts.size()));
     return SFX_OK;
 }
 

@@ -75,6 +75,13 @@ class ExportingHelper:
     behind the frame (sfx_ring_side_track): it alone orders the bytes on the sink's descriptor, in all three loops."""
     _track: Optional[mjpeg.SoundTrack] = None
     _track_ends: Optional[np.ndarray] = None   # the ring borrows it (and the track's pcm) until it is destroyed
+    opendml: Any = None
+    """An mjpeg or png export to `.avi` is written as OpenDML (AVI 2.0: `RIFF 'AVIX'` segments behind the first RIFF chunk, 64-bit `indx` /
+    `ix##` indexes; mjpeg.py states the file), which holds exports past AVI 1.0's 4 GiB: True — segments of 1 GiB — or the segment size
+    in bytes (4 096 … 2^31). The ring's writer thread leaves the gap in front of a segment's first frame (sfx_ring_segments), next to
+    the side track's rule and for the same reason. None, False: the AVI 1.0 file, byte for byte as before."""
+    _budget: Optional[int] = None              # the checked segment size of an OpenDML export
+    _cuts: list = Factory(list)                # the frames in front of which the ring's writer left a gap (sfx_ring_segment_cuts)
 
     # ring
     ring: Optional[N.Handle] = None
@@ -213,6 +220,23 @@ class ExportingHelper:
         reader = chosen[0]._file_reader
         return mjpeg.SoundTrack(reader.samples, reader.samplerate)
 
+    @property
+    def wants_opendml(self) -> bool:
+        return self.opendml is not None and self.opendml is not False
+
+    def find_budget(self) -> int:
+        """The segment size `opendml` asks for; ValueError when the export is no `.avi` file of an mjpeg or png export, or the size is out of range"""
+        rule = "opendml goes with an '.avi' file of a Motion-JPEG or PNG export (output='clip.avi', pixel_format='mjpeg' or 'png')"
+        if not self.sized:
+            raise ValueError(f"{rule}, not pixel_format {self.pixel_format!r}")
+        if self.kind == "pipe" or self.container != "avi":
+            raise ValueError(f"{rule}: {'a pipe' if self.kind == 'pipe' else repr(self.path.suffix)} delivers the bare {'PNG' if self.png else 'JPEG'} images back to back, without a limit")
+        return mjpeg.check_opendml(self.opendml)
+
+    def avi_writer(self, fileno: Optional[int]) -> mjpeg.AviWriter:
+        return mjpeg.AviWriter(fileno, self.scene.width, self.scene.height, self.scene.fps, track=self._track,
+                               fourcc=b"MPNG" if self.png else b"MJPG", opendml=self._budget)
+
     def ffmpeg_output(self, output) -> None:
         if self.sized:
             if (output in ("pipe", "-", bytes)):
@@ -223,6 +247,8 @@ class ExportingHelper:
                 self.kind = "path-mjpeg"
             if self.wants_track:
                 self._track = self.find_track()
+            if self.wants_opendml:
+                self._budget = self.find_budget()
             if self.path is not None:
                 self.path.parent.mkdir(parents=True, exist_ok=True)
             if self.top_down is None:
@@ -230,6 +256,8 @@ class ExportingHelper:
             return
         if self.wants_track:
             self.find_track()
+        if self.wants_opendml:
+            self.find_budget()
         if (output in ("pipe", "-", bytes)):
             self.kind = "pipe"
             self.ffmpeg.pipe_output()
@@ -272,8 +300,7 @@ class ExportingHelper:
             self.file = open(self.path, "wb", buffering=0)
             self.fileno = self.file.fileno()
             if self.container == "avi":
-                self._avi = mjpeg.AviWriter(self.fileno, self.scene.width, self.scene.height, self.scene.fps, track=self._track,
-                                            fourcc=b"MPNG" if self.png else b"MJPG")
+                self._avi = self.avi_writer(self.fileno)
                 self._avi.begin()
         elif self.kind == "pipe":
             self.file = tempfile.TemporaryFile(mode="w+b")
@@ -293,6 +320,8 @@ class ExportingHelper:
             self._track_ends = self._track.ends(self.total_frames, self.scene.fps)
             N.check(N.lib().sfx_ring_side_track(handle, self._track.pcm.ctypes.data, self._track.pcm.nbytes,
                                                 N.as_ptr(self._track_ends, C.c_uint64), len(self._track_ends)))
+        if self._budget is not None:                          # (the headers' size is fixed once opendml and the track are known)
+            N.check(N.lib().sfx_ring_segments(handle, len(self.avi_writer(None).headers(0, 0, 0, 0)), self._budget, mjpeg.GAP_BYTES))
         if self.staged:
             self._yuv_slots = [self.scene.context.alloc(self.frame_bytes) for _ in range(self.slots)]
 
@@ -309,6 +338,10 @@ class ExportingHelper:
                     sizes = (C.c_uint32*max(1, count.value))()
                     N.check(N.lib().sfx_ring_sizes(self.ring, sizes, count.value, C.byref(count)))
                     self._sizes += list(sizes[:count.value])
+                    N.check(N.lib().sfx_ring_segment_cuts(self.ring, None, 0, C.byref(count)))
+                    cuts = (C.c_uint32*max(1, count.value))()
+                    N.check(N.lib().sfx_ring_segment_cuts(self.ring, cuts, count.value, C.byref(count)))
+                    self._cuts += list(cuts[:count.value])
                 N.lib().sfx_ring_destroy(self.ring)
             for pointer in self._yuv_slots:
                 self.scene.context.free(pointer)

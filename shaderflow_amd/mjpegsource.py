@@ -1,7 +1,7 @@
 """
 Motion-JPEG sources of a ShaderVideo, read without ffmpeg: the containers this package writes (mjpeg.py) read back, and the same from
-other encoders — `.avi` (RIFF AVI 1.0 with an `MJPG` video stream) and `.mjpeg` / `.mjpg` (JPEG images back to back). The frames stay
-compressed on the host and over the link; the device decodes them where the texture lives (csrc/jpeg_decode_kernels.hpp defines the
+other encoders — `.avi` (RIFF AVI 1.0, or OpenDML with its `AVIX` segments, with an `MJPG` video stream) and `.mjpeg` / `.mjpg` (JPEG
+images back to back). The frames stay compressed on the host and over the link; the device decodes them where the texture lives (csrc/jpeg_decode_kernels.hpp defines the
 decode, `sfx_jpeg_frame` of include/shaderflow_hip.h the layout of a staged frame, mirrored here as `STAGED`).
 
   * `parse_header(stream)`: a frame's marker segments up to its scan → `JpegHeader` (geometry, sampling, tables, where the scan
@@ -301,7 +301,7 @@ class RawReader(Clip):
 
 
 class AviReader(AviClip):
-    """RIFF AVI 1.0 with an `MJPG` video stream (handler or compression, in either case): one JPEG stream per chunk"""
+    """RIFF AVI (1.0, or OpenDML with its `AVIX` segments) with an `MJPG` video stream (handler or compression, in either case): one JPEG stream per chunk"""
 
     def __init__(self, path: Path):
         super().__init__(path, (sys.modules[__name__],))

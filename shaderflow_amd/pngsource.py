@@ -1,6 +1,7 @@
 """
-PNG sources of a ShaderVideo, read without ffmpeg: the `MPNG` `.avi` files `pixel_format="png"` writes (mjpeg.py has the container)
-read back, the same from other writers, and PNG files handed over as `bytes`. The frames stay compressed on the host and over the
+PNG sources of a ShaderVideo, read without ffmpeg: the `MPNG` `.avi` files `pixel_format="png"` writes (mjpeg.py has the container;
+its OpenDML form, `opendml=`, included: clips.py walks the `AVIX` segments of a file past 4 GiB) read back, the same from other
+writers, and PNG files handed over as `bytes`. The frames stay compressed on the host and over the
 link; the device inflates and unfilters them where the texture lives (csrc/png_decode_kernels.hpp defines the decode,
 `sfx_png_frame` of include/shaderflow_hip.h the layout of a staged frame, mirrored here as `STAGED`).
 
@@ -196,7 +197,7 @@ def describe_status(status: int) -> str:
 
 
 class AviReader(AviClip):
-    """RIFF AVI 1.0 with an `MPNG` video stream (handler or compression, in either case): one PNG file per chunk"""
+    """RIFF AVI (1.0, or OpenDML with its `AVIX` segments) with an `MPNG` video stream (handler or compression, in either case): one PNG file per chunk"""
 
     def __init__(self, path: Path):
         super().__init__(path, (sys.modules[__name__],))

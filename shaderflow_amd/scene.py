@@ -318,6 +318,7 @@ class ShaderScene(ShaderModule):
         pixel_format: Optional[str] = None,
         jpeg_quality: int = 90,
         sound_track: Any = False,
+        opendml: Any = None,
     ) -> Optional[Union[Path, bytes]]:
         """Render the scene to `output` (scene.py:493-639). `output` may be a path (raw rgb24 frames, or a video
         when an `ffmpeg` binary exists), "pipe"/"-"/bytes (returns the raw frames), or None with freewheel=True
@@ -329,7 +330,9 @@ class ShaderScene(ShaderModule):
         JPEG frames encoded on the device at `jpeg_quality` (1…100) into `.avi`, `.mjpeg` or "pipe", no ffmpeg (ExportingHelper.jpeg_quality) — or "png":
         lossless, every frame a complete PNG file encoded on the device, into `.avi` (fourcc MPNG) or "pipe", no ffmpeg (ExportingHelper.png).
         `sound_track`: an mjpeg or png export to `.avi` carries the scene's sound as a PCM stream — True (the scene's one ShaderAudio with a loaded clip), that
-        module, or its name (ExportingHelper.sound_track; mjpeg.py states the stream)."""
+        module, or its name (ExportingHelper.sound_track; mjpeg.py states the stream).
+        `opendml`: an mjpeg or png export to `.avi` is written as OpenDML (AVI 2.0), which holds exports past AVI 1.0's 4 GiB — True (segments of
+        1 GiB) or the segment size in bytes (ExportingHelper.opendml; mjpeg.py states the file)."""
         self.initialize()
         self.exporting = (bool(output))
         self.freewheel = (self.exporting or freewheel)
@@ -363,7 +366,9 @@ class ShaderScene(ShaderModule):
             self.ssaa = ssaa
 
         export = ExportingHelper(self, top_down=top_down, pixel_format=(pixel_format or os.environ.get("SHADERFLOW_PIXEL_FORMAT") or "rgb24"),
-                                 jpeg_quality=jpeg_quality, sound_track=sound_track)
+                                 jpeg_quality=jpeg_quality, sound_track=sound_track, opendml=opendml)
+        if export.wants_opendml and not self.exporting:
+            raise ValueError("opendml goes with an '.avi' file of a Motion-JPEG or PNG export (output='clip.avi', pixel_format='mjpeg' or 'png'): there is no output")
         if export.wants_track and not self.exporting:
             raise ValueError("sound_track goes into an '.avi' file of a Motion-JPEG export (output='clip.avi', pixel_format='mjpeg'): there is no output")
         if self.exporting and export.sized and (is_sharded() or shard is not None):

@@ -21,7 +21,9 @@ Where frames come from: the reference pipes the file through an `ffmpeg` subproc
     and are decoded on the device into the texture (csrc/jpeg_decode_kernels.hpp: baseline, 8 bit, one interleaved scan, 4:2:0 /
     4:2:2 / 4:4:4 / grey; anything else raises ValueError naming the marker or field). With `format="mjpeg"`, `frames=` yields such
     streams as `bytes`. A frame whose entropy-coded data is damaged raises RuntimeError naming the source frame; it is not drawn. A
-    stream without restart markers is cut into subsequences that decode in parallel (DESIGN.md §7c): entropy decoding on the host is out of scope;
+    stream without restart markers is cut into subsequences that decode in parallel: entropy decoding on the host is out of scope.
+    An `.avi` that continues in OpenDML `RIFF 'AVIX'` segments (what `opendml=` exports, and large captures: files past 4 GiB) is read to
+    its end, for this codec and the next (clips.py);
   * `path=` an `.avi` file with a PNG video stream (fourcc `MPNG`: what `pixel_format="png"` exports), read natively (pngsource.py): the
     PNG files stay compressed in pinned memory and over the link and are inflated and unfiltered on the device into the texture,
     bit-exactly (csrc/png_decode_kernels.hpp: 8-bit RGB without interlace; anything else raises ValueError naming the IHDR field; chunk

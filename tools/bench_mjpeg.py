@@ -8,6 +8,10 @@ Writes profiles/mjpeg_bench.txt. GPU box only.
 `--sound-track`: the sound-track leg alone — the same export at quality 90 to an `.avi` file (memory-backed where /dev/shm exists: an
 AVI is seeked and truncated, /dev/null will not do), with and without `sound_track=True`, taking turns, three runs each after one
 unmeasured run of both. Its lines are APPENDED to profiles/mjpeg_bench.txt.
+
+`--opendml [BYTES]`: the OpenDML leg alone, measured the same way — the `.avi` export at quality 90 with and without `opendml=BYTES`
+(64 MiB by default, so that a 900-frame export of about half a gigabyte is cut several times: the default segment of 1 GiB would never
+be reached, and the writer thread's comparison runs per frame either way). Its lines are APPENDED to profiles/mjpeg_bench.txt.
 """
 import argparse
 import csv
@@ -65,6 +69,43 @@ def sound_track_leg(frames: int) -> list[str]:
     return lines
 
 
+def opendml_leg(frames: int, budget: int) -> list[str]:
+    """frames/s of the `.avi` export with and without `opendml=budget`, run in turns in this process"""
+    from shaderflow_amd import _native as N
+    from shaderflow_amd.clips import AviClip
+    from shaderflow_amd import mjpegsource
+    rates: dict = {False: [], True: []}
+    sizes: dict = {}
+    counts: dict = {}
+    where = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    with tempfile.TemporaryDirectory(dir=where) as directory:
+        for run in range(4):                                            # the first of each is not measured
+            for segmented in (False, True):
+                path = Path(directory)/"clip.avi"
+                took, _ = export("mjpeg", 90, frames, path, opendml=budget if segmented else None)
+                sizes[segmented] = path.stat().st_size
+                if run == 3:
+                    clip = AviClip(path, (mjpegsource,))
+                    counts[segmented] = (len(clip), path.read_bytes().count(b"AVIX"))
+                    clip.close()
+                path.unlink()
+                if run:
+                    rates[segmented].append(frames/took)
+                    print(f"run {run} {'with' if segmented else 'without'} opendml: {frames/took:7.0f} frames/s", flush=True)
+    without, with_segments = rates[False], rates[True]
+    spread = max(without) - min(without)
+    mean = (lambda values: sum(values)/len(values))
+    lines = [f"opendml: mjpeg q90 to an .avi file in {where or 'the temporary directory'}, {frames} frames, segments of {budget} bytes, "
+             f"three runs each in turns after one unmeasured run of both, kernel sources {N.source_fingerprint()}",
+             f"  without opendml: {', '.join(f'{r:.0f}' for r in without)} frames/s (mean {mean(without):.0f}, spread {spread:.0f}), {sizes[False]} bytes, "
+             f"{counts[False][0]} frames read back",
+             f"  with opendml   : {', '.join(f'{r:.0f}' for r in with_segments)} frames/s (mean {mean(with_segments):.0f}), {sizes[True]} bytes, "
+             f"{counts[True][0]} frames read back from {counts[True][1] + 1} RIFF chunks",
+             f"  mean with - mean without = {mean(with_segments) - mean(without):+.0f} frames/s: "
+             + ("within" if mean(without) - mean(with_segments) <= spread else "BELOW the AVI 1.0 runs by more than") + " the spread among the runs without opendml"]
+    return lines
+
+
 def kernel_times(quality: int, frames: int) -> list[str]:
     """rocprofv3's per-kernel statistics of a short mjpeg export in a fresh process: the lines of the JPEG kernels"""
     rocprof = shutil.which("rocprofv3")
@@ -93,7 +134,15 @@ def main() -> None:
     parser.add_argument("--child", type=int, default=None, help="(internal) one mjpeg export at this quality, nothing else")
     parser.add_argument("--no-profile", action="store_true")
     parser.add_argument("--sound-track", action="store_true", help="the sound-track leg alone, appended to profiles/mjpeg_bench.txt")
+    parser.add_argument("--opendml", type=int, nargs="?", const=64 << 20, default=None, metavar="BYTES",
+                        help="the OpenDML leg alone (segments of BYTES, 64 MiB by default), appended to profiles/mjpeg_bench.txt")
     args = parser.parse_args()
+    if args.opendml is not None:
+        lines = opendml_leg(args.frames, args.opendml)
+        with open(ROOT/"profiles"/"mjpeg_bench.txt", "a") as file:
+            file.write("\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     if args.sound_track:
         lines = sound_track_leg(args.frames)
         with open(ROOT/"profiles"/"mjpeg_bench.txt", "a") as file:

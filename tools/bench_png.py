@@ -7,6 +7,10 @@ three PNG kernels' times. Writes profiles/png_bench.txt. GPU box only.
 
 rgb24 goes to /dev/null. mjpeg and png go to an `.avi` file (memory-backed where /dev/shm exists): an AVI is seeked and truncated,
 /dev/null will not do, and png has no other file container. AVI 1.0 holds 4 GiB, which bounds --frames for png at 4K.
+
+`--opendml`: one export past 4 GiB alone — png with `opendml=True` (segments of 1 GiB), `--frames` of them (900 are about 4.55 GB) — then
+the file read back: the frames `clips.AviClip` finds, the last one's offset, the RIFF chunks, and tests/odml_ref.py over the whole
+file. The file is deleted afterwards; its lines are APPENDED to profiles/png_bench.txt. `--directory` says where it goes.
 """
 import argparse
 import csv
@@ -37,6 +41,37 @@ def export(pixel_format: str, frames: int, output) -> float:
     return time.perf_counter() - started
 
 
+def opendml_leg(frames: int, directory) -> list[str]:
+    import mmap
+
+    from shaderflow_amd import _native as N
+    from shaderflow_amd import pngsource
+    from tests import odml_ref
+    with tempfile.TemporaryDirectory(dir=directory) as folder:
+        free = shutil.disk_usage(folder).free
+        need = frames*N.PngEncoder.capacity(W, H)//4                     # (a frame is about a fifth of its capacity)
+        if free < need:
+            return [f"opendml: no room for {frames} png frames in {folder}: {free} bytes free, about {need} needed: not run"]
+        path = Path(folder)/"clip.avi"
+        started = time.perf_counter()
+        visualizer().main(width=W, height=H, ssaa=SSAA, fps=FPS, time=frames/FPS, output=path, pixel_format="png", opendml=True)
+        took = time.perf_counter() - started
+        size = path.stat().st_size
+        clip = pngsource.AviReader(path)
+        count, last, largest = len(clip), clip.index[-1], clip.largest
+        clip.close()
+        with open(path, "rb") as file, mmap.mmap(file.fileno(), 0, access=mmap.ACCESS_READ) as data:
+            avi = odml_ref.parse(data)
+            walked = avi["walk"][b"00dc"]
+            spans = odml_ref.spans(avi)
+        path.unlink()
+    return [f"opendml: png to an .avi file in {folder.rsplit('/', 1)[0]}, {frames} frames, segments of 1 GiB, kernel sources {N.source_fingerprint()}",
+            f"  {size} bytes ({size/2**32:.3f} x 4 GiB) in {took:.2f} s = {frames/took:.0f} frames/s (one run), {size/frames:.0f} bytes per frame, the largest {largest}",
+            f"  AviClip: {count} frames, the last at byte {last[0]} ({last[1]} bytes){', past 2^32' if last[0] > 1 << 32 else ''}",
+            f"  odml_ref: valid; {len(spans)} RIFF chunks of {', '.join(str(span) for span in spans)} bytes; {len(walked)} frames by walk and by index, "
+            f"the same places as AviClip's: {walked == clip.index}"]
+
+
 def kernel_times(frames: int) -> list[str]:
     """rocprofv3's per-kernel statistics of a short png export in a fresh process: the lines of the PNG kernels"""
     rocprof = shutil.which("rocprofv3")
@@ -65,7 +100,15 @@ def main() -> None:
     parser.add_argument("--rounds", type=int, default=3, help="turns of rgb24, mjpeg, png; the first is not measured")
     parser.add_argument("--child", action="store_true", help="(internal) one png export, nothing else")
     parser.add_argument("--no-profile", action="store_true")
+    parser.add_argument("--opendml", action="store_true", help="one png export past 4 GiB with opendml=True, read back; appended to profiles/png_bench.txt")
+    parser.add_argument("--directory", default=None, help="where --opendml's file goes (the temporary directory by default)")
     args = parser.parse_args()
+    if args.opendml:
+        lines = opendml_leg(args.frames, args.directory)
+        with open(ROOT/"profiles"/"png_bench.txt", "a") as file:
+            file.write("\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     shm = "/dev/shm" if os.path.isdir("/dev/shm") else None
     if args.child:
         with tempfile.TemporaryDirectory(dir=shm) as directory:
