@@ -250,6 +250,34 @@ class Bloom(ShaderScene):
         self.shader.fragment = self.FRAGMENT
 
 
+class Glow(ShaderScene):
+    """The cheap glow of Shadertoy-style fragments: the picture's own mip chain is the blur. `mipmaps=True` builds the chain on the
+    device, `textureLod(background, uv, k)` reads level k — each a picture blurred twice as wide as the one before — and the bright
+    parts of levels 1 … 5 are summed over the image. The image itself is softened by a 3 x 3 box of `textureOffset` taps (whole
+    texels of the level the lookup selects — here, under a chain, the level the pixel's own footprint asks for; the loop of taps
+    earns the sampler an LDS tile, which a mipmapped texture bypasses: the draw takes the code object's untiled twin)."""
+    background: Optional[np.ndarray] = None
+    FRAGMENT = """
+        uniform float iGlow = 0.7;
+        void main() {
+            vec3 image = vec3(0);
+            for (int x = -1; x <= 1; x++)
+                for (int y = -1; y <= 1; y++)
+                    image += textureOffset(background, astuv, ivec2(x, y)).rgb/9.0;
+            vec3 glow = vec3(0);
+            for (int k = 1; k <= 5; k++)
+                glow += max(textureLod(background, astuv, float(k)).rgb - 0.45, 0.0)/5.0;
+            fragColor = vec4(image + iGlow*(1.5 + sin(iTime))*glow, 1);
+        }
+    """
+
+    def build(self):
+        super().build()
+        image = self.background if self.background is not None else synth.background_image(640, 360)
+        self.back = ShaderTexture(scene=self, name="background", mipmaps=True).from_numpy(image)
+        self.back.repeat(True)                                        # applies the sampler state: builds the chain of the picture
+        self.shader.fragment = self.FRAGMENT
+
 
 class AudioTrails(_AudioScene):
     """Audio-reactive trails (not one of the reference's): a fragment of its own, translated at run time, with two layers and four

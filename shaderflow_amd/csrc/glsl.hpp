@@ -146,6 +146,30 @@ SF_HD float bilerp(float w00, float w10, float w01, float w11, float t00, float 
 // k_render<dynamics> at 1080p: 0.19 → 1.17 ms)
 #define SF_COLD static __host__ __device__ __attribute__((noinline))
 SF_COLD vec4 texture_mipmapped(Tex t, vec2 uv);      // by value: a reference would pin every caller's Tex in scratch memory
+// the NEAREST / LINEAR filter on the texture as it stands (one level), the texel coordinates moved by (dx, dy) before they wrap:
+// texture() below with the offset of textureOffset (GLSL 3.30 section 8.7). Two bodies on purpose — texture() written as
+// texture_plain(t, uv, 0, 0) gives the same bits but cost every kernel that samples three VGPRs (tools/jit_register_table.py).
+SF_HD vec4 texture_plain(const Tex& t, vec2 uv, int dx, int dy) {
+    float u = uv.x*(float)t.width;
+    float v = uv.y*(float)t.height;
+    if (t.filter == FILTER_NEAREST) {
+        int i = wrap_texel((int)::floorf(u) + dx, t.width, t.repeat_x);
+        int j = wrap_texel((int)::floorf(v) + dy, t.height, t.repeat_y);
+        return texel(t, i, j);
+    }
+    float ub = u - 0.5f, vb = v - 0.5f;
+    float fu = ::floorf(ub), fv = ::floorf(vb);
+    float a = ub - fu, b = vb - fv;
+    int i0 = wrap_texel((int)fu + dx, t.width, t.repeat_x), i1 = wrap_texel((int)fu + 1 + dx, t.width, t.repeat_x);
+    int j0 = wrap_texel((int)fv + dy, t.height, t.repeat_y), j1 = wrap_texel((int)fv + 1 + dy, t.height, t.repeat_y);
+    vec4 t00 = texel(t, i0, j0), t10 = texel(t, i1, j0), t01 = texel(t, i0, j1), t11 = texel(t, i1, j1);
+    float na = 1.0f - a, nb = 1.0f - b;
+    float w00 = na*nb, w10 = a*nb, w01 = na*b, w11 = a*b;
+    return {bilerp(w00, w10, w01, w11, t00.x, t10.x, t01.x, t11.x),
+            bilerp(w00, w10, w01, w11, t00.y, t10.y, t01.y, t11.y),
+            bilerp(w00, w10, w01, w11, t00.z, t10.z, t01.z, t11.z),
+            bilerp(w00, w10, w01, w11, t00.w, t10.w, t01.w, t11.w)};
+}
 SF_HD vec4 texture(const Tex& t, vec2 uv) {       // GLSL texture(sampler2D, vec2)
     if (__builtin_expect(t.filter >= FILTER_LINEAR_MIPMAP, 0)) return texture_mipmapped(t, uv);
     float u = uv.x*(float)t.width;
@@ -199,12 +223,17 @@ SF_HD vec4 texture_level(const Tex& t, vec2 uv, int level, int filter) {
     v.filter = filter;
     return texture(v, uv);
 }
-SF_HD float mip_lambda(const Tex& t, float dudx, float dvdx, float dudy, float dvdy) {
+SF_HD float mip_lambda_base(float dudx, float dvdx, float dudy, float dvdy) {       // not clamped: a bias is added to this
     const float along_x = dudx*dudx + dvdx*dvdx, along_y = dudy*dudy + dvdy*dvdy;
     const float rho2 = along_x > along_y ? along_x : along_y;
-    const float lambda = 0.5f*sf::log2(rho2);                        // log2(rho); rho2 = 0 (a constant coordinate) gives -inf: magnification
+    return 0.5f*sf::log2(rho2);                                      // log2(rho); rho2 = 0 (a constant coordinate) gives -inf: magnification
+}
+SF_HD float mip_lambda_clamp(const Tex& t, float lambda) {
     const float top = (float)((t.levels > 1 ? t.levels : 1) - 1);
     return lambda > top ? top : lambda;
+}
+SF_HD float mip_lambda(const Tex& t, float dudx, float dvdx, float dudy, float dvdy) {
+    return mip_lambda_clamp(t, mip_lambda_base(dudx, dvdx, dudy, dvdy));
 }
 // ---- the fixed-point filter model (opt-in, sfx_ctx_filter_model) ---------------------------------------------------------------------
 // OpenGL leaves the precision of the bilinear weights to the implementation (>= 4 subtexel bits, 3.3 core section 3.8.11). The float
@@ -215,11 +244,11 @@ SF_HD float mip_lambda(const Tex& t, float dudx, float dvdx, float dudy, float d
 // the parity oracle keeps the checker's copy). With the model on, frames meet that implementation's within 1 LSB where
 // the float weights leave up to 1.3 % of the values 2 off (a second filter or a quantisation after the first: tests/test_gpu_mesa.py).
 SF_HD int fixed8_lerp(int w, int a, int b) { return (a + ((w*(b - a) + 128) >> 8)) & 255; }
-SF_COLD vec4 texture_fixed8(Tex t, vec2 uv) {
+SF_HD vec4 texture_fixed8_at(const Tex& t, vec2 uv, int dx, int dy) {      // (dx, dy): textureOffset's, added before the wrap
     const int fx = (int)::rintf(uv.x*(float)t.width*256.0f) - 128, fy = (int)::rintf(uv.y*(float)t.height*256.0f) - 128;
     const int wx = fx & 255, wy = fy & 255;
-    const int i0 = wrap_texel(fx >> 8, t.width, t.repeat_x), i1 = wrap_texel((fx >> 8) + 1, t.width, t.repeat_x);
-    const int j0 = wrap_texel(fy >> 8, t.height, t.repeat_y), j1 = wrap_texel((fy >> 8) + 1, t.height, t.repeat_y);
+    const int i0 = wrap_texel((fx >> 8) + dx, t.width, t.repeat_x), i1 = wrap_texel((fx >> 8) + 1 + dx, t.width, t.repeat_x);
+    const int j0 = wrap_texel((fy >> 8) + dy, t.height, t.repeat_y), j1 = wrap_texel((fy >> 8) + 1 + dy, t.height, t.repeat_y);
     const uint8_t* data = (const uint8_t*)t.data;
     const int n = t.components;
     const uint8_t* p00 = data + ((size_t)j0*t.width + i0)*n; const uint8_t* p10 = data + ((size_t)j0*t.width + i1)*n;
@@ -231,7 +260,13 @@ SF_COLD vec4 texture_fixed8(Tex t, vec2 uv) {
     if (n > 3) c.w = channel(3);
     return c;
 }
+SF_COLD vec4 texture_fixed8(Tex t, vec2 uv) { return texture_fixed8_at(t, uv, 0, 0); }
 
+// (texture(s, uv)'s own statement of the level rule, older than texture_at_lambda below, which restates it for every other form:
+// texture_mipmapped is texture_at_lambda at lambda_base, bias 0, offset 0. Kept as a body of its own because it is part of every kernel
+// that samples, the library's included: as a call into texture_at_lambda those kernels compile to other code — one to two VGPRs fewer
+// and no scratch by tools/jit_register_table.py — and "the kernels that existed compile to what they compiled to" was this change's
+// bar. tests/test_gpu_texture.py holds the two bodies to the same bits: texture = textureGrad of the quad's differences.)
 SF_COLD vec4 texture_mipmapped(Tex t, vec2 uv) {
     if (t.filter == FILTER_LINEAR_FIXED8) return texture_fixed8(t, uv);            // (shares the cold entry: one rare branch in texture())
     const float u = uv.x*(float)t.width, v = uv.y*(float)t.height;
@@ -245,6 +280,65 @@ SF_COLD vec4 texture_mipmapped(Tex t, vec2 uv) {
     if (d2 == d1 || f == 0.0f) return a;
     const vec4 b = texture_level(t, uv, d2, FILTER_LINEAR);
     return {fmaf(f, b.x - a.x, a.x), fmaf(f, b.y - a.y, a.y), fmaf(f, b.z - a.z, a.z), fmaf(f, b.w - a.w, a.w)};
+}
+
+// ---- the lookups with an explicit level of detail, a bias, gradients and offsets (GLSL 3.30 section 8.7) --------------------------------
+// THE RULES (normative; csrc/jit_runtime.hpp declares the functions, tests/texture_ref.py restates these lines in exact arithmetic):
+//   levels   L = t.levels where a chain is attached (t.mips, t.levels > 1), else 1; top = L - 1.
+//   lambda   textureLod:        lambda = lod.
+//            texture(.., bias): lambda = lambda_base + bias, lambda_base = 0.5*log2(rho^2) of the quad differences (mip_lambda_base,
+//                               NOT clamped before the bias is added; -inf for a constant coordinate stays -inf).
+//            textureGrad:       rho^2 from dPdx*(width, height) and dPdy*(width, height) (3.8.11: du/dx = w ds/dx), then as above.
+//            lambda is then clamped to top from above (a NaN selects level 0).
+//   level    only LINEAR_MIPMAP / NEAREST_MIPMAP with L > 1 select one: lambda <= 0 -> the plain filter on level 0;
+//            LINEAR_MIPMAP_LINEAR -> a = level floor(lambda), b = level floor(lambda) + 1 (bilinear each), fmaf(f, b - a, a) with
+//            f = lambda - floor(lambda), b skipped where f = 0 or floor(lambda) = top; NEAREST_MIPMAP_NEAREST -> the nearest texel of
+//            level ceil(lambda + 0.5) - 1. NEAREST / LINEAR (with or without a chain: minification and magnification coincide) and
+//            L = 1 read level 0 with the plain filter whatever lambda is. LINEAR_FIXED8 (the checker's filter model) reads level 0.
+//   offset   the integer offset is added to the texel coordinates of the SELECTED level before they wrap: (int)fu + d and
+//            (int)fu + 1 + d in the linear filter, (int)floorf(u) + d in the nearest one; both levels of a blend get the same d, each
+//            in its own texels. Any int is taken (two's complement addition); GL guarantees -8 ... 7 only.
+//   fetch    texelFetch(s, p, lod) reads texel p of level lod; lod outside [0, top] reads (0, 0, 0, 0), as p outside the level does
+//            (this project's rule: GL leaves both undefined). textureSize(s, lod) = max(1, w >> lod) x max(1, h >> lod), lod clamped
+//            to [0, top].
+//   proj     textureProj*: P.xy / P.z (or P.w), the correctly rounded quotient, then the form without Proj.
+// Everything below the entry points is out of line (SF_COLD), like texture_mipmapped: a fragment that never meets a chain pays a call
+// it does not take.
+SF_HD int chain_levels(const Tex& t) { return (t.levels > 1 && t.mips) ? t.levels : 1; }
+SF_HD vec4 texture_level(const Tex& t, vec2 uv, int level, int filter, int dx, int dy) {
+    Tex v = mip_level(t, level);
+    v.filter = filter;
+    return texture_plain(v, uv, dx, dy);
+}
+SF_HD vec4 texture_at_lambda(const Tex& t, vec2 uv, float lambda, int dx, int dy) {
+    if (t.filter == FILTER_LINEAR_FIXED8) return texture_fixed8_at(t, uv, dx, dy);
+    const bool linear = (t.filter == FILTER_LINEAR || t.filter == FILTER_LINEAR_MIPMAP);
+    const int plain = linear ? FILTER_LINEAR : FILTER_NEAREST, levels = chain_levels(t);
+    const float top = (float)(levels - 1);
+    lambda = lambda > top ? top : lambda;
+    if (t.filter < FILTER_LINEAR_MIPMAP || levels <= 1 || !(lambda > 0.0f)) return texture_level(t, uv, 0, plain, dx, dy);
+    if (!linear) return texture_level(t, uv, (int)::ceilf(lambda + 0.5f) - 1, FILTER_NEAREST, dx, dy);
+    const float below = ::floorf(lambda), f = lambda - below;
+    const int d1 = (int)below;
+    const vec4 a = texture_level(t, uv, d1, FILTER_LINEAR, dx, dy);
+    if (d1 + 1 >= levels || f == 0.0f) return a;
+    const vec4 b = texture_level(t, uv, d1 + 1, FILTER_LINEAR, dx, dy);
+    return {fmaf(f, b.x - a.x, a.x), fmaf(f, b.y - a.y, a.y), fmaf(f, b.z - a.z, a.z), fmaf(f, b.w - a.w, a.w)};
+}
+SF_COLD vec4 texture_lod(Tex t, vec2 uv, float lod, int dx, int dy) { return texture_at_lambda(t, uv, lod, dx, dy); }
+SF_COLD vec4 texture_bias(Tex t, vec2 uv, float bias, int dx, int dy) {            // implicit derivatives: every lane of the quad calls it
+    const float u = uv.x*(float)t.width, v = uv.y*(float)t.height;
+    return texture_at_lambda(t, uv, mip_lambda_base(quad_dx(u), quad_dx(v), quad_dy(u), quad_dy(v)) + bias, dx, dy);
+}
+SF_COLD vec4 texture_grad(Tex t, vec2 uv, vec2 dpdx, vec2 dpdy, int dx, int dy) {
+    const float w = (float)t.width, h = (float)t.height;
+    return texture_at_lambda(t, uv, mip_lambda_base(dpdx.x*w, dpdx.y*h, dpdy.x*w, dpdy.y*h), dx, dy);
+}
+// texture() moved by an offset: the plain filters in line (a blur's taps), a mipmapped texture by its implicit derivatives
+SF_HD vec4 texture_offset(const Tex& t, vec2 uv, int dx, int dy) {
+    // (GLSL wants the offset a constant expression: with a literal (0, 0) — texture() through the LDS tile — only texture_mipmapped is left)
+    if (__builtin_expect(t.filter >= FILTER_LINEAR_MIPMAP, 0)) return (dx | dy) ? texture_bias(t, uv, 0.0f, dx, dy) : texture_mipmapped(t, uv);
+    return texture_plain(t, uv, dx, dy);
 }
 
 // texture(t, uv).xy for fragments that read two components only: the same operations as texture() on .x and .y
@@ -274,11 +368,22 @@ SF_HD vec2 texture_xy(const Tex& t, vec2 uv) {
     return {bilerp(w00, w10, w01, w11, t00.x, t10.x, t01.x, t11.x), bilerp(w00, w10, w01, w11, t00.y, t10.y, t01.y, t11.y)};
 }
 
-// texelFetch(sampler, ivec2, 0). Out-of-range coordinates are undefined in GL 3.3 (§3.8.9); with robust buffer
+// texelFetch(sampler, ivec2, lod). Out-of-range coordinates are undefined in GL 3.3 (§3.8.9); with robust buffer
 // access — what desktop drivers do in practice — the fetch returns zeros, and that is the rule here.
 SF_HD vec4 texel_fetch(const Tex& t, int i, int j) {
     if ((unsigned)i >= (unsigned)t.width || (unsigned)j >= (unsigned)t.height) return {0.0f, 0.0f, 0.0f, 0.0f};
     return texel(t, i, j);
+}
+
+SF_COLD vec4 texel_fetch_level(Tex t, int i, int j, int lod) {
+    if ((unsigned)lod >= (unsigned)chain_levels(t)) return {0.0f, 0.0f, 0.0f, 0.0f};
+    return texel_fetch(mip_level(t, lod), i, j);
+}
+SF_HD void level_size(const Tex& t, int lod, int& w, int& h) {      // textureSize(sampler, lod)
+    const int top = chain_levels(t) - 1;
+    lod = lod < 0 ? 0 : (lod > top ? top : lod);
+    w = (t.width >> lod) > 1 ? (t.width >> lod) : 1;
+    h = (t.height >> lod) > 1 ? (t.height >> lod) : 1;
 }
 
 // Colour write to a unorm8 target (OpenGL 3.3 §2.1.6 / §4.1): clamp to [0, 1] (NaN -> 0), scale by 255, round half to even.

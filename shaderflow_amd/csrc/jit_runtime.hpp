@@ -625,25 +625,27 @@ SF_HD sf::vec2 lo(const vec2& c) { return {c.x, c.y}; }
 SF_HD sf::vec3 lo(const vec3& c) { return {c.x, c.y, c.z}; }
 // an unbound sampler reads as opaque black texels, like an incomplete GL texture
 SF_HD int tile_bound(float texel) { return (int)sf::min(sf::max(texel, -16777216.0f), 16777216.0f); }
-SF_HD sf::vec4 tiled_texture(const Tex& t, const TileView& v, sf::vec2 uv) {      // sf::texture (glsl.hpp) with the texel fetch swapped
-    if (t.filter >= FILTER_LINEAR_MIPMAP) return sf::texture(t, uv);       // mipmapped: the tile holds level 0 only
+SF_HD int tile_bound(int offset) { return offset < -16777216 ? -16777216 : (offset > 16777216 ? 16777216 : offset); }
+// sf::texture_offset (glsl.hpp) with the texel fetch swapped; (dx, dy) is textureOffset's, (0, 0) for texture()
+SF_HD sf::vec4 tiled_texture(const Tex& t, const TileView& v, sf::vec2 uv, int dx = 0, int dy = 0) {
+    if (t.filter >= FILTER_LINEAR_MIPMAP) return sf::texture_offset(t, uv, dx, dy);      // mipmapped: the tile holds level 0 only
     const float u = uv.x*(float)t.width, w = uv.y*(float)t.height;
     const bool nearest = t.filter == FILTER_NEAREST;
     const float ub = nearest ? u : u - 0.5f, vb = nearest ? w : w - 0.5f;
     const float fu = ::floorf(ub), fv = ::floorf(vb);
     if (v.record) {
-        const int i = tile_bound(fu), j = tile_bound(fv), far = nearest ? 0 : 1;
+        const int i = tile_bound(fu) + tile_bound(dx), j = tile_bound(fv) + tile_bound(dy), far = nearest ? 0 : 1;      // the box widens by the offset
         int* box = v.record;
         if (i < box[0]) box[0] = i;
         if (j < box[1]) box[1] = j;
         if (i + far > box[2]) box[2] = i + far;
         if (j + far > box[3]) box[3] = j + far;
-        return sf::texture(t, uv);
+        return sf::texture_offset(t, uv, dx, dy);
     }
-    const unsigned rx = (unsigned)(int)fu - (unsigned)v.x0, ry = (unsigned)(int)fv - (unsigned)v.y0;
+    const unsigned rx = (unsigned)(int)fu + (unsigned)dx - (unsigned)v.x0, ry = (unsigned)(int)fv + (unsigned)dy - (unsigned)v.y0;
     if (nearest) {
         if (rx < v.nearest_w && ry < v.nearest_h) { const float4 c = v.texels[ry*(unsigned)v.w + rx]; return {c.x, c.y, c.z, c.w}; }
-        return sf::texture(t, uv);
+        return sf::texture_offset(t, uv, dx, dy);
     }
     if (rx < v.linear_w && ry < v.linear_h) {
         const float4* p = v.texels + (ry*(unsigned)v.w + rx);
@@ -656,17 +658,63 @@ SF_HD sf::vec4 tiled_texture(const Tex& t, const TileView& v, sf::vec2 uv) {    
                 bilerp(w00, w10, w01, w11, t00.z, t10.z, t01.z, t11.z),
                 bilerp(w00, w10, w01, w11, t00.w, t10.w, t01.w, t11.w)};
     }
-    return sf::texture(t, uv);
+    return sf::texture_offset(t, uv, dx, dy);
 }
 SF_HD vec4 texture(sampler2D s, const vec2& uv) {
     if (!(s.t && s.t->data)) return vec4(0.0f, 0.0f, 0.0f, 1.0f);
     if (s.tile.texels) return up(tiled_texture(*s.t, s.tile, lo(uv)));
     return up(sf::texture(*s.t, lo(uv)));
 }
-SF_HD vec4 texture(sampler2D s, const vec2& uv, float) { return texture(s, uv); }          // one level: the bias selects nothing
-SF_HD vec4 textureLod(sampler2D s, const vec2& uv, float) { return texture(s, uv); }
-SF_HD vec4 texelFetch(sampler2D s, ivec2 p, int) { return (s.t && s.t->data) ? up(sf::texel_fetch(*s.t, p.x, p.y)) : vec4(0.0f, 0.0f, 0.0f, 1.0f); }
-SF_HD ivec2 textureSize(sampler2D s, int) { return (s.t && s.t->data) ? ivec2(s.t->width, s.t->height) : ivec2(1, 1); }
+// The rest of the sampler2D column of the §8.7 table. glsl.hpp states the rules ("THE RULES": level selection, offsets, fetches,
+// projection) and keeps everything that meets a chain, a bias or a gradient out of line; what stays in line here is the plain
+// filter on level 0 — from the tile where the sampler has one — which is all a texture without a chain can select.
+SF_HD bool bound(const sampler2D& s) { return s.t && s.t->data; }
+SF_HD bool mipmapped(const sampler2D& s) { return __builtin_expect(s.t->filter >= FILTER_LINEAR_MIPMAP, 0); }
+SF_HD vec4 unbound_texel() { return vec4(0.0f, 0.0f, 0.0f, 1.0f); }
+SF_HD sf::vec4 tap(const sampler2D& s, const vec2& uv, const ivec2& o) {      // level 0 (mipmapped: by the implicit derivatives) moved by o
+    return s.tile.texels ? tiled_texture(*s.t, s.tile, lo(uv), o.x, o.y) : sf::texture_offset(*s.t, lo(uv), o.x, o.y);
+}
+SF_HD vec2 projected(const vec3& p) { return vec2(p.x/p.z, p.y/p.z); }
+SF_HD vec2 projected(const vec4& p) { return vec2(p.x/p.w, p.y/p.w); }
+SF_HD vec4 textureOffset(sampler2D s, const vec2& uv, ivec2 o) { return bound(s) ? up(tap(s, uv, o)) : unbound_texel(); }
+SF_HD vec4 textureOffset(sampler2D s, const vec2& uv, ivec2 o, float bias) {
+    if (!bound(s)) return unbound_texel();
+    return up(mipmapped(s) ? sf::texture_bias(*s.t, lo(uv), bias, o.x, o.y) : tap(s, uv, o));
+}
+SF_HD vec4 textureLodOffset(sampler2D s, const vec2& uv, float lod, ivec2 o) {
+    if (!bound(s)) return unbound_texel();
+    return up(mipmapped(s) ? sf::texture_lod(*s.t, lo(uv), lod, o.x, o.y) : tap(s, uv, o));
+}
+SF_HD vec4 textureGradOffset(sampler2D s, const vec2& uv, const vec2& dPdx, const vec2& dPdy, ivec2 o) {
+    if (!bound(s)) return unbound_texel();
+    return up(mipmapped(s) ? sf::texture_grad(*s.t, lo(uv), lo(dPdx), lo(dPdy), o.x, o.y) : tap(s, uv, o));
+}
+SF_HD vec4 texture(sampler2D s, const vec2& uv, float bias) { return textureOffset(s, uv, ivec2(0, 0), bias); }
+SF_HD vec4 textureLod(sampler2D s, const vec2& uv, float lod) { return textureLodOffset(s, uv, lod, ivec2(0, 0)); }
+SF_HD vec4 textureGrad(sampler2D s, const vec2& uv, const vec2& dPdx, const vec2& dPdy) { return textureGradOffset(s, uv, dPdx, dPdy, ivec2(0, 0)); }
+#define SF_RT_PROJ(P) \
+    SF_HD vec4 textureProj(sampler2D s, const P& p) { return texture(s, projected(p)); } \
+    SF_HD vec4 textureProj(sampler2D s, const P& p, float bias) { return texture(s, projected(p), bias); } \
+    SF_HD vec4 textureProjOffset(sampler2D s, const P& p, ivec2 o) { return textureOffset(s, projected(p), o); } \
+    SF_HD vec4 textureProjOffset(sampler2D s, const P& p, ivec2 o, float bias) { return textureOffset(s, projected(p), o, bias); } \
+    SF_HD vec4 textureProjLod(sampler2D s, const P& p, float lod) { return textureLod(s, projected(p), lod); } \
+    SF_HD vec4 textureProjLodOffset(sampler2D s, const P& p, float lod, ivec2 o) { return textureLodOffset(s, projected(p), lod, o); } \
+    SF_HD vec4 textureProjGrad(sampler2D s, const P& p, const vec2& dPdx, const vec2& dPdy) { return textureGrad(s, projected(p), dPdx, dPdy); } \
+    SF_HD vec4 textureProjGradOffset(sampler2D s, const P& p, const vec2& dPdx, const vec2& dPdy, ivec2 o) { return textureGradOffset(s, projected(p), dPdx, dPdy, o); }
+SF_RT_PROJ(vec3) SF_RT_PROJ(vec4)
+// level 0 is the texture itself: a literal 0, as nearly every fragment writes it, leaves nothing of the other branch
+SF_HD vec4 texelFetch(sampler2D s, ivec2 p, int lod) {
+    if (!bound(s)) return unbound_texel();
+    return up((lod == 0) ? sf::texel_fetch(*s.t, p.x, p.y) : sf::texel_fetch_level(*s.t, p.x, p.y, lod));
+}
+SF_HD vec4 texelFetchOffset(sampler2D s, ivec2 p, int lod, ivec2 o) { return texelFetch(s, ivec2(p.x + o.x, p.y + o.y), lod); }
+SF_HD ivec2 textureSize(sampler2D s, int lod) {
+    if (!bound(s)) return ivec2(1, 1);
+    if (lod == 0) return ivec2(s.t->width, s.t->height);
+    int w, h;
+    sf::level_size(*s.t, lod, w, h);
+    return ivec2(w, h);
+}
 
 // ---- prelude: include/shaderflow.glsl ---------------------------------------------------------------------------------
 constexpr float SQRT2 = 1.4142135623730951f, SQRT3 = 1.7320508075688772f, SQRT5 = 2.2360679774997898f;     // :7-11 (PI, TAU: sfmath.hpp)
@@ -1024,6 +1072,10 @@ inline void sfx_jit_host_user(sf::Uniforms* u, int slot, const void* words, int 
 inline void sfx_jit_host_texture(sf::Tex* textures, int slot, const void* data, int width, int height, int components, int dtype, int filter, int repeat_x, int repeat_y) {
     textures[slot] = sf::Tex{data, width, height, components, dtype, filter, repeat_x, repeat_y};
 }
+// a chain (levels 1 … levels-1, packed as glsl.hpp mip_level reads them) and any FILTER_* for a texture already set
+inline void sfx_jit_host_texture_mips(sf::Tex* textures, int slot, const void* mips, int levels, int filter) {
+    textures[slot].mips = mips; textures[slot].levels = levels; textures[slot].filter = filter;
+}
 }
 #define SF_JIT_HOST_POINTS(FRAGMENT) \
     extern "C" void sfx_jit_host_render(const sf::Uniforms* u, const sf::Tex* textures, int wr, int hr, unsigned* rgba8) { \
@@ -1046,7 +1098,8 @@ inline void sfx_jit_host_texture(sf::Tex* textures, int slot, const void* data, 
         } \
     } \
     extern "C" void* sfx_jit_host_keep[] = {(void*)sfx_jit_host_uniforms_size, (void*)sfx_jit_host_textures_size, (void*)sfx_jit_host_defaults, \
-                                            (void*)sfx_jit_host_uniform, (void*)sfx_jit_host_user, (void*)sfx_jit_host_texture};
+                                            (void*)sfx_jit_host_uniform, (void*)sfx_jit_host_user, (void*)sfx_jit_host_texture, \
+                                            (void*)sfx_jit_host_texture_mips};
 #else
 #define SF_JIT_HOST_POINTS(FRAGMENT)
 #endif

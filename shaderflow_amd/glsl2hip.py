@@ -8,7 +8,8 @@ with `opengl.program`, falling back to `missing.glsl` on errors). Without a driv
    `sf::rt::FragmentBase` (csrc/jit_runtime.hpp): globals and uniforms become members, functions become member
    functions, `main` becomes `main_`. GLSL and C++ share almost all of their expression and statement syntax; the
    header supplies the vector types (with swizzles), the built-in functions on the deterministic binary32 routines of
-   csrc/sfmath.hpp and the reference's prelude, so what is rewritten is small:
+   csrc/sfmath.hpp, the whole sampler2D column of the §8.7 texture lookups (explicit lod, bias, gradients, offsets, projection,
+   fetches of any level: csrc/glsl.hpp "THE RULES") and the reference's prelude, so what is rewritten is small:
      * floating literals get an `f` suffix (C++ would compute in double),
      * `in/out/inout` parameter qualifiers become values and references, precision/layout/interpolation qualifiers go,
      * `uniform`/`in`/`out` declarations go (the members exist already), prototypes go,
@@ -592,7 +593,8 @@ class _Translator:
         return Translation(cpp, bindings, tiled.name if tiled else None)
 
 
-_TEXTURE_CALLS = r"(?:texture|textureLod|gtexture|gmtexture|stexture|astexture|agtexture|agmtexture)"
+# the lookups the tile can serve: level 0 with the plain filter, moved by an offset or not (jit_runtime.hpp tiled_texture)
+_TEXTURE_CALLS = r"(?:texture|textureLod|textureOffset|textureLodOffset|textureProj|textureProjOffset|gtexture|gmtexture|stexture|astexture|agtexture|agmtexture)"
 
 
 def _closing_in_text(code: str, at: int, opening: str, closing: str) -> int:
@@ -629,7 +631,10 @@ def _sampler_worth_a_tile(code: str, samplers: list[Binding]) -> Optional[Bindin
     written out), or None. SHADERFLOW_JIT_TILE=0 turns the tile off, =<sampler name> forces it for that sampler.
 
     The tile costs one extra evaluation of the fragment per block (jit_runtime.hpp JitShader::setup) and never changes a
-    result, so the choice is about speed only: a single tap does not pay for the probe."""
+    result, so the choice is about speed only: a single tap does not pay for the probe. Taps are `texture` and the prelude's
+    helpers, `textureOffset` (a blur written with offsets: the recorded box widens by them), `textureProj[Offset]`, and
+    `textureLod[Offset]` — on a texture without a chain a lod selects nothing and the tap is served from the tile; on a mipmapped
+    one every lookup bypasses it (the tile holds level 0 only)."""
     wish = os.environ.get("SHADERFLOW_JIT_TILE", "1")
     if wish.lower() in ("0", "off", "false", "no"):
         return None
