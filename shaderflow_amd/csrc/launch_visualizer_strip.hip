@@ -32,7 +32,8 @@ static int launch_visualizer_tables_and_kernel(Context* ctx, const RenderArgs& a
     t.cell_bytes = HALF ? 8 : 48;                                     // float16 cells in three planes where the lanes of a wave read different cells (visualizer_fast.hpp)
     const size_t entries = (size_t)frames*((size_t)a.wr + a.hr)*VIS_ENTRY_QUADS*sizeof(float4);
     const size_t blocks = (size_t)frames*((size_t)t.blocks_x + t.blocks_y)*sizeof(int4);
-    const size_t ysteps = STRIP_S ? (size_t)frames*a.hr*10*sizeof(float4) : 0;
+    // (+ WALK - 1 rows: a strip's rows are loaded at immediate offsets from its first one, past the frame's last row too)
+    const size_t ysteps = STRIP_S ? ((size_t)frames*a.hr + (WALK - 1))*10*sizeof(float4) : 0;
     // the pixel tier (visualizer_fast.hpp visualizer_pixel_gains): fused 2x / 4x launches whose bars come as a table; SHADERFLOW_VIS_PIXEL_TIER=0
     // turns it off (A/B measurements, and the tests that compare the two tiers)
     const Tex& sp = a.tex[TEX_SPECTROGRAM];

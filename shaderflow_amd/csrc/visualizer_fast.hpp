@@ -39,7 +39,7 @@ struct VisTables {
     float4* rows;                        // [frame][hr][VIS_ENTRY_QUADS]
     int4* block_x;                       // [frame][blocks_x] = { x0, tw, fits, 0 }: window of background cells of a block column
     int4* block_y;                       // [frame][blocks_y] = { y0, th, fits, 0 }
-    float4* ysteps;                      // [frame][hr][10] = { frac(y+), frac(y-), row bytes(y+), row bytes(y-) } of the diagonal taps' walk steps; may be null
+    float4* ysteps;                      // [frame][hr][10] = { y*(y+), y*(y-), row bytes(y+), row bytes(y-) } of the diagonal taps' walk steps (frac = r - y*; float16 cells: the fractions themselves); may be null
     int blocks_x, blocks_y;              // blocks per row / column of the sample grid
     int block_columns, block_rows;       // samples per block along x / y
     int tile_pitch, tile_rows;           // LDS tile the offsets are computed for (cells)
@@ -165,9 +165,12 @@ __device__ __forceinline__ void visualizer_axis_entry(const RenderArgs& a, const
         e[1] = make_float4(c.rot_s*uv, c.rot_c*uv, uv*uv, ag*ag);
         e[2] = make_float4(vignette, 1.0f - g, 1.0f + g, 0.0f);   // :72-73 compare these with the waveform
         if (t.ysteps) {
-            // The y half of a diagonal tap — fraction and row of cells of y +- k*s (VisualizerShader::blur_tile's walk) — depends
+            // The y half of a diagonal tap — row of cells and fraction of y +- k*s (VisualizerShader::blur_tile's walk) — depends
             // on the sample ROW and the walk step only: 10 entries per row instead of eight instructions per tap quadruple of
-            // every sample, and wave-uniform for a wave whose lanes share their rows
+            // every sample, and wave-uniform for a wave whose lanes share their rows. For the float32-cell instances the fraction is
+            // carried as y* = the cell row's coordinate minus (plus) the displacement: frac(y +- d) = r - y*, and y* is THE SAME for
+            // every sample row whose tap lands in that row of cells (floor(r +- d) and d are) — what lets the strip kernel keep one
+            // running pair per walk step for both sides (VisualizerStrip::SHARED_SIDES)
             const float dstep = (a.tap_x[11] - a.tap_x[10])*ax, dfirst = a.tap_x[10]*ax;
             const float row_bytes = (float)(t.tile_pitch*t.cell_bytes);
             float4* ys = t.ysteps + ((long)frame*n + k)*10;
@@ -175,7 +178,8 @@ __device__ __forceinline__ void visualizer_axis_entry(const RenderArgs& a, const
                 const float d = fmaf((float)w, dstep, dfirst);
                 const float yp = r + d, ym = r - d;
                 const float ayp = __builtin_amdgcn_fractf(yp), aym = __builtin_amdgcn_fractf(ym);
-                ys[w] = make_float4(ayp, aym, __int_as_float((int)((yp - ayp)*row_bytes)), __int_as_float((int)((ym - aym)*row_bytes)));
+                const bool shared_sides = t.cell_bytes != 8;            // VisualizerStrip::SHARED_SIDES: y* for the float32-cell instances, the fractions themselves for the float16 ones
+                ys[w] = make_float4(shared_sides ? (yp - ayp) - d : ayp, shared_sides ? (ym - aym) + d : aym, __int_as_float((int)((yp - ayp)*row_bytes)), __int_as_float((int)((ym - aym)*row_bytes)));
             }
         }
     }
@@ -684,6 +688,12 @@ struct VisualizerStrip {
     static constexpr int PLANE = HALF ? TILE_ROWS*TILE_PITCH*8 : 16;   // bytes between the three quads of one cell
     static_assert(2*PLANE < 65536, "the planes are reached through ds_read's 16-bit immediate offset");
     static constexpr int ROWBYTES = TILE_PITCH*CELL;
+    // The diagonal walk. Float32 cells (samples a quarter of a texel apart and closer: long runs of rows inside one row of cells): ONE
+    // running pair for both y sides of a walk step, and k_visualizer_axes' walk-step table carries y* (visualizer_axis_entry). The
+    // float16-cell instances (0.4 texel per sample and more, strips of one to six rows: a fold at every second row or oftener) keep an
+    // accumulation per side and the fractions in the table — measured: 1080p at 2x 32.52 -> 32.72 ms, without SSAA 16.10 -> 16.87 ms per
+    // 300 frames with the shared form (profiles/r08_strip_diagonal_sides.txt)
+    static constexpr bool SHARED_SIDES = !HALF;
     __device__ __forceinline__ static void load_cell(const char* p, Quad& q0, Quad& q1, Quad& q2) {
         q0 = *(const Quad*)p; q1 = *(const Quad*)(p + PLANE); q2 = *(const Quad*)(p + 2*PLANE);
     }
@@ -927,34 +937,36 @@ struct VisualizerStrip {
             {
                 const float ax = c.intensity*a.bg_scale_x*(float)bg.width;
                 const float step = (a.tap_x[11] - a.tap_x[10])*ax, first = a.tap_x[10]*ax;
-                const float4* ysteps[WALK];
+                typedef float pk2 __attribute__((ext_vector_type(2)));
+                // ONE pointer per table and the rows at immediate offsets (the scalar registers are as scarce as the vector ones here). The
+                // wave's rows r < `rows` exist; behind them the loads meet the next frame's entries or, in the last frame, what follows the
+                // table (its padding, launch_visualizer_strip.hip) — fetched and never used
+                const long entry = (long)frame*a.hr + (jr0 < a.hr ? jr0 : a.hr - 1);
+                const float4* ysteps = t.ysteps + entry*10;
+                const float* row_r = (const float*)(t.rows + entry*VIS_ENTRY_QUADS);
+                pk2 Y[(WALK + 1)/2];                                  // the rows' texel coordinates Y_r, two rows to a scalar pair
 #pragma unroll
-                for (int r = 0; r < WALK; r++) {
-                    const int jr = jr0 + r;
-                    ysteps[r] = t.ysteps + ((long)frame*a.hr + (jr < a.hr ? jr : a.hr - 1))*10;
+                for (int r = 0; r < WALK; r += 2) Y[r/2] = pk2{row_r[r*VIS_ENTRY_QUADS*4], row_r[(r + 1 < WALK ? r + 1 : r)*VIS_ENTRY_QUADS*4]};
+                [[maybe_unused]] const float4* ysteps_of[WALK];       // (the instances that accumulate side by side: a pointer per row)
+                if constexpr (!SHARED_SIDES) {
+#pragma unroll
+                    for (int r = 0; r < WALK; r++) {
+                        const int jr = jr0 + r;
+                        ysteps_of[r] = t.ysteps + ((long)frame*a.hr + (jr < a.hr ? jr : a.hr - 1))*10;
+                    }
                 }
                 float xp = xr + first, xm = xr - first;
 #pragma unroll 1
                 for (int w = 0; w < 10; w++) {
                     const float axp = __builtin_amdgcn_fractf(xp), axm = __builtin_amdgcn_fractf(xm);
                     const int cxp = (int)((xp - axp)*(float)CELL), cxm = (int)((xm - axm)*(float)CELL);
-                    float4 y[WALK];
-#pragma unroll
-                    for (int r = 0; r < WALK; r++) y[r] = ysteps[r][w];   // { frac(y+), frac(y-), row bytes(y+), row bytes(y-) }
-                    float U[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}}, V[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-                    int previous[2] = {-2*ROWBYTES, -2*ROWBYTES};     // (no row of cells: neither equal nor adjacent to a real one)
-                    // both y sides of a walk step advance row by row together (their first cells are fetched at once)
-                    auto advance = [&](int r, int side) {
-                        const int cell_row = __float_as_int(side ? y[r].w : y[r].z);
-                        // (a walk step's first row folds without asking — it always does: `previous` starts at no row — so that the compiler drops
-                        // the thirteen v_mov 0 that initialised U and V for the path nobody takes)
-                        if (r == 0 || cell_row != previous[side]) {
-                            previous[side] = cell_row;
+                    // a row of cells folded with the step's two x fractions: U = (A + ax*B)(x+) + (A + ax*B)(x-), V = (C + ax*D)(x+) + (C + ax*D)(x-)
+                    auto fold = [&](int cell_row, float (&u)[3], float (&v)[3]) {
+                        {
                             SF_COUNT_FOLD();
                             Quad p0, p1, p2, m0, m1, m2;
                             load_cell(tile + (cxp + cell_row), p0, p1, p2);
                             load_cell(tile + (cxm + cell_row), m0, m1, m2);
-                            float* u = U[side]; float* v = V[side];
                             if constexpr (HALF) {
                                 // the sums of two components are exact in float16: packed adds, two per instruction
                                 const Quad s0 = p0 + m0, s1 = p1 + m1, s2 = p2 + m2;
@@ -970,10 +982,27 @@ struct VisualizerStrip {
                             v[0] = fmaf(axp, F(p2.y), v[0]);  v[1] = fmaf(axp, F(p2.z), v[1]);  v[2] = fmaf(axp, F(p2.w), v[2]);
                             v[0] = fmaf(axm, F(m2.y), v[0]);  v[1] = fmaf(axm, F(m2.z), v[1]);  v[2] = fmaf(axm, F(m2.w), v[2]);
                         }
+                    };
+                    if constexpr (!SHARED_SIDES) {
+                    // ---- side by side (the float16-cell instances): acc[r] += U[side] + frac(y)*V[side] for either side, a full fold where a
+                    //      side's row of cells changes ----
+                    float4 y[WALK];
+#pragma unroll
+                    for (int r = 0; r < WALK; r++) y[r] = ysteps_of[r][w];   // { frac(y+), frac(y-), row bytes(y+), row bytes(y-) }
+                    float U[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}}, V[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+                    int previous[2] = {-2*ROWBYTES, -2*ROWBYTES};     // (no row of cells: neither equal nor adjacent to a real one)
+                    // both y sides of a walk step advance row by row together (their first cells are fetched at once)
+                    auto advance = [&](int r, int side) {
+                        const int cell_row = __float_as_int(side ? y[r].w : y[r].z);
+                        // (a walk step's first row folds without asking — it always does: `previous` starts at no row — so that the compiler drops
+                        // the thirteen v_mov 0 that initialised U and V for the path nobody takes)
+                        if (r == 0 || cell_row != previous[side]) {
+                            previous[side] = cell_row;
+                            fold(cell_row, U[side], V[side]);
+                        }
                         // red and green of a row advance together as v_pk_add_f32 / v_pk_fma_f32 with the row's SCALAR fractions broadcast by
                         // op_sel (tools/ubench_pk_f32.hip: a scalar pair costs a packed form nothing, a v_mov v, s 4.2 cycles); blue keeps
                         // scalar-source fmas
-                        typedef float pk2 __attribute__((ext_vector_type(2)));
                         pk2 a01 = {acc[r][0], acc[r][1]};
                         const pk2 u01 = {U[side][0], U[side][1]}, v01 = {V[side][0], V[side][1]};
                         const pk2 fractions = {y[r].x, y[r].y};               // a scalar pair: { frac(y+), frac(y-) }
@@ -986,6 +1015,96 @@ struct VisualizerStrip {
                     };
 #pragma unroll
                     for (int r = 0; r < WALK; r++) if (r < rows) { advance(r, 0); advance(r, 1); }
+                    } else {
+                    float4 y[WALK];
+#pragma unroll
+                    for (int r = 0; r < WALK; r++) y[r] = ysteps[r*10 + w];   // { y*(y+), y*(y-), row bytes(y+), row bytes(y-) }
+                    // ONE running pair for both y sides of the step. Inside a row of cells a side's pair of taps is U + (Y_r - y*)*V =
+                    // G + Y_r*V with G = U - y*·V, and G, V stay what they are for every sample row of the strip whose tap lands in that row of
+                    // cells. The two sides add to TG + Y_r*TV (TG = G+ + G-, TV = V+ + V-): a row costs one add and one multiply-add per
+                    // channel for both sides together. A side that moves up ONE row of cells needs no full fold either: the bilinear surface
+                    // is continuous across the boundary (U_c + V_c = U_c+1), so only V changes, G_new = G_old - y*_new·(V_new - V_old), and
+                    // V_new takes the C, D half of the two cells only. A side that moves further (samples more than a texel apart: the net
+                    // under the tiles' bounds) folds both sides again.
+                    pk2 TG01, TV01;                                   // red, green: the operands of the rows' packed forms
+                    float TG2, TV2, Vs[2][3];
+                    int previous[2];
+                    auto in_vgpr = [](float scalar) {                 // ONE v_mov for a scalar that several multiply-adds read (not `asm volatile`: see the column lines)
+                        float v;
+                        asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(scalar));
+                        return v;
+                    };
+                    // V alone: the C, D half of the two cells — the 24 contiguous bytes from offset 24 of a float32 cell
+                    auto fold_v = [&](int cell_row, float (&v)[3]) {
+                        static_assert(SHARED_SIDES ? !HALF : true, "the half fold reads float32 cells");
+                        SF_COUNT_FOLD();
+                        const char* p = tile + (cxp + cell_row);
+                        const char* m = tile + (cxm + cell_row);
+                        const float2 p1 = *(const float2*)(p + 24), m1 = *(const float2*)(m + 24);
+                        const float4 p2 = *(const float4*)(p + 32), m2 = *(const float4*)(m + 32);
+                        v[0] = p1.x + m1.x; v[1] = p1.y + m1.y; v[2] = p2.x + m2.x;
+                        v[0] = fmaf(axp, p2.y, v[0]);  v[1] = fmaf(axp, p2.z, v[1]);  v[2] = fmaf(axp, p2.w, v[2]);
+                        v[0] = fmaf(axm, m2.y, v[0]);  v[1] = fmaf(axm, m2.z, v[1]);  v[2] = fmaf(axm, m2.w, v[2]);
+                    };
+                    // both sides folded in full (their cells are fetched at once): a walk step's first row, and a side that jumped
+                    auto fold_both = [&](int r) {
+                        previous[0] = __float_as_int(y[r].z); previous[1] = __float_as_int(y[r].w);
+                        float up[3], um[3];
+                        fold(previous[0], up, Vs[0]);
+                        fold(previous[1], um, Vs[1]);
+                        const float sp = in_vgpr(y[r].x), sm = in_vgpr(y[r].y);
+                        TG01.x = fmaf(-sp, Vs[0][0], up[0]) + fmaf(-sm, Vs[1][0], um[0]);
+                        TG01.y = fmaf(-sp, Vs[0][1], up[1]) + fmaf(-sm, Vs[1][1], um[1]);
+                        TG2 = fmaf(-sp, Vs[0][2], up[2]) + fmaf(-sm, Vs[1][2], um[2]);
+                        TV01.x = Vs[0][0] + Vs[1][0]; TV01.y = Vs[0][1] + Vs[1][1]; TV2 = Vs[0][2] + Vs[1][2];
+                    };
+                    // a side enters the next row of cells
+                    auto cross = [&](int side, int cell_row, float ystar) {
+                        previous[side] = cell_row;
+                        float vn[3];
+                        fold_v(cell_row, vn);
+                        const float s = in_vgpr(ystar);
+                        const float d0 = vn[0] - Vs[side][0], d1 = vn[1] - Vs[side][1], d2 = vn[2] - Vs[side][2];
+                        Vs[side][0] = vn[0]; Vs[side][1] = vn[1]; Vs[side][2] = vn[2];
+                        TV01.x = TV01.x + d0; TV01.y = TV01.y + d1; TV2 = TV2 + d2;
+                        TG01.x = fmaf(-s, d0, TG01.x); TG01.y = fmaf(-s, d1, TG01.y); TG2 = fmaf(-s, d2, TG2);
+                    };
+#pragma unroll
+                    for (int r = 0; r < WALK; r++) if (r < rows) {
+                        // (a walk step's first row folds without asking)
+                        if (r == 0) fold_both(0);
+                        else {
+                            // (two scalar compares and two branches for a row that stays where it is — the scalar unit issues one instruction
+                            // per slot for the SIMD's six waves, and a row's vector work is six instructions: every scalar instruction spent
+                            // here on telling a jump from a crossing first made the walk SLOWER than the two accumulations it replaces)
+                            // ONE branch (two xor, one or) for a row that stays where it is; what moved is sorted out behind it. Offsets are
+                            // multiples of ROWBYTES: a difference that is neither 0 nor ROWBYTES is above it as an unsigned number
+                            const int cp = __float_as_int(y[r].z), cm = __float_as_int(y[r].w);
+                            // (in asm: written in C++ the compiler turns the test back into two compares, four selects and two ands)
+                            int moved_p, moved;
+                            asm("s_xor_b32 %0, %1, %2" : "=s"(moved_p) : "s"(cp), "s"(previous[0]) : "scc");
+                            asm("s_xor_b32 %0, %1, %2\n\ts_or_b32 %0, %0, %3" : "=&s"(moved) : "s"(cm), "s"(previous[1]), "s"(moved_p) : "scc");
+                            if (moved != 0) {
+                                const unsigned dp = (unsigned)(cp - previous[0]), dm = (unsigned)(cm - previous[1]);
+                                if ((dp > dm ? dp : dm) > (unsigned)ROWBYTES) fold_both(r);
+                                else {
+                                    if (dp != 0) cross(0, cp, y[r].x);
+                                    if (dm != 0) cross(1, cm, y[r].y);
+                                }
+                            }
+                        }
+                        // red and green of a row advance together as v_pk_add_f32 / v_pk_fma_f32 with the row's SCALAR coordinate broadcast by
+                        // op_sel (tools/ubench_pk_f32.hip: a scalar pair costs a packed form nothing, a v_mov v, s 4.2 cycles); blue keeps
+                        // a scalar-source fma
+                        pk2 a01 = {acc[r][0], acc[r][1]};
+                        asm("v_pk_add_f32 %0, %0, %1" : "+v"(a01) : "v"(TG01));
+                        if ((r & 1) == 0) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(a01) : "s"(Y[r/2]), "v"(TV01));
+                        else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(a01) : "s"(Y[r/2]), "v"(TV01));
+                        acc[r][0] = a01.x; acc[r][1] = a01.y;
+                        acc[r][2] = acc[r][2] + TG2;
+                        acc[r][2] = fmaf((r & 1) ? Y[r/2].y : Y[r/2].x, TV2, acc[r][2]);
+                    }
+                    }
                     xp = xp + step; xm = xm - step;
                 }
             }

@@ -173,9 +173,14 @@ def main() -> None:
             fold = 28 <= n <= 31 and block["counts"].get("lds", 0) == 6
             skip_path = (not block["counts"].get("lds")) and all(cls in ("salu", "branch", "mov", "waitcnt") for cls in block["counts"]) and n <= 14 and not within(lines, (M["diag"][0], M["diag_setup_end"][0] + 12)) and i > 0 and "diagonal set-up" not in why[i - 1]
             if block["counts"].get("lds", 0) >= 12 and n > 40:
-                # VIS_STRIP_FIRST_ROW_FOLDS: the first row's two folds (twelve reads) sit in the step's own block; every other fold is conditional
+                # the first row's two folds (twelve reads) sit in the step's own block; round 8: the same block behind every later row is
+                # the full fold of both sides for a side that skipped a row of cells — samples more than a texel apart, never at C3
+                first_row = diag_fold_seen < 2
                 diag_fold_seen = 2
-                weights[i], why[i] = 10.0, "diagonal per step / per advance"
+                weights[i], why[i] = (10.0, "diagonal per step / per advance") if first_row else (0.0, "a side skips a row of cells (never at C3)")
+            elif block["counts"].get("lds", 0) == 4 and 20 <= n <= 40:
+                # round 8: a side enters the next row of cells — the C, D half of its two cells (ds_read2_b64 + ds_read_b64 each), V, dV, TV, TG
+                weights[i], why[i] = 10.0*p, "diagonal fold"
             elif fold:
                 diag_fold_seen += 1
                 weights[i] = 10.0*(1.0 if diag_fold_seen <= 2 else p)
