@@ -577,6 +577,29 @@ int sfx_video_png_paths(sfx_handle video, uint64_t* segment_frames, uint64_t* se
  * `info`: {segments, 1 when the segment path decoded the frame, 1 when it fell back to the serial path}. Synchronous. */
 int sfx_png_decode(sfx_handle ctx, const void* staged, size_t nbytes, int width, int height, int mode, uint8_t* filtered_out, uint8_t* rgb_out,
                    uint32_t* status, uint32_t* info /* [3] */);
+/* General planar sources (no reference counterpart): 4:2:0, 4:2:2, 4:4:4 and grey frames of 8, 10 or 12 bits, BT.601 / BT.709 /
+ * BT.2020 (non-constant luminance), limited or full range, chroma replicated or interpolated, converted by k_video_planar. The
+ * NORMATIVE definition — plane order and sizes, the five fixed-point coefficients per layout, chroma carried in sixteenths, one
+ * rounding per value — is the header comment of csrc/video_kernels.hpp; unpinned against swscale like SFX_VIDEO_I420, whose layout
+ * (8-bit 4:2:0 bt601 limited nearest) it reproduces bit for bit. Deep samples are little-endian 16-bit words. */
+enum { SFX_VIDEO_PLANAR = 4 /* a planar frame of the layout given to sfx_video_create_planar */ };
+enum { SFX_PLANAR_420 = 0, SFX_PLANAR_422 = 1, SFX_PLANAR_444 = 2, SFX_PLANAR_MONO = 3 };      /* subsampling */
+enum { SFX_PLANAR_BT601 = 0, SFX_PLANAR_BT709 = 1, SFX_PLANAR_BT2020 = 2 };                     /* matrix */
+enum { SFX_PLANAR_LIMITED = 0, SFX_PLANAR_FULL = 1 };                                           /* range */
+enum { SFX_PLANAR_NEAREST = 0, SFX_PLANAR_LINEAR = 1 };                                         /* filter */
+enum { SFX_PLANAR_CENTRE = 0, SFX_PLANAR_LEFT = 1 };                                            /* siting (horizontal; read by the linear filter) */
+typedef struct sfx_planar_layout {
+    int32_t subsampling;            /* SFX_PLANAR_420 … SFX_PLANAR_MONO */
+    int32_t depth;                  /* 8, 10 or 12 (grey: 8) */
+    int32_t matrix, range, filter, siting;
+} sfx_planar_layout;
+SFX_STATIC_ASSERT(sizeof(sfx_planar_layout) == 24, "six 32-bit fields");
+/* sfx_video_create for such a source: slots of the layout's frame size (Y, then Cb and Cr where the layout has them), everything else
+ * as there; sfx_video_step and a landing frame of sfx_sequence_run launch k_video_planar. SFX_E_INVALID naming the extents for an
+ * odd extent on a subsampled axis, naming the field for a value outside the enumerations above. 4:4:4 and grey have no chroma to
+ * interpolate: their filter is read as nearest. sfx_video_create itself keeps refusing format 4. */
+int sfx_video_create_planar(sfx_handle ctx, const sfx_handle* boxes, int temporal, int width, int height, const sfx_planar_layout* layout,
+                            int slots, sfx_handle* video);
 /* video.py:57-66 has no counterpart: stops the copy stream, then frees the staging */
 int sfx_video_destroy(sfx_handle video);
 

@@ -67,7 +67,13 @@ class ClockTick(C.Structure):
 
 
 PASS_LAYERS, PASS_FUSED, PASS_RESOLVE = 0, 1, 2
-VIDEO_RGB24, VIDEO_I420, VIDEO_MJPEG, VIDEO_PNG = 0, 1, 2, 3
+VIDEO_RGB24, VIDEO_I420, VIDEO_MJPEG, VIDEO_PNG, VIDEO_PLANAR = 0, 1, 2, 3, 4
+
+
+class PlanarLayout(C.Structure):
+    """sfx_planar_layout (include/shaderflow_hip.h): the SFX_PLANAR_* numbers of a planar source's layout (planarsource.PlanarLayout.native)"""
+    _fields_ = [("subsampling", C.c_int32), ("depth", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32), ("filter", C.c_int32),
+                ("siting", C.c_int32)]
 
 
 class PianoParams(C.Structure):
@@ -229,6 +235,7 @@ PROTOTYPES: dict[str, tuple] = {
     "sfx_video_jpeg_paths": (C.c_int, [Handle, P(C.c_uint64), P(C.c_uint64)]),
     "sfx_video_create_png": (C.c_int, [Handle, P(Handle), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, P(Handle)]),
     "sfx_video_png_paths": (C.c_int, [Handle, P(C.c_uint64), P(C.c_uint64)]),
+    "sfx_video_create_planar": (C.c_int, [Handle, P(Handle), C.c_int, C.c_int, C.c_int, P(PlanarLayout), C.c_int, P(Handle)]),
     "sfx_png_decode": (C.c_int, [Handle, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
     "sfx_sequence_run": (C.c_int, [Handle, P(Sequence)]),
     "sfx_device_alloc": (C.c_int, [Handle, C.c_size_t, P(C.c_void_p)]),

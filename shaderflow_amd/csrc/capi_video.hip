@@ -13,11 +13,15 @@
 // Compressed sources: the handle owns a decoder (video_decoder.hpp; a unit per format) and knows nothing else of the format. A slot then
 // holds a staged frame of its own length, at most frame_bytes: the submit asks the decoder to accept it, and the landing frame makes the
 // decoder's launches where k_video_frame would run.
+//
+// General planar sources (sfx_video_create_planar: SFX_VIDEO_PLANAR) are uncompressed like rgb24 and I420 — fixed-size slots, no decoder —
+// and land through k_video_planar: the handle keeps the kernel's instance and the layout's coefficients, built here on the host.
 
 #include "video_decoder.hpp"
 #include "video_kernels.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 
 using namespace sf;
@@ -36,6 +40,8 @@ struct Video : Object {
     void* staging_block = nullptr;          // with a decoder: the slots' device staging as one allocation (`staging` holds views into it)
     uint32_t* first_bad = nullptr;          // with a decoder, pinned: {status, serial} of the first landed frame with a bad status since sfx_video_status last asked (and the decoder's own words: VideoDecoder::launch)
     uint32_t serial = 0;                    // frames landed so far
+    int subsampling = 0, sample_bytes = 1, filter = 0;   // SFX_VIDEO_PLANAR: k_video_planar's instance …
+    VideoPlanarParams planar = {};                        // … and its coefficients
 };
 enum { SLOT_NEW = 0, SLOT_SUBMITTED = 1, SLOT_CONSUMED = 2 };
 
@@ -107,6 +113,68 @@ extern "C" int sfx_video_create(sfx_handle hc, const sfx_handle* boxes, int temp
     return video_create(c, boxes, temporal, width, height, format, (size_t)width*height*3/(format == SFX_VIDEO_I420 ? 2 : 1), slots, nullptr, out);   // (extents below 1 are refused there)
 }
 
+// The five fixed-point coefficients, the luma offset and the chroma midpoint of a layout (video_kernels.hpp's rule; tests/planar_ref.py
+// restates it): floor(x 2^S + 1/2) of ys, 2(1-Kr) cs, 2(1-Kb) Kb/Kg cs, 2(1-Kr) Kr/Kg cs, 2(1-Kb) cs
+static VideoPlanarParams planar_coefficients(const sfx_planar_layout& l) {
+    static const double KR[3] = {0.299, 0.2126, 0.2627}, KB[3] = {0.114, 0.0722, 0.0593};
+    const double kr = KR[l.matrix], kb = KB[l.matrix], kg = 1.0 - kr - kb;
+    const int b = l.depth, S = b == 8 ? 8 : (b == 10 ? 14 : 16);
+    const double steps = (double)(1 << (b - 8)), top = (double)((1 << b) - 1);
+    const double ys = l.range == SFX_PLANAR_FULL ? 255.0/top : 255.0/(219.0*steps), cs = l.range == SFX_PLANAR_FULL ? 255.0/top : 255.0/(224.0*steps);
+    const double one = (double)(1 << S);
+    auto fixed = [&](double x) { return (int)floor(x*one + 0.5); };
+    VideoPlanarParams q;
+    q.cy = fixed(ys); q.crv = fixed(2.0*(1.0 - kr)*cs); q.cgu = fixed(2.0*(1.0 - kb)*kb/kg*cs); q.cgv = fixed(2.0*(1.0 - kr)*kr/kg*cs); q.cbu = fixed(2.0*(1.0 - kb)*cs);
+    q.offset = l.range == SFX_PLANAR_FULL ? 0 : 16 << (b - 8); q.mid = 1 << (b - 1); q.shift = S; q.depth = b; q.siting = l.siting;
+    return q;
+}
+
+extern "C" int sfx_video_create_planar(sfx_handle hc, const sfx_handle* boxes, int temporal, int width, int height, const sfx_planar_layout* layout, int slots, sfx_handle* out) {
+    CTX_OR_FAIL(c, hc);
+    if (!layout) return fail(SFX_E_INVALID, "video: null planar layout");
+    const sfx_planar_layout l = *layout;
+    if (l.subsampling < SFX_PLANAR_420 || l.subsampling > SFX_PLANAR_MONO) return fail(SFX_E_INVALID, "video: planar layout field subsampling = %d (0 … 3)", l.subsampling);
+    if (l.depth != 8 && l.depth != 10 && l.depth != 12) return fail(SFX_E_INVALID, "video: planar layout field depth = %d (8, 10 or 12)", l.depth);
+    if (l.subsampling == SFX_PLANAR_MONO && l.depth != 8) return fail(SFX_E_INVALID, "video: planar layout field depth = %d: grey frames are read at 8 bits only", l.depth);
+    if (l.matrix < SFX_PLANAR_BT601 || l.matrix > SFX_PLANAR_BT2020) return fail(SFX_E_INVALID, "video: planar layout field matrix = %d (0 … 2)", l.matrix);
+    if (l.range != SFX_PLANAR_LIMITED && l.range != SFX_PLANAR_FULL) return fail(SFX_E_INVALID, "video: planar layout field range = %d (0 or 1)", l.range);
+    if (l.filter != SFX_PLANAR_NEAREST && l.filter != SFX_PLANAR_LINEAR) return fail(SFX_E_INVALID, "video: planar layout field filter = %d (0 or 1)", l.filter);
+    if (l.siting != SFX_PLANAR_CENTRE && l.siting != SFX_PLANAR_LEFT) return fail(SFX_E_INVALID, "video: planar layout field siting = %d (0 or 1)", l.siting);
+    if (width < 1 || height < 1) return fail(SFX_E_INVALID, "video: a planar source of %d x %d", width, height);
+    const bool halved_x = l.subsampling == SFX_PLANAR_420 || l.subsampling == SFX_PLANAR_422, halved_y = l.subsampling == SFX_PLANAR_420;
+    if ((halved_x && (width & 1)) || (halved_y && (height & 1)))
+        return fail(SFX_E_INVALID, "video: a %s source needs an even %s, not %d x %d", halved_y ? "4:2:0" : "4:2:2", halved_y ? "width and height" : "width", width, height);
+    const size_t bytes = l.depth > 8 ? 2 : 1, luma = (size_t)width*height;
+    const size_t chroma = l.subsampling == SFX_PLANAR_MONO ? 0 : (size_t)(halved_x ? width/2 : width)*(halved_y ? height/2 : height);
+    const int rc = video_create(c, boxes, temporal, width, height, SFX_VIDEO_PLANAR, (luma + 2*chroma)*bytes, slots, nullptr, out);
+    if (rc) return rc;
+    Video* v = get<Video>(*out, MAGIC_VIDEO);
+    v->subsampling = l.subsampling; v->sample_bytes = (int)bytes;
+    v->filter = halved_x ? l.filter : SFX_PLANAR_NEAREST;             // (4:4:4 and grey have nothing to interpolate)
+    v->planar = planar_coefficients(l);
+    return SFX_OK;
+}
+
+// k_video_planar's instance for a handle's layout
+template <int SUB, int BPS, int FILTER>
+static void planar_launch(const Video* v, dim3 grid, dim3 block, const uint8_t* src, uint8_t* dst) {
+    hipLaunchKernelGGL((k_video_planar<SUB, BPS, FILTER>), grid, block, 0, v->ctx->stream, src, dst, v->width, v->height, v->planar);
+}
+template <int SUB> static void planar_launch_sub(const Video* v, dim3 grid, dim3 block, const uint8_t* src, uint8_t* dst) {
+    constexpr bool FILTERED = SUB == PLANAR_420 || SUB == PLANAR_422;
+    if (v->sample_bytes == 1) { if (FILTERED && v->filter) planar_launch<SUB, 1, FILTERED ? 1 : 0>(v, grid, block, src, dst); else planar_launch<SUB, 1, 0>(v, grid, block, src, dst); }
+    else if constexpr (SUB != PLANAR_MONO) { if (FILTERED && v->filter) planar_launch<SUB, 2, FILTERED ? 1 : 0>(v, grid, block, src, dst); else planar_launch<SUB, 2, 0>(v, grid, block, src, dst); }
+}
+static void video_launch_planar(const Video* v, const uint8_t* src, uint8_t* dst) {
+    const long lanes = video_planar_lanes(v->subsampling, v->width, v->height);
+    const dim3 grid((unsigned)((lanes + VIDEO_THREADS - 1)/VIDEO_THREADS)), block(VIDEO_THREADS);
+    switch (v->subsampling) {
+        case PLANAR_420: planar_launch_sub<PLANAR_420>(v, grid, block, src, dst); break;
+        case PLANAR_422: planar_launch_sub<PLANAR_422>(v, grid, block, src, dst); break;
+        case PLANAR_444: planar_launch_sub<PLANAR_444>(v, grid, block, src, dst); break;
+        default: planar_launch_sub<PLANAR_MONO>(v, grid, block, src, dst); break;
+    }
+}
 
 extern "C" int sfx_video_slot(sfx_handle h, int slot, void** host, size_t* nbytes) {
     Video* v = get<Video>(h, MAGIC_VIDEO);
@@ -171,6 +239,7 @@ int video_launch_frame(sfx_handle h, Context* c, int slot) {
     const long lanes = video_frame_lanes(v->format, v->width, v->height);
     const dim3 grid((unsigned)((lanes + VIDEO_THREADS - 1)/VIDEO_THREADS)), block(VIDEO_THREADS);
     if (v->decoder) v->decoder->launch(v->ctx->stream, slot, (const uint8_t*)v->staging[slot], v->first_bad, v->serial++, (uint8_t*)front->data, 1);
+    else if (v->format == SFX_VIDEO_PLANAR) video_launch_planar(v, (const uint8_t*)v->staging[slot], (uint8_t*)front->data);
     else if (v->format == SFX_VIDEO_I420) hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_I420>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     else hipLaunchKernelGGL(k_video_frame<SFX_VIDEO_RGB24>, grid, block, 0, v->ctx->stream, (const uint8_t*)v->staging[slot], (uint8_t*)front->data, v->width, v->height);
     const int rc = launch_status();

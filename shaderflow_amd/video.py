@@ -8,13 +8,16 @@ frame), rows flipped to GL order, after rolling the temporal matrix.
 
 Where frames come from: the reference pipes the file through an `ffmpeg` subprocess (ffmpeg.py:1116-1137). Here:
   * `frames=` any iterable of (height, width, 3) uint8 arrays, top row first — what that iterator yields; with `format="i420"` the
-    iterable yields 1-D uint8 arrays of width*height*3//2 bytes instead (planar 4:2:0: Y, U, V, top row first);
+    iterable yields 1-D uint8 arrays of width*height*3//2 bytes instead (planar 4:2:0: Y, U, V, top row first); with a planar pixel
+    format ("yuv420p", "yuv422p", "yuv444p", each also with "10le" or "12le", or "gray") 1-D uint8 arrays of that layout's frame
+    size, or uint16 arrays of the samples for the deep layouts;
   * `path=` a `.npy` holding (n, height, width, 3) uint8, or a raw `.rgb` file with `width`/`height` given;
   * `path=` a `.y4m` file (YUV4MPEG2, the uncompressed interchange format: 1.5 bytes per pixel), read natively: width, height and
-    fps come from its header. 8-bit progressive 4:2:0 only (`C420`, `C420jpeg`, `C420mpeg2`, `C420paldv`, or no `C` tag): another
-    chroma layout, a higher bit depth, interlacing or `XCOLORRANGE=FULL` raise ValueError naming the tag;
-  * `path=` a raw `.yuv` / `.i420` file with `width`, `height` and `fps` given: planar 4:2:0 frames, what this package's own
-    yuv420p export writes (exporting.py);
+    fps come from its header, and so does the layout (planarsource.py): progressive 4:2:0 (`C420`, `C420jpeg`, `C420mpeg2`,
+    `C420paldv`, or no `C` tag), 4:2:2 (`C422`), 4:4:4 (`C444`), each at 8, 10 or 12 bits (`p10`, `p12`), grey (`Cmono`), limited
+    or full range (`XCOLORRANGE=`). Interlacing, alpha, `C411`, other depths and deep grey raise ValueError naming the tag;
+  * `path=` a raw `.yuv` / `.i420` file with `width`, `height` and `fps` given: planar frames of `format` (yuv420p when none is
+    given: what this package's own yuv420p export writes, exporting.py — with `yuv_matrix="bt709"` when the export had it);
   * `path=` an `.avi` file with a Motion-JPEG video stream (fourcc `MJPG`: what `pixel_format="mjpeg"` exports, and what many cameras
     and editors write) or a bare `.mjpeg` / `.mjpg` stream (JPEG images back to back; `fps=` given), read natively (mjpegsource.py):
     the frames stay compressed in pinned memory and over the link — a quality-90 4K frame is about 665 KB against 24.9 MB of rgb24 —
@@ -35,10 +38,14 @@ Where frames come from: the reference pipes the file through an `ffmpeg` subproc
 A source shorter than the scene keeps its last frame on screen (the reference's generator would raise
 StopIteration out of `update`).
 
-Planar sources are converted on the device by `k_video_frame` (csrc/video_kernels.hpp): BT.601 limited range in integer arithmetic,
-chroma replicated over its 2 x 2 block — this project's own definition, **unpinned against swscale** (no ffmpeg binary to pin it
-against), like the yuv420p output. The frame loop shows them through the same kernel (`VideoStage`: a pinned frame, an asynchronous
-copy, one launch), so the conversion has one definition; rgb sources in the frame loop are flipped and uploaded by the host as ever.
+Planar sources are converted on the device (csrc/video_kernels.hpp, whose header comment is the definition): integer arithmetic with
+the layout's matrix (`yuv_matrix`: bt601, bt709, bt2020), range (`yuv_range`) and depth, subsampled chroma replicated
+(`chroma="nearest"`) or interpolated with the triangle filter at the file's siting (`chroma="linear"`) — this project's own
+definition, **unpinned against swscale** (no ffmpeg binary to pin it against), like the yuv420p output. The 8-bit 4:2:0 bt601 limited
+nearest layout is `format == "i420"` and `k_video_frame`'s, as ever; every other one is `format == "planar"` (the layout in `header`)
+and `k_video_planar`'s, which gives the same bytes at that layout. The frame loop shows them through the same kernels (`VideoStage`:
+a pinned frame, an asynchronous copy, one launch), so the conversion has one definition; rgb sources in the frame loop are flipped and
+uploaded by the host as ever.
 Scenes that qualify draw whole chunks of frames per native call instead (videosequence.py).
 """
 from __future__ import annotations
@@ -54,7 +61,7 @@ import numpy as np
 from attrs import define
 
 from shaderflow_amd import _native as N
-from shaderflow_amd import mjpegsource, pngsource
+from shaderflow_amd import mjpegsource, planarsource, pngsource
 from shaderflow_amd.clips import AviClip
 from shaderflow_amd.module import ShaderModule, logger
 from shaderflow_amd.texture import ShaderTexture
@@ -87,89 +94,26 @@ def iter_video_frames(path: Path, width: int, height: int) -> Iterator[np.ndarra
 
 
 def parse_y4m_header(line: bytes) -> tuple[int, int, float]:
-    """(width, height, fps) of a YUV4MPEG2 stream header; ValueError names the tag this reader does not take"""
-    tokens = line.rstrip(b"\n").decode("ascii", "replace").split(" ")
-    if tokens[0] != "YUV4MPEG2":
-        raise ValueError(f"not a YUV4MPEG2 stream: it begins with {tokens[0][:16]!r}")
-    width = height = fps = None
-    for token in filter(None, tokens[1:]):
-        tag, value = token[0], token[1:]
-        if tag == "W":
-            width = int(value)
-        elif tag == "H":
-            height = int(value)
-        elif tag == "F":
-            num, _, den = value.partition(":")
-            fps = float(int(num))/float(int(den or 1))
-        elif tag == "I" and value != "p":
-            raise ValueError(f"y4m tag {token!r}: only progressive frames (Ip) are read")
-        elif tag == "C" and value not in Y4M_CHROMA:
-            raise ValueError(f"y4m tag {token!r}: only 8-bit 4:2:0 ({', '.join('C' + c for c in Y4M_CHROMA)}) is read")
-        elif tag == "X" and value.upper() == "COLORRANGE=FULL":
-            raise ValueError(f"y4m tag {token!r}: only limited-range video is read")
-    if not (width and height and fps) or width < 1 or height < 1 or fps <= 0:
-        raise ValueError(f"y4m header without W, H and F: {line[:80]!r}")
-    if width % 2 or height % 2:
-        raise ValueError(f"y4m W{width} H{height}: 4:2:0 frames need even extents")
+    """(width, height, fps) of a YUV4MPEG2 stream header: the 8-bit 4:2:0 limited-range front of planarsource.parse_y4m. ValueError
+    names the tag this reader does not take"""
+    width, height, fps, fields = planarsource.parse_y4m(line)
+    if fields["subsampling"] != "420" or fields["depth"] != 8:
+        raise ValueError(f"y4m tag {fields['tags']['C']!r}: only 8-bit 4:2:0 ({', '.join('C' + c for c in Y4M_CHROMA)}) is read")
+    if fields["range"] == "full":
+        raise ValueError(f"y4m tag {fields['tags']['X']!r}: only limited-range video is read")
     return width, height, fps
 
 
-class PlanarFile:
-    """Frames of a `.y4m` or raw planar file, in order: an iterator of 1-D uint8 arrays of width*height*3//2 bytes, and `readinto(view)`
-    for a caller with a buffer of its own (the sequence's pinned slots: no intermediate array). A truncated last frame ends the clip,
-    as a short read ends iter_video_frames."""
+class PlanarFile(planarsource.PlanarReader):
+    """Frames of an 8-bit 4:2:0 `.y4m` or raw planar file, in order: an iterator of 1-D uint8 arrays of width*height*3//2 bytes, and
+    `readinto(view)` (planarsource.PlanarReader: the frame loop every planar reader shares). Another layout raises ValueError naming
+    the tag: `planarsource.PlanarClip`, which ShaderVideo opens, reads those."""
 
-    def __init__(self, path: Path, width: Optional[int] = None, height: Optional[int] = None, fps: Optional[float] = None):
-        self.path, self.y4m = Path(path), Path(path).suffix.lower() == ".y4m"
-        self.file = open(self.path, "rb", buffering=0)
-        if self.y4m:
-            header = self._line(limit=4096)
-            width, height, fps = parse_y4m_header(header)
-        self.width, self.height, self.fps = width, height, fps
-        self.frame_bytes = width*height*3//2
+    def _header(self, line: bytes) -> tuple[int, int, float]:
+        return parse_y4m_header(line)
 
-    def _line(self, limit: int = 256) -> bytes:
-        """Up to and including the next newline (unbuffered file: a few bytes at a time only for these short lines)"""
-        line = bytearray()
-        while len(line) < limit and (byte := self.file.read(1)):
-            line += byte
-            if byte == b"\n":
-                break
-        return bytes(line)
-
-    def readinto(self, view) -> bool:
-        """The next frame into `view` (a writable buffer of frame_bytes bytes); False at the end of the clip"""
-        if self.file is None:
-            return False
-        if self.y4m:
-            line = self._line()
-            if not line:
-                return self._end()
-            if not (line.startswith(b"FRAME") and line.endswith(b"\n")):
-                raise ValueError(f"{self.path}: expected a FRAME line, found {line[:32]!r}")
-            if any(token[:1] == b"I" for token in line[5:].split()):
-                raise ValueError(f"{self.path}: frame tag {line[5:].strip()!r}: per-frame interlacing is not read")
-        target, got = memoryview(view).cast("B"), 0
-        while got < self.frame_bytes:
-            count = self.file.readinto(target[got:])
-            if not count:
-                return self._end()                                    # a truncated last frame ends the clip
-            got += count
-        return True
-
-    def _end(self) -> bool:
-        self.file.close()
-        self.file = None
-        return False
-
-    def __iter__(self):
-        return self
-
-    def __next__(self) -> np.ndarray:
-        frame = np.empty(self.frame_bytes, np.uint8)
-        if not self.readinto(frame):
-            raise StopIteration
-        return frame
+    def _frame_bytes(self) -> int:
+        return self.width*self.height*3//2
 
 
 class VideoStage:
@@ -184,13 +128,24 @@ class VideoStage:
             raise ValueError("a staged video needs an RGB8 texture with layers = 1")
         boxes = [box.texture for (_, _, box) in texture.boxes]
         self.serials = tuple(box.serial for box in boxes)              # which device textures the handle writes into
-        self.planar, self.codec = video.format == "i420", CODECS.get(video.format)
+        self.planar, self.codec = video.format in ("i420", "planar"), CODECS.get(video.format)      # planar: 1-D frames of a fixed size
+        self.layout = video.header if video.format == "planar" else None                           # a planarsource.PlanarLayout: k_video_planar's
         self.width, self.height, self.header = video.width, video.height, video.header
-        self.frame_bytes = video.capacity if self.codec else video.width*video.height*3//(2 if self.planar else 1)   # what a slot holds
+        if self.codec:
+            self.frame_bytes = video.capacity                         # what a slot holds
+        elif self.layout:
+            self.frame_bytes = self.layout.frame_bytes(video.width, video.height)
+        else:
+            self.frame_bytes = video.width*video.height*3//(2 if self.planar else 1)
         self.slots, self.handle = slots(self.frame_bytes) if callable(slots) else slots, N.Handle()
         handles = (N.Handle*len(boxes))(*[box.handle for box in boxes])
         if self.codec:
             self.handle = self.codec.create(video.scene.context.handle, handles, texture.temporal, video.header, video.capacity, self.slots)
+            return
+        if self.layout:
+            native = self.layout.native()
+            N.check(N.lib().sfx_video_create_planar(video.scene.context.handle, handles, texture.temporal, video.width, video.height,
+                                                    C.byref(native), self.slots, C.byref(self.handle)))
             return
         N.check(N.lib().sfx_video_create(video.scene.context.handle, handles, texture.temporal, video.width, video.height,
                                          N.VIDEO_I420 if self.planar else N.VIDEO_RGB24, self.slots, C.byref(self.handle)))
@@ -202,13 +157,16 @@ class VideoStage:
         return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(C.c_uint8)), shape=(nbytes.value,))
 
     def fill(self, view: np.ndarray, frame, label: str) -> Optional[int]:
-        """One source frame — an rgb array, an i420 array or a JPEG stream, as the video's format says — into the pinned `view`; returns
-        the bytes to `submit` (None: the format's fixed size). `label` names the frame in an error."""
+        """One source frame — an rgb array, an i420 array, a planar array of the layout or a JPEG stream, as the video's format says —
+        into the pinned `view`; returns the bytes to `submit` (None: the format's fixed size). `label` names the frame in an error."""
         if self.codec:                                                # the stream's tables, interval starts and scan (a PNG file's IDAT data); only they are copied
             return self.codec.stage(frame, self.header, view, label)
+        if self.layout and self.layout.depth > 8 and getattr(frame, "dtype", None) == np.uint16:
+            frame = np.ascontiguousarray(frame).astype("<u2", copy=False).reshape(-1).view(np.uint8)     # deep samples: little-endian words
         frame = np.asarray(frame, np.uint8)
         if frame.size != self.frame_bytes:
-            raise ValueError(f"{label}: {'an i420' if self.planar else 'an rgb'} frame of {self.width} x {self.height} has {self.frame_bytes} bytes, the source gave {frame.size}")
+            kind = f"a planar {self.layout.describe()}" if self.layout else ("an i420" if self.planar else "an rgb")
+            raise ValueError(f"{label}: {kind} frame of {self.width} x {self.height} has {self.frame_bytes} bytes, the source gave {frame.size}")
         np.copyto(view.reshape(frame.shape), frame)                   # (a memory-mapped clip is read here, without the GIL)
         return None
 
@@ -265,9 +223,19 @@ class ShaderVideo(ShaderModule):
     fps: Optional[float] = None
     format: Optional[str] = None
     """None: the source yields rgb arrays; "i420": planar 4:2:0 frames of width*height*3//2 bytes (set by the planar file sources);
-    "mjpeg": baseline JPEG streams as `bytes` (set by the Motion-JPEG file sources); "png": PNG files as `bytes` (set by an MPNG `.avi`)"""
+    "mjpeg": baseline JPEG streams as `bytes` (set by the Motion-JPEG file sources); "png": PNG files as `bytes` (set by an MPNG `.avi`).
+    A planar pixel format may be given for a raw `.yuv` file or for `frames=`: "yuv420p", "yuv422p", "yuv444p" (each also with "10le"
+    or "12le") or "gray". Once the source is open the field reads "i420" when the layout is 8-bit 4:2:0 bt601 limited nearest, and
+    "planar" — the layout in `header` — for every other one."""
     header: Optional[object] = None
-    """format "mjpeg" / "png": the first frame's header (mjpegsource.JpegHeader / pngsource.PngHeader): the geometry every frame must have"""
+    """format "mjpeg" / "png": the first frame's header (mjpegsource.JpegHeader / pngsource.PngHeader): the geometry every frame must
+    have; format "planar": the frames' planarsource.PlanarLayout"""
+    yuv_matrix: str = "bt601"
+    """planar sources: "bt601", "bt709" (what `ExportingHelper.yuv_matrix = "bt709"` exports) or "bt2020" — no file says it"""
+    yuv_range: Optional[str] = None
+    """planar sources: "limited" or "full"; None: a `.y4m` file's XCOLORRANGE tag, else limited"""
+    chroma: str = "nearest"
+    """planar sources: subsampled chroma replicated ("nearest") or interpolated ("linear": the triangle filter, sited as the file says)"""
     capacity: int = 0
     """format "mjpeg" / "png": bytes of a staged frame at the most (from the container's largest chunk; for `frames=` a raw picture's worth)"""
     _stage: Optional[VideoStage] = None
@@ -278,13 +246,15 @@ class ShaderVideo(ShaderModule):
 
     def __attrs_post_init__(self):
         ShaderModule.__attrs_post_init__(self)
-        if self.format not in (None, "i420", *CODECS):
-            raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays), 'i420', 'mjpeg' or 'png'")
+        if self.format not in (None, "i420", *CODECS, *planarsource.FORMAT_NAMES):
+            raise ValueError(f"ShaderVideo format {self.format!r}: None (rgb arrays), 'i420', 'mjpeg', 'png' or a planar pixel format ({', '.join(planarsource.FORMAT_NAMES)})")
         self._reader = self._open()
         if not all((self.width, self.height, self.fps)):
             raise ValueError("ShaderVideo needs width, height and fps (give them, or a source they can be read from)")
         if self.format == "i420" and (self.width % 2 or self.height % 2):
             raise ValueError(f"a 4:2:0 source needs even extents, not {self.width} x {self.height}")
+        if self.format == "planar":
+            self.header.check_extents(self.width, self.height)
         self.texture = ShaderTexture(scene=self.scene, name=self.name, width=self.width, height=self.height,
                                      dtype=np.uint8, components=3)
 
@@ -294,6 +264,8 @@ class ShaderVideo(ShaderModule):
                 self.height, self.width = self.height or self.frames.shape[1], self.width or self.frames.shape[2]
             if self.format in CODECS:
                 return self._open_compressed(iter(self.frames), None)
+            if self.format is not None:                                 # 1-D planar frames (uint16 arrays for the deep layouts)
+                self._take_layout(planarsource.PlanarLayout.from_format(self.format, matrix=self.yuv_matrix, range=self.yuv_range or "limited", chroma=self.chroma))
             return iter(self.frames)
         if self.path is None:
             raise ValueError("ShaderVideo needs `path=` or `frames=`")
@@ -311,8 +283,12 @@ class ShaderVideo(ShaderModule):
         if suffix == ".y4m" or suffix in PLANAR_SUFFIXES:
             if suffix != ".y4m" and not all((self.width, self.height, self.fps)):
                 raise ValueError("raw planar yuv420p video needs width=, height= and fps=")
-            clip = PlanarFile(self.path, self.width, self.height, self.fps)
-            self.width, self.height, self.fps, self.format = clip.width, clip.height, self.fps or clip.fps, "i420"
+            if self.format in CODECS:
+                raise ValueError(f"{self.path}: a planar file is not format {self.format!r}")
+            clip = planarsource.PlanarClip(self.path, self.width, self.height, self.fps, format=self.format, matrix=self.yuv_matrix,
+                                           range=self.yuv_range, chroma=self.chroma)
+            self.width, self.height, self.fps = clip.width, clip.height, self.fps or clip.fps
+            self._take_layout(clip.layout)
             return clip
         if suffix in MJPEG_SUFFIXES:
             self._clip = clip = mjpegsource.RawReader(self.path, self.fps)
@@ -331,6 +307,10 @@ class ShaderVideo(ShaderModule):
         width, height, fps = _probe(self.path)
         self.width, self.height, self.fps = self.width or width, self.height or height, self.fps or fps
         return iter_video_frames(self.path, self.width, self.height)
+
+    def _take_layout(self, layout: "planarsource.PlanarLayout") -> None:
+        """The two paths of a planar source: the I420 layout keeps k_video_frame and its bytes, every other one is k_video_planar's"""
+        self.format, self.header = ("i420", None) if layout.is_i420 else ("planar", layout)
 
     def _open_compressed(self, source: Iterator, largest: Optional[int]) -> Iterator:
         """A source of JPEG streams, or of PNG files (`format`): the clip's geometry and sampling are its first frame's"""
@@ -360,7 +340,7 @@ class ShaderVideo(ShaderModule):
             self._read += 1                                             # (a damaged frame is passed over: the next update() shows the next one)
             self._show_staged(frame, self._read - 1)
             return
-        if self.format == "i420":
+        if self.format in ("i420", "planar"):
             self._show_staged(frame, self._read)
         else:
             frame = np.ascontiguousarray(np.flip(np.asarray(frame, np.uint8), axis=0))

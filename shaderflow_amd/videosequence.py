@@ -22,8 +22,8 @@ Behind a run — finished, quit or failed — the host objects are where the fra
 draws go back in front of it for a later `update()`.
 
 Which scenes run this way, alone or beside audio modules or a piano, is `Sequence`'s to say (sequence.py). Out of scope, so they keep
-the frame loop: several videos, `layers != 1`, a subclass of ShaderVideo, sharded runs, a scene `update()` of its own, and — for the
-planar sources — bt709 or full-range input, chroma interpolation and 10-bit sources (the reader refuses what it can see of them).
+the frame loop: several videos, `layers != 1`, a subclass of ShaderVideo, sharded runs and a scene `update()` of its own. Planar
+sources of every layout (`video.format == "planar"`: planarsource.py) land through `k_video_planar` where `k_video_frame` would run.
 
 Motion-JPEG sources (`video.format == "mjpeg"`: mjpegsource.py) stay compressed in the slots: the reader stages each JPEG stream
 (`mjpegsource.stage`: tables, interval starts, scan), only those bytes are copied, and a landing launches the decode kernels
