@@ -4,6 +4,15 @@
 
 struct bvec2; struct bvec3; struct bvec4;      // defined after both integer families (jit_runtime.hpp)
 
+// T(v) is the first component (§5.4.1); ++ and -- add and subtract one at every component (§5.9)
+#define SF_RT_INT_COMMON(V, N) \
+    template <class S, typename std::enable_if<std::is_arithmetic<S>::value, int>::type = 0> \
+    SF_HD explicit operator S() const { return (S)d[0]; } \
+    SF_HD V& operator++() { for (int k = 0; k < N; k++) d[k] = d[k] + 1; return *this; } \
+    SF_HD V& operator--() { for (int k = 0; k < N; k++) d[k] = d[k] - 1; return *this; } \
+    SF_HD V operator++(int) { const V before = *this; ++*this; return before; } \
+    SF_HD V operator--(int) { const V before = *this; --*this; return before; }
+
 struct SF_RT_V2 {
     union {
         struct { SF_RT_T x, y; }; struct { SF_RT_T r, g; }; struct { SF_RT_T s, t; };
@@ -26,6 +35,7 @@ struct SF_RT_V2 {
     SF_HD SF_RT_V2& operator=(const SF_RT_V2& o) { for (int k = 0; k < 2; k++) d[k] = o.d[k]; return *this; }
     SF_HD SF_RT_T& operator[](int k) { return d[k]; }
     SF_HD SF_RT_T operator[](int k) const { return d[k]; }
+    SF_RT_INT_COMMON(SF_RT_V2, 2)
 };
 struct SF_RT_V3 {
     union {
@@ -51,6 +61,7 @@ struct SF_RT_V3 {
     SF_HD SF_RT_V3& operator=(const SF_RT_V3& o) { for (int k = 0; k < 3; k++) d[k] = o.d[k]; return *this; }
     SF_HD SF_RT_T& operator[](int k) { return d[k]; }
     SF_HD SF_RT_T operator[](int k) const { return d[k]; }
+    SF_RT_INT_COMMON(SF_RT_V3, 3)
 };
 struct SF_RT_V4 {
     union {
@@ -77,4 +88,6 @@ struct SF_RT_V4 {
     SF_HD SF_RT_V4& operator=(const SF_RT_V4& o) { for (int k = 0; k < 4; k++) d[k] = o.d[k]; return *this; }
     SF_HD SF_RT_T& operator[](int k) { return d[k]; }
     SF_HD SF_RT_T operator[](int k) const { return d[k]; }
+    SF_RT_INT_COMMON(SF_RT_V4, 4)
 };
+#undef SF_RT_INT_COMMON

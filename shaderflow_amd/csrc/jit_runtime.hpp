@@ -26,13 +26,20 @@ struct vec2; struct vec3; struct vec4;
 
 // ---- swizzles ---------------------------------------------------------------------------------------------------------
 // A swizzle is a member of the vector's anonymous union (same storage): reading converts it to a vector of the selected
-// components, writing assigns them (GLSL requires distinct components for that; not checked).
+// components, writing assigns them (GLSL requires distinct components for that; not checked). The right-hand side may be the
+// vector the swizzle lives in (`v.wzyx = v`, §5.8: the value is taken before anything is written), so it is copied first.
 template <class T, class V, int P, int... I>
 struct SwzT {
     T d[P];
     SF_HD operator V() const { return V(d[I]...); }
-    SF_HD SwzT& operator=(const V& v) { int k = 0; ((d[I] = v.d[k++]), ...); return *this; }
+    template <class S, typename std::enable_if<std::is_arithmetic<S>::value, int>::type = 0>
+    SF_HD explicit operator S() const { const int index[] = {I...}; return (S)d[index[0]]; }      // float(v.zyx): the first component (§5.4.1)
+    SF_HD SwzT& operator=(const V& v) { const V c = v; int k = 0; ((d[I] = c.d[k++]), ...); return *this; }
     SF_HD SwzT& operator=(const SwzT& o) { const V v = o; return *this = v; }
+    SF_HD SwzT& operator++() { const V me = *this; return *this = me + T(1); }
+    SF_HD SwzT& operator--() { const V me = *this; return *this = me - T(1); }
+    SF_HD V operator++(int) { const V me = *this; *this = me + T(1); return me; }
+    SF_HD V operator--(int) { const V me = *this; *this = me - T(1); return me; }
     // `v.xy op= x` for anything `vec2 op x` is defined for (vectors, scalars, matrices)
     template <class X> SF_HD SwzT& operator+=(const X& x) { const V me = *this; return *this = me + x; }
     template <class X> SF_HD SwzT& operator-=(const X& x) { const V me = *this; return *this = me - x; }
@@ -53,6 +60,12 @@ template <class V, int P, int... I> using Swz = SwzT<float, V, P, I...>;
     SF_HD V(const V& o) { for (int k = 0; k < N; k++) d[k] = o.d[k]; } \
     SF_HD float& operator[](int k) { return d[k]; } \
     SF_HD float operator[](int k) const { return d[k]; } \
+    template <class S, typename std::enable_if<std::is_arithmetic<S>::value, int>::type = 0> \
+    SF_HD explicit operator S() const { return (S)d[0]; } \
+    SF_HD V& operator++() { for (int k = 0; k < N; k++) d[k] = d[k] + 1.0f; return *this; } \
+    SF_HD V& operator--() { for (int k = 0; k < N; k++) d[k] = d[k] - 1.0f; return *this; } \
+    SF_HD V operator++(int) { const V before = *this; ++*this; return before; } \
+    SF_HD V operator--(int) { const V before = *this; --*this; return before; } \
     SF_HD V& operator+=(const V& o) { for (int k = 0; k < N; k++) d[k] = d[k] + o.d[k]; return *this; } \
     SF_HD V& operator-=(const V& o) { for (int k = 0; k < N; k++) d[k] = d[k] - o.d[k]; return *this; } \
     SF_HD V& operator*=(const V& o) { for (int k = 0; k < N; k++) d[k] = d[k]*o.d[k]; return *this; } \
@@ -122,6 +135,12 @@ struct bvec4 {
     SF_HD explicit bvec4(const uvec4& v) : x(v.x != 0u), y(v.y != 0u), z(v.z != 0u), w(v.w != 0u) {}
     SF_HD explicit bvec4(const vec4& v);
 };
+SF_HD bool operator==(const bvec2& a, const bvec2& b) { return a.x == b.x && a.y == b.y; }                  // §5.9: all components
+SF_HD bool operator==(const bvec3& a, const bvec3& b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
+SF_HD bool operator==(const bvec4& a, const bvec4& b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
+SF_HD bool operator!=(const bvec2& a, const bvec2& b) { return !(a == b); }
+SF_HD bool operator!=(const bvec3& a, const bvec3& b) { return !(a == b); }
+SF_HD bool operator!=(const bvec4& a, const bvec4& b) { return !(a == b); }
 SF_HD ivec2::ivec2(const bvec2& v) { x = v.x ? 1 : 0; y = v.y ? 1 : 0; }
 SF_HD ivec3::ivec3(const bvec3& v) { x = v.x ? 1 : 0; y = v.y ? 1 : 0; z = v.z ? 1 : 0; }
 SF_HD ivec4::ivec4(const bvec4& v) { x = v.x ? 1 : 0; y = v.y ? 1 : 0; z = v.z ? 1 : 0; w = v.w ? 1 : 0; }
@@ -213,8 +232,33 @@ SF_HD bvec2::bvec2(const vec2& v) : x(v.x != 0.0f), y(v.y != 0.0f) {}
 SF_HD bvec3::bvec3(const vec3& v) : x(v.x != 0.0f), y(v.y != 0.0f), z(v.z != 0.0f) {}
 SF_HD bvec4::bvec4(const vec4& v) : x(v.x != 0.0f), y(v.y != 0.0f), z(v.z != 0.0f), w(v.w != 0.0f) {}
 
+// A GLSL array (§4.1.9): a value. `b = a` copies, an `in` parameter is the callee's own copy, `==` compares element by element
+// (§5.8-5.9) — none of which a C array does. The translator declares `T name[N]` as `sf_arr<T,N> name` and writes the constructor
+// `T[N](a, b)` as `sf_arr_of<T>(a, b)`, which converts each argument like GLSL's constructor does (int to float included).
+template <class T, int N>
+struct sf_arr {
+    T v[N];
+    SF_HD T& operator[](int k) { return v[k]; }
+    SF_HD const T& operator[](int k) const { return v[k]; }
+    SF_HD bool operator==(const sf_arr& o) const { bool e = true; for (int k = 0; k < N; k++) e = e && (v[k] == o.v[k]); return e; }
+    SF_HD bool operator!=(const sf_arr& o) const { return !(*this == o); }
+};
+template <class T, class... A> SF_HD sf_arr<T, (int)sizeof...(A)> sf_arr_of(const A&... a) { return {{T(a)...}}; }
+// A swizzle as an `out` or `inout` argument (§6.1.1): the function works on a vector of its own, which is written back through
+// the swizzle when the call's full expression ends. Anything else is passed as it is.
+template <class S, class V>
+struct sf_out_arg {
+    S& target; V value;
+    SF_HD explicit sf_out_arg(S& s) : target(s), value(s) {}
+    SF_HD ~sf_out_arg() { target = value; }
+    SF_HD operator V&() { return value; }
+};
+template <class T, class V, int P, int... I> SF_HD sf_out_arg<SwzT<T, V, P, I...>, V> sf_out(SwzT<T, V, P, I...>& s) { return sf_out_arg<SwzT<T, V, P, I...>, V>(s); }
+template <class X> SF_HD X& sf_out(X& x) { return x; }
+
 // `.length()` of arrays and vectors (the translator writes length_of(name))
 template <class T, int N> SF_HD constexpr int length_of(const T (&)[N]) { return N; }
+template <class T, int N> SF_HD constexpr int length_of(const sf_arr<T, N>&) { return N; }
 SF_HD constexpr int length_of(const vec2&) { return 2; }
 SF_HD constexpr int length_of(const vec3&) { return 3; }
 SF_HD constexpr int length_of(const vec4&) { return 4; }
@@ -228,6 +272,10 @@ SF_HD uint to_uint(float x) { return (x != x || x <= 0.0f) ? 0u : ((x >= 4294967
 SF_HD uint to_uint(int x) { return (uint)x; }
 SF_HD uint to_uint(uint x) { return x; }
 SF_HD uint to_uint(bool x) { return x ? 1u : 0u; }
+// … of a vector: its first component (a swizzle converts to its vector first)
+#define SF_RT_FIRST(V) SF_HD int to_int(const V& v) { return to_int(v.d[0]); } SF_HD uint to_uint(const V& v) { return to_uint(v.d[0]); }
+SF_RT_FIRST(vec2) SF_RT_FIRST(vec3) SF_RT_FIRST(vec4) SF_RT_FIRST(ivec2) SF_RT_FIRST(ivec3) SF_RT_FIRST(ivec4) SF_RT_FIRST(uvec2) SF_RT_FIRST(uvec3) SF_RT_FIRST(uvec4)
+#undef SF_RT_FIRST
 SF_HD ivec2::ivec2(const vec2& v) { x = sf::to_int(v.x); y = sf::to_int(v.y); }
 SF_HD ivec3::ivec3(const vec3& v) { x = sf::to_int(v.x); y = sf::to_int(v.y); z = sf::to_int(v.z); }
 SF_HD ivec4::ivec4(const vec4& v) { x = sf::to_int(v.x); y = sf::to_int(v.y); z = sf::to_int(v.z); w = sf::to_int(v.w); }
@@ -516,8 +564,15 @@ struct matn {
     SF_HD explicit matn(const matn<W, M>& o) {
         for (int j = 0; j < N; j++) for (int i = 0; i < N; i++) c[j].d[i] = (i < M && j < M) ? o.c[j].d[i] : ((i == j) ? 1.0f : 0.0f);
     }
+    // mat2 from one vec4 (§5.4.2: the components fill the matrix in column-major order)
+    template <int M = N, typename std::enable_if<M == 2, int>::type = 0>
+    SF_HD explicit matn(const vec4& v) { c[0] = V(v.x, v.y); c[1] = V(v.z, v.w); }
     SF_HD V& operator[](int j) { return c[j]; }
     SF_HD const V& operator[](int j) const { return c[j]; }
+    SF_HD matn& operator++() { for (int j = 0; j < N; j++) ++c[j]; return *this; }
+    SF_HD matn& operator--() { for (int j = 0; j < N; j++) --c[j]; return *this; }
+    SF_HD matn operator++(int) { const matn before = *this; ++*this; return before; }
+    SF_HD matn operator--(int) { const matn before = *this; --*this; return before; }
     SF_HD matn& operator*=(const matn& o) { *this = *this*o; return *this; }
     SF_HD matn& operator*=(float s) { for (int j = 0; j < N; j++) c[j] *= s; return *this; }
     SF_HD matn& operator/=(float s) { for (int j = 0; j < N; j++) c[j] /= s; return *this; }

@@ -14,15 +14,32 @@ with `opengl.program`, falling back to `missing.glsl` on errors). Without a driv
      * `in/out/inout` parameter qualifiers become values and references, precision/layout/interpolation qualifiers go,
      * `uniform`/`in`/`out` declarations go (the members exist already), prototypes go,
      * `int(x)`/`uint(x)` become `to_int(x)`/`to_uint(x)` (defined results for NaN and overflow),
-     * array constructors `T[n](…)` become `{…}`, `T[n] name` becomes `T name[n]`,
+     * arrays are values in GLSL (§4.1.9, §5.8-5.9) and become the header's `sf_arr<T,n>`: `T name[n]`, `T[n] name`, `T[n] a, b`
+       and `T w[] = T[](…)` as locals, globals, members, parameters (an `in` array is the callee's copy) and return types; the
+       constructor `T[n](a, b)` becomes `sf_arr_of<T>(a, b)`; `x.length()` of any postfix expression becomes `length_of(x)`,
+     * a struct gets `bool operator==(const S&) const = default;` (§5.9: member by member),
+     * a swizzle passed for an `out`/`inout` parameter of one of the fragment's functions (or of `modf`) goes through `sf_out(…)`,
+       which hands the function a vector and writes it back through the swizzle after the call,
      * `const` scalars with literal initialisers become `static constexpr` (array bounds),
-     * `discard` sets a flag and returns, identifiers that are C++ keywords get a trailing underscore.
+     * `discard` sets a flag and returns, identifiers that are C++ keywords get a trailing underscore,
+     * a `#define` continued with backslash-newline is spliced; `#line` before every function body (and after a directive inside
+       one) keeps `__LINE__` and the compiler's messages on the lines of the GLSL text.
 2. `compile()` runs hipcc (`--genco`, the flags of csrc/Makefile) and caches the code object by content hash;
    libshaderflow_hip loads it with `sfx_program_load`.
 
-What is not supported raises `TranslationError` (the caller logs it and binds the `missing` kernel, like the reference
-does for a GLSL compile error): geometry beyond one fullscreen quad, arrays as function
-return values, uniform arrays, more than 16 samplers or 64 uniform floats, non-square matrices.
+The rule (tests/language_cases.py holds it row by row): a fragment that is valid GLSL 3.30 computes GLSL's value, or
+`translate()` refuses it by name with a `TranslationError` (the caller logs it and binds the `missing` kernel, like the reference
+does for a GLSL compile error) — nothing is left to fail inside hipcc seconds later. Refused:
+     * `&&` next to `^^` without parentheses (`^^` is written `!=`, which binds tighter than `&&`),
+     * a C++ keyword used as an identifier together with its renamed form (`new` and `new_`),
+     * an array without a size whose initialiser is not an array constructor (`float b[] = a;`),
+     * non-square matrices and samplers other than `sampler2D` (the types do not exist here),
+     * uniforms of other types than scalars, vectors, square matrices and `sampler2D`, uniform arrays of more than one dimension or
+       with a size that is no literal or literal `const int`, uniform initialisers that are no literal constant expressions, more
+       than 16 samplers or 64 uniform floats.
+Known limits that are not refused: there is no geometry beyond one fullscreen quad; `out`/`inout` parameters are references, so a
+function that writes one and then reads the same variable under its global name sees its own write, where GLSL copies out on
+return; `%` of a negative operand, undefined in GLSL, is C's.
 """
 from __future__ import annotations
 
@@ -180,12 +197,188 @@ def _is_length_call(tokens: list[Tok], dot: int) -> bool:
     return open_ < len(tokens) and tokens[open_].text == "(" and close < len(tokens) and tokens[close].text == ")"
 
 
-def _rewrite_tokens(tokens: list[Tok], structs: set[str]) -> list[Tok]:
+_QUALIFIERS = {"in", "out", "inout", "const"} | _DROPPED_QUALIFIERS
+_SWIZZLE = re.compile(r"[xyzw]{2,4}|[rgba]{2,4}|[stpq]{2,4}")
+_BUILTIN_OUT_PARAMETERS = {"modf": {1}}
+_STATEMENT_WORDS = {"return", "if", "else", "while", "for", "do", "switch", "case"}
+
+
+def _split_top_level(tokens: list[Tok]) -> list[list[Tok]]:
+    """the token runs between the commas that are inside no bracket"""
+    parts, depth, current = [], 0, []
+    for t in tokens:
+        if t.kind == "op" and t.text in ("(", "[", "{"):
+            depth += 1
+        elif t.kind == "op" and t.text in (")", "]", "}"):
+            depth -= 1
+        if t.kind == "op" and t.text == "," and depth == 0:
+            parts.append(current); current = []
+        else:
+            current.append(t)
+    if any(t.kind not in ("ws", "comment") for t in current):
+        parts.append(current)
+    return parts
+
+
+def _postfix_start(out: list[Tok]) -> int:
+    """index in `out` where the postfix expression that ends `out` begins: `s.w`, `a[1].b`, `f(x)[2]`, `name`"""
+    k = len(out)
+    while True:
+        j = _significant(out, k - 1, -1)
+        if j < 0:
+            return k
+        t = out[j]
+        if t.kind == "op" and t.text in (")", "]"):
+            depth = 0
+            while j >= 0:
+                if out[j].kind == "op" and out[j].text in (")", "]"):
+                    depth += 1
+                elif out[j].kind == "op" and out[j].text in ("(", "["):
+                    depth -= 1
+                    if depth == 0:
+                        break
+                j -= 1
+            if j < 0:
+                raise TranslationError("unbalanced bracket before .length()")
+            k = j
+        elif t.kind == "ident" and t.text not in _STATEMENT_WORDS:
+            k = j
+            dot = _significant(out, j - 1, -1)
+            if dot >= 0 and out[dot].kind == "op" and out[dot].text == ".":
+                k = dot
+                continue
+            return k
+        else:
+            return k
+
+
+def out_parameters(tokens: list[Tok], types: set[str]) -> dict[str, set[int]]:
+    """function name → positions of its `out` / `inout` parameters (every overload of a name together), the built-ins' included"""
+    found = {name: set(positions) for name, positions in _BUILTIN_OUT_PARAMETERS.items()}
+    depth = 0
+    for k, t in enumerate(tokens):
+        if t.kind == "op" and t.text in "{}":
+            depth += 1 if t.text == "{" else -1
+        elif depth == 0 and t.kind == "ident" and t.text in types:
+            name = _significant(tokens, k + 1)
+            if name < len(tokens) and tokens[name].kind == "op" and tokens[name].text == "[":
+                name = _significant(tokens, _matching(tokens, name, "[", "]") + 1)
+            open_ = _significant(tokens, name + 1)
+            if open_ < len(tokens) and tokens[name].kind == "ident" and tokens[open_].kind == "op" and tokens[open_].text == "(":
+                parameters = _split_top_level(tokens[open_ + 1:_matching(tokens, open_, "(", ")")])
+                positions = {i for i, p in enumerate(parameters) if any(w.kind == "ident" and w.text in ("out", "inout") for w in p)}
+                if positions:
+                    found.setdefault(tokens[name].text, set()).update(positions)
+    return found
+
+
+def _is_swizzle(tokens: list[Tok]) -> bool:
+    """the expression ends in a swizzle of two to four components (`v.zw`, `m[1].yx`)"""
+    last = _significant(tokens, len(tokens) - 1, -1)
+    dot = _significant(tokens, last - 1, -1) if last > 0 else -1
+    return dot >= 0 and tokens[last].kind == "ident" and bool(_SWIZZLE.fullmatch(tokens[last].text)) and tokens[dot].kind == "op" and tokens[dot].text == "."
+
+
+def _declarators(tokens: list[Tok], start: int, types: set[str]) -> tuple[list, int]:
+    """the declarators from the name at tokens[start]: [(name, tokens of `[size]` or None, tokens of the initialiser or None)] and
+    the index of the token that ends them (`;`, `)`, the comma before the next parameter, `(` of a function head)"""
+    found = []
+    k = start
+    while True:
+        j = _significant(tokens, k + 1)
+        size = initialiser = None
+        if j < len(tokens) and tokens[j].kind == "op" and tokens[j].text == "[":
+            close = _matching(tokens, j, "[", "]")
+            size = tokens[j + 1:close]
+            j = _significant(tokens, close + 1)
+        if j < len(tokens) and tokens[j].kind == "op" and tokens[j].text == "=":
+            depth, end = 0, j + 1
+            while end < len(tokens):
+                text = tokens[end].text if tokens[end].kind == "op" else ""
+                if text in ("(", "[", "{"):
+                    depth += 1
+                elif text in (")", "]", "}"):
+                    if depth == 0:
+                        break
+                    depth -= 1
+                elif depth == 0 and text in (",", ";"):
+                    break
+                end += 1
+            initialiser = tokens[j + 1:end]
+            j = end
+        found.append((tokens[k], size, initialiser))
+        if j < len(tokens) and tokens[j].kind == "op" and tokens[j].text == ",":
+            name = _significant(tokens, j + 1)
+            after = _significant(tokens, name + 1)
+            if (after < len(tokens) and tokens[name].kind == "ident" and tokens[name].text not in types | _QUALIFIERS
+                    and tokens[after].kind == "op" and tokens[after].text in ("[", "=", ",", ";")):
+                k = name
+                continue
+        return found, j
+
+
+def _constructor_length(name: str, initialiser: Optional[list[Tok]]) -> str:
+    """the size of `T name[] = T[n](…)` or `= T[](a, b, c)`"""
+    words = [t for t in (initialiser or []) if t.kind not in ("ws", "comment")]
+    if len(words) > 3 and words[1].text == "[":
+        close = _matching(words, 1, "[", "]")
+        if close + 1 < len(words) and words[close + 1].text == "(":
+            if close > 2:
+                return "".join(t.text for t in words[2:close])
+            return str(len(_split_top_level(words[close + 2:_matching(words, close + 1, "(", ")")])))
+    raise TranslationError(f"array '{name}' is declared without a size: its initialiser must be an array constructor")
+
+
+def _array_declaration(tokens: list[Tok], k: int, types: set[str], structs: set[str], outs: dict, out: list[Tok]) -> Optional[int]:
+    """`T a[3], b`, `T[2] p, q`, `T w[] = T[](…)`, `T[2] f(` at tokens[k] == T → `sf_arr<T,3> a; T b`, `sf_arr<T,2> p, q`, … appended to
+    `out`; returns the index of the last token it took, or None when no array is declared there (the text then stays as it is)"""
+    nxt = _significant(tokens, k + 1)
+    prefix = None
+    first = nxt
+    if tokens[nxt].kind == "op":
+        close = _matching(tokens, nxt, "[", "]")
+        first = _significant(tokens, close + 1)
+        prefix = tokens[nxt + 1:close]
+    if first >= len(tokens) or tokens[first].kind != "ident":
+        return None
+    found, end = _declarators(tokens, first, types)
+    if prefix is None and all(size is None for (_, size, _) in found):
+        return None
+    before = _significant(out, len(out) - 1, -1)
+    constant = "const " if before >= 0 and out[before].kind == "ident" and out[before].text == "const" else ""
+    emitted: list[Tok] = []
+    previous = None
+    for (name, size, initialiser) in found:
+        bound = size if size is not None else prefix
+        type_ = tokens[k].text
+        if bound is not None:
+            length = re.sub(r"\s+", "", _text(_rewrite_tokens(bound, structs, outs))) or _constructor_length(name.text, initialiser)
+            type_ = f"sf_arr<{type_},{length}>"
+        declared = _text(_rewrite_tokens([name], structs, outs))
+        if previous is not None:                                   # one C++ declaration cannot mix `sf_arr<T,3> a` with `T b`
+            emitted.append(Tok("op", ", " if type_ == previous else f"; {constant}"))
+        if type_ != previous:
+            emitted += [Tok("ident", type_), Tok("ws", " ")]
+        emitted.append(Tok("ident", declared))
+        if initialiser is not None:
+            emitted += [Tok("ws", " "), Tok("op", "=")] + _rewrite_tokens(initialiser, structs, outs)
+        previous = type_
+    dropped = _text(tokens[k:end]).count("\n") - _text(emitted).count("\n")      # keep the line count of the source
+    out.extend(emitted)
+    if dropped > 0:
+        out.append(Tok("ws", "\n"*dropped))
+    return end - 1
+
+
+def _rewrite_tokens(tokens: list[Tok], structs: set[str], outs: Optional[dict] = None, uniform: bool = False) -> list[Tok]:
     out: list[Tok] = []
     k = 0
     types = _TYPES | structs
+    outs = outs or {}
     while k < len(tokens):
         t = tokens[k]
+        if t.kind == "op" and t.text == ";":
+            uniform = False
         if t.kind == "comment":
             out.append(Tok("ws", "\n"*t.text.count("\n") or " "))
         elif t.kind == "number":
@@ -208,18 +401,42 @@ def _rewrite_tokens(tokens: list[Tok], structs: set[str]) -> list[Tok]:
                         raise TranslationError("`&&` next to `^^` without parentheses: write (a && b) ^^ c")
                     j += step
             out.append(Tok("op", "!="))
-        elif t.kind == "op" and t.text == "." and _is_length_call(tokens, k) and out and out[-1].kind == "ident":
-            # `name.length()` of an array or vector (§4.1.9, §5.5) → length_of(name) (jit_runtime.hpp)
-            name = out.pop()
-            out.append(Tok("ident", f"length_of({name.text})"))
+        elif t.kind == "op" and t.text == "." and _is_length_call(tokens, k) and _postfix_start(out) < len(out):
+            # `name.length()`, `s.member.length()` of an array or vector (§4.1.9, §5.5) → length_of(name) (jit_runtime.hpp)
+            start = _postfix_start(out)
+            operand = _text(out[start:]).strip()
+            del out[start:]
+            out.append(Tok("ident", f"length_of({operand})"))
             k = _matching(tokens, _significant(tokens, _significant(tokens, k + 1) + 1), "(", ")")
         elif t.kind == "ident":
             nxt = _significant(tokens, k + 1)
             following = tokens[nxt].text if nxt < len(tokens) else ""
-            if t.text in _DROPPED_QUALIFIERS:
+            before = _significant(tokens, k - 1, -1)
+            taken = None
+            if t.text in types and not uniform and nxt < len(tokens) and (following == "[" or tokens[nxt].kind == "ident"):
+                taken = _array_declaration(tokens, k, types, structs, outs, out)
+            if taken is not None:
+                k = taken
+            elif t.text in _DROPPED_QUALIFIERS:
                 pass
+            elif t.text == "uniform":
+                uniform = True
+                out.append(t)
             elif t.text == "layout" and following == "(":
-                k = _matching(tokens, nxt, "(", ")")
+                close = _matching(tokens, nxt, "(", ")")
+                out.append(Tok("ws", "\n"*_text(tokens[k:close]).count("\n") or " "))
+                k = close
+            elif t.text in outs and following == "(" and not (before >= 0 and tokens[before].kind == "ident" and tokens[before].text in types):
+                # a call of a function with `out` / `inout` parameters: a swizzle in such a position goes through sf_out (jit_runtime.hpp)
+                close = _matching(tokens, nxt, "(", ")")
+                out += [t, Tok("op", "(")]
+                for position, argument in enumerate(_split_top_level(tokens[nxt + 1:close])):
+                    inner = _rewrite_tokens(argument, structs, outs)
+                    if position:
+                        out.append(Tok("op", ","))
+                    out += [Tok("ident", "sf_out"), Tok("op", "("), *inner, Tok("op", ")")] if position in outs[t.text] and _is_swizzle(argument) else inner
+                out.append(Tok("op", ")"))
+                k = close
             elif t.text in _CPP_ONLY_KEYWORDS:
                 out.append(Tok("ident", t.text + "_"))
             elif t.text == "main":
@@ -227,17 +444,20 @@ def _rewrite_tokens(tokens: list[Tok], structs: set[str]) -> list[Tok]:
             elif t.text in ("int", "uint") and following == "(":
                 out.append(Tok("ident", "to_" + t.text))
             elif t.text in types and following == "[":
-                # `T[n](a, b)` array constructor → `{a, b}`;  `T[n] name` → `T name[n]`
+                # `T[n](a, b)` array constructor → `sf_arr_of<T>(a, b)` (jit_runtime.hpp; in a uniform's initialiser, which is only
+                # read here, `{a, b}`);  `uniform T[n] name` → `T name[n]`
                 close = _matching(tokens, nxt, "[", "]")
                 after = _significant(tokens, close + 1)
                 if after < len(tokens) and tokens[after].text == "(":
                     end = _matching(tokens, after, "(", ")")
-                    inner = _rewrite_tokens(tokens[after + 1:end], structs)
-                    out.append(Tok("op", "{")); out.extend(inner); out.append(Tok("op", "}"))
+                    inner = _rewrite_tokens(tokens[after + 1:end], structs, outs)
+                    out += [Tok("op", "{")] if uniform else [Tok("ident", f"sf_arr_of<{t.text}>"), Tok("op", "(")]
+                    out.extend(inner)
+                    out.append(Tok("op", "}" if uniform else ")"))
                     k = end
                 elif after < len(tokens) and tokens[after].kind == "ident":
                     out.append(t); out.append(Tok("ws", " ")); out.append(Tok("ident", tokens[after].text))
-                    out.extend(_rewrite_tokens(tokens[nxt:close + 1], structs))
+                    out.extend(_rewrite_tokens(tokens[nxt:close + 1], structs, outs))
                     k = after
                 else:
                     out.append(t)
@@ -256,8 +476,8 @@ def _text(tokens: Iterable[Tok]) -> str:
 # ---- function heads ---------------------------------------------------------------------------------------------------
 
 def _rewrite_parameters(tokens: list[Tok]) -> list[Tok]:
-    """`in T a, out T b, inout T c, const in T d, T e[3], out T f[3]` → `T a, T& b, T& c, const T d, const T (&e)[3], T (&f)[3]`
-    (an `in` array is a copy in GLSL; here it is a view that cannot be written, which a compiler error reports if a fragment does)"""
+    """`in T a, out T b, inout T c, const in T d` → `T a, T& b, T& c, const T d`. Array parameters arrive as `sf_arr<T,3> e` and
+    `out sf_arr<T,3> f` (_array_declaration) and follow the same rule: an `in` array is the function's own copy, as in GLSL"""
     out: list[Tok] = []
     parameter: list[Tok] = []
 
@@ -268,15 +488,8 @@ def _rewrite_parameters(tokens: list[Tok]) -> list[Tok]:
         reference = any(t.kind == "ident" and t.text in ("out", "inout") for t in words)
         constant = any(t.kind == "ident" and t.text == "const" for t in words)
         core = [t for t in words if not (t.kind == "ident" and t.text in ("in", "out", "inout", "const"))]
-        bracket = next((i for i, t in enumerate(core) if t.kind == "op" and t.text == "["), None)
-        if bracket is None:
-            type_, rest = core[0], core[1:]
-            text = ("const " if constant and not reference else "") + type_.text + ("&" if reference else "") + " " + _text(rest)
-        else:
-            if bracket < 2:
-                raise TranslationError(f"unnamed array parameter: {_text(parameter).strip()!r}")
-            type_, name, bounds = core[0], core[bracket - 1], core[bracket:]
-            text = ("" if reference else "const ") + f"{type_.text} (&{name.text}){_text(bounds)}"
+        type_, rest = core[0], core[1:]
+        text = ("const " if constant and not reference else "") + type_.text + ("&" if reference else "") + " " + _text(rest)
         if out:
             out.append(Tok("op", ", "))
         out.append(Tok("ident", text))
@@ -298,22 +511,6 @@ def _rewrite_parameters(tokens: list[Tok]) -> list[Tok]:
 # ---- the global scope -------------------------------------------------------------------------------------------------
 
 _CONSTANT_TOKENS = re.compile(r"^[-+*/%()\s\d.eEfFuUxXa-fA-F<>&|^~!?:]*$")
-
-
-def _count_initialisers(tokens: list[Tok]) -> int:
-    """number of top-level elements of the brace list starting at tokens[0] == '{'"""
-    end = _matching(tokens, 0, "{", "}")
-    depth, count, any_token = 0, 0, False
-    for t in tokens[1:end]:
-        if t.kind == "op" and t.text in "([{":
-            depth += 1
-        elif t.kind == "op" and t.text in ")]}":
-            depth -= 1
-        elif t.kind == "op" and t.text == "," and depth == 0:
-            count += 1
-        if t.kind not in ("ws",):
-            any_token = True
-    return count + 1 if any_token else 0
 
 
 class _Translator:
@@ -381,11 +578,6 @@ class _Translator:
                         if type_ == "int" and part.partition("=")[2].strip().isdigit():
                             self.constant_values[part.partition("=")[0].strip()] = int(part.partition("=")[2])
                     return f"\nstatic constexpr {type_} {', '.join(p.strip() for p in parts)};"
-        # members cannot deduce an array bound from their initialiser: write it out
-        match = re.search(r"\[\s*\]\s*=\s*\{", text)
-        if match:
-            brace = next(i for i, t in enumerate(tokens) if t.kind == "op" and t.text == "{")
-            text = text[:match.start()] + f"[{_count_initialisers(tokens[brace:])}] = {{" + text[match.end():]
         return text
 
     @staticmethod
@@ -405,9 +597,17 @@ class _Translator:
         return parts
 
     def struct(self, tokens: list[Tok]) -> str:
-        return _text(tokens)
+        """`==` and `!=` of two structs compare member by member (§5.9): C++20 writes that comparison itself"""
+        words = [k for k, t in enumerate(tokens) if t.kind not in ("ws", "comment")]
+        open_ = next((k for k in words if tokens[k].kind == "op" and tokens[k].text == "{"), None)
+        if open_ is None or len(words) < 3 or tokens[words[1]].kind != "ident" or words[2] != open_:
+            return _text(tokens)
+        close = _matching(tokens, open_, "{", "}")
+        return _text(tokens[:close]) + f" SF_HD bool operator==(const {tokens[words[1]].text}&) const = default; " + _text(tokens[close:])
 
-    def function(self, head: list[Tok], body: list[Tok]) -> str:
+    def function(self, head: list[Tok], body: list[Tok], line: int) -> str:
+        """`line`: the fragment's line of the body's opening brace. A `#line` there (and after every directive inside the body, which
+        takes lines of its own here) keeps `__LINE__` (§3.3) and the compiler's messages on the lines of the GLSL text"""
         open_ = next(i for i, t in enumerate(head) if t.kind == "op" and t.text == "(")
         close = _matching(head, open_, "(", ")")
         before = head[:open_]
@@ -415,22 +615,24 @@ class _Translator:
         parameters = _rewrite_parameters(head[open_ + 1:close])
         if _text(parameters).strip() == "void":
             parameters = []
-        body_text = self.function_body(body, return_type)
-        return "\nSF_HD " + _text(before).lstrip() + "(" + _text(parameters) + ")" + _text(head[close + 1:]) + body_text
+        body_text = self.function_body(body, return_type, line)
+        return "\nSF_HD " + _text(before).lstrip() + "(" + _text(parameters) + ")" + _text(head[close + 1:]).rstrip() + f"\n#line {line}\n" + body_text
 
-    def function_body(self, body: list[Tok], return_type: str) -> str:
+    def function_body(self, body: list[Tok], return_type: str, line: int) -> str:
         out = []
         for t in body:
+            line += t.text.count("\n")
             if t.kind == "ident" and t.text == "discard":
                 # the invocation ends in GLSL; here the flag makes the result transparent whatever the callers still compute
                 out.append("{ discarded_ = true; return; }" if return_type == "void" else "{ discarded_ = true; return {}; }")
             elif t.kind == "pp":
-                out.append("\n" + self.preprocessor(t.text).strip("\n") + "\n")
+                out.append("\n" + self.preprocessor(t.text).strip("\n") + f"\n#line {line + 1}")
             else:
                 out.append(t.text)
         return "".join(out)
 
     def preprocessor(self, text: str) -> str:
+        text = re.sub(r"\\\r?\n", " ", text)                       # a continued line (§3.1) is one line
         stripped = text.strip()
         directive = re.match(r"#\s*(\w+)", stripped)
         name = directive.group(1) if directive else ""
@@ -470,8 +672,19 @@ class _Translator:
                 nxt = _significant(raw, k + 1)
                 if nxt < len(raw) and raw[nxt].kind == "ident":
                     self.structs.add(raw[nxt].text)
-        tokens = _rewrite_tokens(raw, self.structs)
+        names = {t.text for t in raw if t.kind == "ident"}
+        missing = sorted(name for name in names if re.fullmatch(r"mat[234]x[234]|[iu]?sampler(?:[123]D|Cube|Buffer|2DRect|2DMS)(?:Array)?(?:Shadow)?", name)
+                         and name not in _TYPES)
+        if missing:
+            raise TranslationError(f"type {', '.join(missing)}: only float, int, uint and bool scalars and vectors, square float matrices and sampler2D exist here")
+        for word in sorted(_CPP_ONLY_KEYWORDS & names):
+            if word + "_" in names:
+                raise TranslationError(f"identifiers '{word}' and '{word}_': '{word}' is a C++ keyword and is renamed to '{word}_' here; rename one of the two")
+        tokens = _rewrite_tokens(raw, self.structs, out_parameters(raw, _TYPES | self.structs))
         k, statement = 0, []
+        lines = [1]                                                # lines[k]: the fragment's line tokens[k] starts on (the rewrites keep newlines)
+        for t in tokens:
+            lines.append(lines[-1] + t.text.count("\n"))
         while k < len(tokens):
             t = tokens[k]
             if t.kind == "pp":
@@ -488,7 +701,7 @@ class _Translator:
                 elif texts and texts[0] == "struct":               # struct definition (up to its ';')
                     statement.extend(tokens[k:end + 1])
                 elif "(" in texts:                                 # function definition
-                    self.body.append(self.function(statement, tokens[k:end + 1])); statement = []
+                    self.body.append(self.function(statement, tokens[k:end + 1], lines[k])); statement = []
                 else:
                     raise TranslationError(f"unexpected block after {_text(statement).strip()!r}")
                 k = end
@@ -566,7 +779,7 @@ class _Translator:
                 bindings.append(Binding(name, type_, next_float, count, integer, default=defaults[0] if defaults else None))
                 next_float += count
             else:
-                members.append(f"    {type_} {name}[{length}];")
+                members.append(f"    sf_arr<{type_},{length}> {name};")
                 for index in range(length):
                     loads.append(load(f"{name}[{index}]", next_float))
                     bindings.append(Binding(f"{name}[{index}]", type_, next_float, count, integer,
@@ -648,7 +861,7 @@ def _sampler_worth_a_tile(code: str, samplers: list[Binding]) -> Optional[Bindin
     # helper functions that tap a sampler PARAMETER (`vec4 blur(sampler2D tex, vec2 uv) { for (…) … texture(tex, …) }`): the taps
     # count for whatever sampler a call passes in that position, once more heavily when the call itself sits in a loop
     helpers = []                                               # (name, position of the sampler parameter, weight of its taps)
-    for definition in re.finditer(r"\bSF_HD\s+[\w:<>]+\s+(\w+)\s*\(([^()]*)\)\s*(?:const\s*)?\{", code):
+    for definition in re.finditer(r"\bSF_HD\s+[\w:<>,]+\s+(\w+)\s*\(([^()]*)\)\s*(?:const\s*)?(?:#line \d+\s*)?\{", code):
         body_end = _closing_in_text(code, definition.end() - 1, "{", "}")
         for position, parameter in enumerate(_split_arguments(definition.group(2))):
             declared = re.fullmatch(r"\s*(?:const\s+)?sampler2D\s*&?\s*(\w+)\s*", parameter)

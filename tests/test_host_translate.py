@@ -33,7 +33,8 @@ def test_parameter_qualifiers_become_values_and_references():
     assert "SF_HD void main_()" in out
     arrays = body(G.translate("float total(float values[3], const in vec2 pair[2]) { return values[0] + pair[1].x; }\n"
                               "void fill(out float values[3], inout vec2 p) { values[0] = p.x; }\nvoid main() {}").cpp)
-    assert "SF_HD float total(const float (&values)[3], const vec2 (&pair)[2])" in arrays and "SF_HD void fill(float (&values)[3], vec2& p)" in arrays
+    # arrays are values (csrc/jit_runtime.hpp sf_arr): an `in` array is the function's own copy, as in GLSL
+    assert "SF_HD float total(sf_arr<float,3> values, const sf_arr<vec2,2> pair)" in arrays and "SF_HD void fill(sf_arr<float,3>& values, vec2& p)" in arrays
 
 
 def test_declarations_of_the_engine_go_and_globals_become_members():
@@ -110,9 +111,10 @@ def test_arrays_casts_keywords_and_discard():
         fragColor = vec4(WEIGHTS[index]*new + float(bits), PAIR[1].xy, ray.direction.z);
     }"""
     out = body(G.translate(source).cpp)
-    assert "const float WEIGHTS[3] = {0.25f, 0.5f, 0.25f};" in out
-    assert re.search(r"vec3 PAIR\[2\] = \{vec3\(0\), vec3\(1\)\};", out)
-    assert "float taps[3] = {1.0f, 2.0f, 3.0f};" in out
+    out = re.sub(r" +", " ", out)
+    assert "const sf_arr<float,3> WEIGHTS = sf_arr_of<float>(0.25f, 0.5f, 0.25f);" in out
+    assert "sf_arr<vec3,2> PAIR = sf_arr_of<vec3>(vec3(0), vec3(1));" in out
+    assert "sf_arr<float,3> taps = sf_arr_of<float>(1.0f, 2.0f, 3.0f);" in out
     assert "to_int(fragCoord.x) % 3" in out and "to_uint(index) << 2u" in out and "float(bits)" in out
     assert "float new_ = 1.0f;" in out and "bool not_ = false;" in out and "WEIGHTS[index]*new_" in out
     assert "{ discarded_ = true; return; }" in out
@@ -157,7 +159,7 @@ def test_uniform_initialisers_and_uniform_arrays():
     assert by_name["steps"].default == (3.0,) and by_name["steps"].integer and by_name["enabled"].default == (1.0,)
     assert [by_name[f"weights[{k}]"].default for k in range(3)] == [(0.25,), (0.5,), (0.125,)] and by_name["weights[2]"].array == "weights"
     assert by_name["offsets[1]"].default is None and by_name["offsets[1]"].count == 2 and by_name["offsets[1]"].slot == by_name["offsets[0]"].slot + 2
-    assert "float weights[3];" in translation.cpp and "vec2 offsets[2];" in translation.cpp
+    assert "sf_arr<float,3> weights;" in translation.cpp and "sf_arr<vec2,2> offsets;" in translation.cpp
     for bad in ("uniform float g = sqrt(2.0);\nvoid main() {}", "uniform float w[2] = float[](1.0);\nvoid main() {}",
                 "uniform vec3 t = 1.0;\nvoid main() {}", "uniform float m[2][2];\nvoid main() {}"):
         with pytest.raises(G.TranslationError):
