@@ -6,7 +6,8 @@ with `opengl.program`, falling back to `missing.glsl` on errors). Without a driv
 
 1. `translate()` rewrites the fragment token by token into the body of a C++ struct that derives from
    `sf::rt::FragmentBase` (csrc/jit_runtime.hpp): globals and uniforms become members, functions become member
-   functions, `main` becomes `main_`. GLSL and C++ share almost all of their expression and statement syntax; the
+   functions, `main` becomes `main_`. It cuts the fragment's own tokens into the items of the global scope first (directives,
+   declarations, prototypes, functions), rewrites and emits each by its kind, and assembles the struct around them. GLSL and C++ share almost all of their expression and statement syntax; the
    header supplies the vector types (with swizzles), the built-in functions on the deterministic binary32 routines of
    csrc/sfmath.hpp, the whole sampler2D column of the §8.7 texture lookups (explicit lod, bias, gradients, offsets, projection,
    fetches of any level: csrc/glsl.hpp "THE RULES") and the reference's prelude, so what is rewritten is small:
@@ -43,6 +44,9 @@ return; `%` of a negative operand, undefined in GLSL, is C's.
 """
 from __future__ import annotations
 
+import ast
+import bisect
+import builtins
 import hashlib
 import os
 import re
@@ -140,6 +144,10 @@ class Tok:
     kind: str
     text: str
 
+    def is_op(self, *texts: str) -> bool:
+        """the operator `x`, or one of these operators"""
+        return self.kind == "op" and self.text in texts
+
 
 def tokenize(source: str) -> list[Tok]:
     tokens, position = [], 0
@@ -159,23 +167,40 @@ def _float_literal(text: str) -> str:
         text = text[:-2]
     if text[-1] in "fF":
         return text
-    if ("." in text) or ("e" in text) or ("E" in text):
-        return text + ("f" if "." in text or "e" in text.lower() else "")
-    return text
+    return text + "f" if "." in text or "e" in text.lower() else text
 
 
 def _matching(tokens: list[Tok], start: int, open_: str, close: str) -> int:
     """index of the token closing the bracket opened at `start`"""
     depth = 0
     for k in range(start, len(tokens)):
-        if tokens[k].kind == "op":
-            if tokens[k].text == open_:
-                depth += 1
-            elif tokens[k].text == close:
-                depth -= 1
-                if depth == 0:
-                    return k
+        if tokens[k].is_op(open_, close):
+            depth += 1 if tokens[k].text == open_ else -1
+            if depth == 0:
+                return k
     raise TranslationError(f"unbalanced {open_!r}")
+
+
+_BRACKETS = (("(", "[", "{"), (")", "]", "}"))
+
+
+def _scan(tokens: list[Tok], start: int, step: int, stops: tuple = ()) -> int:
+    """index of the first token from `start` (inclusive) in direction `step` that is one of the operators `stops` outside every
+    bracket passed on the way, or the bracket that closes the enclosing one; len(tokens) / -1 if there is none"""
+    opening, closing = _BRACKETS[::step]
+    depth, k = 0, start
+    while 0 <= k < len(tokens):
+        text = tokens[k].text if tokens[k].kind == "op" else None
+        if text in opening:
+            depth += 1
+        elif text in closing:
+            if depth == 0:
+                break
+            depth -= 1
+        elif depth == 0 and text in stops:
+            break
+        k += step
+    return k
 
 
 def _significant(tokens: list[Tok], start: int, step: int = 1) -> int:
@@ -205,18 +230,13 @@ _STATEMENT_WORDS = {"return", "if", "else", "while", "for", "do", "switch", "cas
 
 def _split_top_level(tokens: list[Tok]) -> list[list[Tok]]:
     """the token runs between the commas that are inside no bracket"""
-    parts, depth, current = [], 0, []
-    for t in tokens:
-        if t.kind == "op" and t.text in ("(", "[", "{"):
-            depth += 1
-        elif t.kind == "op" and t.text in (")", "]", "}"):
-            depth -= 1
-        if t.kind == "op" and t.text == "," and depth == 0:
-            parts.append(current); current = []
-        else:
-            current.append(t)
-    if any(t.kind not in ("ws", "comment") for t in current):
-        parts.append(current)
+    parts, start, k = [], 0, _scan(tokens, 0, 1, (",",))
+    while k < len(tokens) and tokens[k].is_op(","):
+        parts.append(tokens[start:k])
+        start = k + 1
+        k = _scan(tokens, start, 1, (",",))
+    if any(t.kind not in ("ws", "comment") for t in tokens[start:]):
+        parts.append(tokens[start:])
     return parts
 
 
@@ -225,58 +245,23 @@ def _postfix_start(out: list[Tok]) -> int:
     k = len(out)
     while True:
         j = _significant(out, k - 1, -1)
-        if j < 0:
-            return k
-        t = out[j]
-        if t.kind == "op" and t.text in (")", "]"):
-            depth = 0
-            while j >= 0:
-                if out[j].kind == "op" and out[j].text in (")", "]"):
-                    depth += 1
-                elif out[j].kind == "op" and out[j].text in ("(", "["):
-                    depth -= 1
-                    if depth == 0:
-                        break
-                j -= 1
-            if j < 0:
+        if j >= 0 and out[j].is_op(")", "]"):
+            k = _scan(out, j - 1, -1)
+            if k < 0:
                 raise TranslationError("unbalanced bracket before .length()")
-            k = j
-        elif t.kind == "ident" and t.text not in _STATEMENT_WORDS:
-            k = j
-            dot = _significant(out, j - 1, -1)
-            if dot >= 0 and out[dot].kind == "op" and out[dot].text == ".":
-                k = dot
-                continue
-            return k
+        elif j >= 0 and out[j].kind == "ident" and out[j].text not in _STATEMENT_WORDS:
+            k = _significant(out, j - 1, -1)
+            if k < 0 or not out[k].is_op("."):
+                return j
         else:
             return k
-
-
-def out_parameters(tokens: list[Tok], types: set[str]) -> dict[str, set[int]]:
-    """function name → positions of its `out` / `inout` parameters (every overload of a name together), the built-ins' included"""
-    found = {name: set(positions) for name, positions in _BUILTIN_OUT_PARAMETERS.items()}
-    depth = 0
-    for k, t in enumerate(tokens):
-        if t.kind == "op" and t.text in "{}":
-            depth += 1 if t.text == "{" else -1
-        elif depth == 0 and t.kind == "ident" and t.text in types:
-            name = _significant(tokens, k + 1)
-            if name < len(tokens) and tokens[name].kind == "op" and tokens[name].text == "[":
-                name = _significant(tokens, _matching(tokens, name, "[", "]") + 1)
-            open_ = _significant(tokens, name + 1)
-            if open_ < len(tokens) and tokens[name].kind == "ident" and tokens[open_].kind == "op" and tokens[open_].text == "(":
-                parameters = _split_top_level(tokens[open_ + 1:_matching(tokens, open_, "(", ")")])
-                positions = {i for i, p in enumerate(parameters) if any(w.kind == "ident" and w.text in ("out", "inout") for w in p)}
-                if positions:
-                    found.setdefault(tokens[name].text, set()).update(positions)
-    return found
 
 
 def _is_swizzle(tokens: list[Tok]) -> bool:
     """the expression ends in a swizzle of two to four components (`v.zw`, `m[1].yx`)"""
     last = _significant(tokens, len(tokens) - 1, -1)
     dot = _significant(tokens, last - 1, -1) if last > 0 else -1
-    return dot >= 0 and tokens[last].kind == "ident" and bool(_SWIZZLE.fullmatch(tokens[last].text)) and tokens[dot].kind == "op" and tokens[dot].text == "."
+    return dot >= 0 and tokens[last].kind == "ident" and bool(_SWIZZLE.fullmatch(tokens[last].text)) and tokens[dot].is_op(".")
 
 
 def _declarators(tokens: list[Tok], start: int, types: set[str]) -> tuple[list, int]:
@@ -287,31 +272,20 @@ def _declarators(tokens: list[Tok], start: int, types: set[str]) -> tuple[list, 
     while True:
         j = _significant(tokens, k + 1)
         size = initialiser = None
-        if j < len(tokens) and tokens[j].kind == "op" and tokens[j].text == "[":
+        if j < len(tokens) and tokens[j].is_op("["):
             close = _matching(tokens, j, "[", "]")
             size = tokens[j + 1:close]
             j = _significant(tokens, close + 1)
-        if j < len(tokens) and tokens[j].kind == "op" and tokens[j].text == "=":
-            depth, end = 0, j + 1
-            while end < len(tokens):
-                text = tokens[end].text if tokens[end].kind == "op" else ""
-                if text in ("(", "[", "{"):
-                    depth += 1
-                elif text in (")", "]", "}"):
-                    if depth == 0:
-                        break
-                    depth -= 1
-                elif depth == 0 and text in (",", ";"):
-                    break
-                end += 1
+        if j < len(tokens) and tokens[j].is_op("="):
+            end = _scan(tokens, j + 1, 1, (",", ";"))
             initialiser = tokens[j + 1:end]
             j = end
         found.append((tokens[k], size, initialiser))
-        if j < len(tokens) and tokens[j].kind == "op" and tokens[j].text == ",":
+        if j < len(tokens) and tokens[j].is_op(","):
             name = _significant(tokens, j + 1)
             after = _significant(tokens, name + 1)
             if (after < len(tokens) and tokens[name].kind == "ident" and tokens[name].text not in types | _QUALIFIERS
-                    and tokens[after].kind == "op" and tokens[after].text in ("[", "=", ",", ";")):
+                    and tokens[after].is_op("[", "=", ",", ";")):
                 k = name
                 continue
         return found, j
@@ -352,7 +326,7 @@ def _array_declaration(tokens: list[Tok], k: int, types: set[str], structs: set[
         bound = size if size is not None else prefix
         type_ = tokens[k].text
         if bound is not None:
-            length = re.sub(r"\s+", "", _text(_rewrite_tokens(bound, structs, outs))) or _constructor_length(name.text, initialiser)
+            length = "".join(_text(_rewrite_tokens(bound, structs, outs)).split()) or _constructor_length(name.text, initialiser)
             type_ = f"sf_arr<{type_},{length}>"
         declared = _text(_rewrite_tokens([name], structs, outs))
         if previous is not None:                                   # one C++ declaration cannot mix `sf_arr<T,3> a` with `T b`
@@ -370,38 +344,25 @@ def _array_declaration(tokens: list[Tok], k: int, types: set[str], structs: set[
     return end - 1
 
 
-def _rewrite_tokens(tokens: list[Tok], structs: set[str], outs: Optional[dict] = None, uniform: bool = False) -> list[Tok]:
+def _rewrite_tokens(tokens: list[Tok], structs: set[str], outs: Optional[dict] = None) -> list[Tok]:
     out: list[Tok] = []
     k = 0
     types = _TYPES | structs
     outs = outs or {}
     while k < len(tokens):
         t = tokens[k]
-        if t.kind == "op" and t.text == ";":
-            uniform = False
         if t.kind == "comment":
             out.append(Tok("ws", "\n"*t.text.count("\n") or " "))
         elif t.kind == "number":
             out.append(Tok("number", _float_literal(t.text)))
-        elif t.kind == "op" and t.text == "^^":                       # logical exclusive or (§5.9): on bools that is `!=`
+        elif t.is_op("^^"):                                           # logical exclusive or (§5.9): on bools that is `!=`
             # `!=` binds tighter than `&&`, `^^` looser: refuse the one spelling where that would change the meaning silently
             for step in (-1, 1):
-                depth, j = 0, k + step
-                while 0 <= j < len(tokens):
-                    text = tokens[j].text if tokens[j].kind == "op" else ""
-                    if text in ("(", "[") if step == 1 else text in (")", "]"):
-                        depth += 1
-                    elif text in (")", "]") if step == 1 else text in ("(", "["):
-                        if depth == 0:
-                            break
-                        depth -= 1
-                    elif depth == 0 and text in (";", ",", "?", ":", "=", "||", "{", "}"):
-                        break
-                    elif depth == 0 and text == "&&":
-                        raise TranslationError("`&&` next to `^^` without parentheses: write (a && b) ^^ c")
-                    j += step
+                j = _scan(tokens, k + step, step, (";", ",", "?", ":", "=", "||", "&&"))
+                if 0 <= j < len(tokens) and tokens[j].is_op("&&"):
+                    raise TranslationError("`&&` next to `^^` without parentheses: write (a && b) ^^ c")
             out.append(Tok("op", "!="))
-        elif t.kind == "op" and t.text == "." and _is_length_call(tokens, k) and _postfix_start(out) < len(out):
+        elif t.is_op(".") and _is_length_call(tokens, k) and _postfix_start(out) < len(out):
             # `name.length()`, `s.member.length()` of an array or vector (§4.1.9, §5.5) → length_of(name) (jit_runtime.hpp)
             start = _postfix_start(out)
             operand = _text(out[start:]).strip()
@@ -413,15 +374,12 @@ def _rewrite_tokens(tokens: list[Tok], structs: set[str], outs: Optional[dict] =
             following = tokens[nxt].text if nxt < len(tokens) else ""
             before = _significant(tokens, k - 1, -1)
             taken = None
-            if t.text in types and not uniform and nxt < len(tokens) and (following == "[" or tokens[nxt].kind == "ident"):
+            if t.text in types and nxt < len(tokens) and (following == "[" or tokens[nxt].kind == "ident"):
                 taken = _array_declaration(tokens, k, types, structs, outs, out)
             if taken is not None:
                 k = taken
             elif t.text in _DROPPED_QUALIFIERS:
                 pass
-            elif t.text == "uniform":
-                uniform = True
-                out.append(t)
             elif t.text == "layout" and following == "(":
                 close = _matching(tokens, nxt, "(", ")")
                 out.append(Tok("ws", "\n"*_text(tokens[k:close]).count("\n") or " "))
@@ -437,28 +395,18 @@ def _rewrite_tokens(tokens: list[Tok], structs: set[str], outs: Optional[dict] =
                     out += [Tok("ident", "sf_out"), Tok("op", "("), *inner, Tok("op", ")")] if position in outs[t.text] and _is_swizzle(argument) else inner
                 out.append(Tok("op", ")"))
                 k = close
-            elif t.text in _CPP_ONLY_KEYWORDS:
+            elif t.text in _CPP_ONLY_KEYWORDS or t.text == "main":
                 out.append(Tok("ident", t.text + "_"))
-            elif t.text == "main":
-                out.append(Tok("ident", "main_"))
             elif t.text in ("int", "uint") and following == "(":
                 out.append(Tok("ident", "to_" + t.text))
             elif t.text in types and following == "[":
-                # `T[n](a, b)` array constructor → `sf_arr_of<T>(a, b)` (jit_runtime.hpp; in a uniform's initialiser, which is only
-                # read here, `{a, b}`);  `uniform T[n] name` → `T name[n]`
+                # `T[n](a, b)` array constructor → `sf_arr_of<T>(a, b)` (jit_runtime.hpp)
                 close = _matching(tokens, nxt, "[", "]")
                 after = _significant(tokens, close + 1)
                 if after < len(tokens) and tokens[after].text == "(":
                     end = _matching(tokens, after, "(", ")")
-                    inner = _rewrite_tokens(tokens[after + 1:end], structs, outs)
-                    out += [Tok("op", "{")] if uniform else [Tok("ident", f"sf_arr_of<{t.text}>"), Tok("op", "(")]
-                    out.extend(inner)
-                    out.append(Tok("op", "}" if uniform else ")"))
+                    out += [Tok("ident", f"sf_arr_of<{t.text}>"), Tok("op", "("), *_rewrite_tokens(tokens[after + 1:end], structs, outs), Tok("op", ")")]
                     k = end
-                elif after < len(tokens) and tokens[after].kind == "ident":
-                    out.append(t); out.append(Tok("ws", " ")); out.append(Tok("ident", tokens[after].text))
-                    out.extend(_rewrite_tokens(tokens[nxt:close + 1], structs, outs))
-                    k = after
                 else:
                     out.append(t)
             else:
@@ -475,42 +423,70 @@ def _text(tokens: Iterable[Tok]) -> str:
 
 # ---- function heads ---------------------------------------------------------------------------------------------------
 
-def _rewrite_parameters(tokens: list[Tok]) -> list[Tok]:
+def _rewrite_parameters(parameters: list[list[Tok]]) -> str:
     """`in T a, out T b, inout T c, const in T d` → `T a, T& b, T& c, const T d`. Array parameters arrive as `sf_arr<T,3> e` and
     `out sf_arr<T,3> f` (_array_declaration) and follow the same rule: an `in` array is the function's own copy, as in GLSL"""
-    out: list[Tok] = []
-    parameter: list[Tok] = []
-
-    def flush() -> None:
+    out = []
+    for parameter in parameters:
         words = [t for t in parameter if t.kind not in ("ws", "comment")]
         if not words:
-            return
+            continue
         reference = any(t.kind == "ident" and t.text in ("out", "inout") for t in words)
         constant = any(t.kind == "ident" and t.text == "const" for t in words)
         core = [t for t in words if not (t.kind == "ident" and t.text in ("in", "out", "inout", "const"))]
-        type_, rest = core[0], core[1:]
-        text = ("const " if constant and not reference else "") + type_.text + ("&" if reference else "") + " " + _text(rest)
-        if out:
-            out.append(Tok("op", ", "))
-        out.append(Tok("ident", text))
-
-    depth = 0
-    for t in tokens:
-        if t.kind == "op" and t.text in "([":
-            depth += 1
-        elif t.kind == "op" and t.text in ")]":
-            depth -= 1
-        if t.kind == "op" and t.text == "," and depth == 0:
-            flush(); parameter = []
-        else:
-            parameter.append(t)
-    flush()
-    return out
+        out.append(("const " if constant and not reference else "") + core[0].text + ("&" if reference else "") + " " + _text(core[1:]))
+    return ", ".join(out)
 
 
 # ---- the global scope -------------------------------------------------------------------------------------------------
 
-_CONSTANT_TOKENS = re.compile(r"^[-+*/%()\s\d.eEfFuUxXa-fA-F<>&|^~!?:]*$")
+_STORAGE_QUALIFIERS = {"uniform", "in", "out", "varying", "attribute", "const"}
+_LITERAL_OPERATORS = set("-+*/%()<>&|^~!?:.")
+_LITERAL_WORD = set("0123456789abcdefABCDEFuUxX")                  # the characters of a number: a word spelled with them alone counts as one
+
+
+@dataclass
+class _Item:
+    """One piece of the global scope, cut from the fragment's own tokens"""
+    kind: str                                    # "directive", "declaration" (… `;`), "prototype", "function", "text" (what a directive cuts short)
+    tokens: list[Tok]                            # all of it; of a function or prototype what stands before the `(`
+    qualifiers: set = field(default_factory=set)         # of a declaration: its storage qualifiers, the index of its type in `tokens`
+    type: int = 0
+    parameters: list = field(default_factory=list)       # of a function or prototype: one token run each
+    tail: list = field(default_factory=list)     # of a function: what stands between `)` and `{`, `{` … `}`, the fragment's line of that `{`
+    body: list = field(default_factory=list)
+    line: int = 0
+
+
+def _storage(tokens: list[Tok]) -> tuple[set, int]:
+    """the storage qualifiers a declaration begins with and the index of what follows them, its type; the qualifiers C++ lacks and
+    `layout(…)` are passed over"""
+    qualifiers, k = set(), 0
+    while k < len(tokens):
+        t, nxt = tokens[k], _significant(tokens, k + 1)
+        if t.kind == "ident" and t.text in _STORAGE_QUALIFIERS:
+            qualifiers.add(t.text)
+        elif t.kind == "ident" and t.text == "layout" and nxt < len(tokens) and tokens[nxt].is_op("("):
+            k = _matching(tokens, nxt, "(", ")")
+        elif not (t.kind in ("ws", "comment") or (t.kind == "ident" and t.text in _DROPPED_QUALIFIERS)):
+            break
+        k += 1
+    return qualifiers, k
+
+
+def out_parameters(items: list[_Item], types: set[str]) -> dict[str, set[int]]:
+    """function name → positions of its `out` / `inout` parameters (every overload of a name together, prototypes too), the built-ins'
+    included. A function counts where a type stands before its name (`T name(`, `T[n] name(`), not one a macro names (`REAL name(`)"""
+    found = {name: set(positions) for name, positions in _BUILTIN_OUT_PARAMETERS.items()}
+    for item in items:
+        positions = {i for i, p in enumerate(item.parameters) if any(w.kind == "ident" and w.text in ("out", "inout") for w in p)}
+        name = _significant(item.tokens, len(item.tokens) - 1, -1)
+        word = _significant(item.tokens, name - 1, -1)
+        if word >= 0 and item.tokens[word].is_op("]"):
+            word = _significant(item.tokens, _scan(item.tokens, word - 1, -1) - 1, -1)
+        if positions and word >= 0 and item.tokens[word].text in types and item.tokens[name].kind == "ident":
+            found.setdefault(item.tokens[name].text, set()).update(positions)
+    return found
 
 
 class _Translator:
@@ -521,102 +497,147 @@ class _Translator:
         self.structs: set[str] = set()
         self.constants: set[str] = set()
         self.constant_values: dict[str, int] = {}                    # `const int N = 3;` → array sizes of uniform declarations
-        self.declared_uniforms: list[tuple[str, str, str]] = []     # (type, name, default text)
+        self.declared_uniforms: list[tuple] = []                    # (type, tokens of the declarator, those of the initialiser or None)
         self.macros: list[str] = []
         self.identifiers: set[str] = set()
+        self.outs: dict[str, set[int]] = {}
+        # for the tile heuristic: the functions that take a sampler2D (name, [(position, parameter)], first and last offset of the body in
+        # the emitted text)
+        self.helpers: list[tuple] = []
 
-    # a statement of the global scope that ends in ';'
-    def declaration(self, tokens: list[Tok]) -> str:
-        first = _significant(tokens, 0)
-        if first >= len(tokens):
-            return _text(tokens)
-        words = [t.text for t in tokens if t.kind == "ident"]
-        head = tokens[first].text
-        if head == "precision":
-            return ""
-        qualifiers = set()
-        k = first
-        while k < len(tokens) and (tokens[k].kind in ("ws",) or (tokens[k].kind == "ident" and tokens[k].text in ("uniform", "in", "out", "varying", "attribute", "const"))):
-            if tokens[k].kind == "ident":
-                qualifiers.add(tokens[k].text)
+    def rewritten(self, tokens: list[Tok]) -> list[Tok]:
+        return _rewrite_tokens(tokens, self.structs, self.outs)
+
+    def text(self, tokens: list[Tok]) -> str:
+        return _text(self.rewritten(tokens))
+
+    # ---- cut: the raw tokens → items
+
+    def statement(self, tokens: list[Tok]) -> _Item:
+        """what ends in `;` at the global scope"""
+        qualifiers, k = _storage(tokens)
+        words = [t for t in tokens[k:] if t.kind not in ("ws", "comment")]
+        open_ = next((j for j in range(k, len(tokens)) if tokens[j].is_op("(")), None)
+        declares = qualifiers & (_STORAGE_QUALIFIERS - {"const"}) or any(t.is_op("=") for t in words)
+        named = len(qualifiers) + sum(t.kind == "ident" for t in words) >= 2
+        if open_ is not None and not declares and named and words[-2].is_op(")"):        # prototype: `T name(params);`
+            return _Item("prototype", tokens[:open_], qualifiers, k, _split_top_level(tokens[open_ + 1:_matching(tokens, open_, "(", ")")]))
+        return _Item("declaration", tokens, qualifiers, k)
+
+    def cut(self, raw: list[Tok]) -> list[_Item]:
+        items: list[_Item] = []
+        lines = [1]                                                # lines[k]: the fragment's line raw[k] starts on
+        for t in raw:
+            lines.append(lines[-1] + t.text.count("\n"))
+        k = start = 0
+        while k < len(raw):
+            t = raw[k]
+            if t.kind == "pp":
+                items += [_Item("text", raw[start:k]), _Item("directive", [t])]
+                start = k + 1
+            elif t.is_op(";"):
+                items.append(self.statement(raw[start:k + 1]))
+                start = k + 1
+            elif t.is_op("{"):
+                end = _matching(raw, k, "{", "}")
+                head = raw[start:k]
+                words = [s for s in head if s.kind not in ("ws", "comment")]
+                # a brace initialiser of a global and a struct definition (up to its ';') are part of the statement
+                if not any(s.is_op("=") for s in words) and not (words and words[0].text == "struct"):
+                    first = _storage(head)[1]
+                    open_ = next((j for j in range(first, len(head)) if head[j].is_op("(")), None)
+                    if open_ is None:
+                        raise TranslationError(f"unexpected block after {_text(_rewrite_tokens(head, self.structs)).strip()!r}")
+                    close = _matching(head, open_, "(", ")")
+                    items.append(_Item("function", head[:open_], parameters=_split_top_level(head[open_ + 1:close]), tail=head[close + 1:],
+                                       body=raw[k:end + 1], line=lines[k]))
+                    start = end + 1
+                k = end
             k += 1
-        rest = tokens[k:]
-        if "uniform" in qualifiers:
-            type_index = _significant(rest, 0)
-            type_ = rest[type_index].text
-            names = _text(rest[type_index + 1:-1])
-            for part in self._split_commas(names):
-                name, _, default = part.partition("=")
-                self.declared_uniforms.append((type_, name.strip(), default.strip()))
-            return ""
-        if qualifiers & {"in", "out", "varying", "attribute"}:
-            type_index = _significant(rest, 0)
-            names = [n.strip() for n in self._split_commas(_text(rest[type_index + 1:-1]))]
-            unknown = [n for n in names if n.split("[")[0].strip() not in BUILTIN_MEMBERS]
-            return (f"\n{rest[type_index].text} {', '.join(unknown)};" if unknown else "")
-        # prototype: `T name(params);` without an initialiser
-        texts = [t.text for t in tokens if t.kind not in ("ws",)]
-        if "=" not in texts and "(" in texts and texts[-2] == ")" and len(words) >= 2:
-            return ""
-        if head == "struct":
-            return self.struct(tokens)
-        text = _text(tokens)
-        if "const" in qualifiers:
-            type_index = _significant(rest, 0)
-            type_ = rest[type_index].text
-            if type_ in ("int", "float", "bool", "uint") and "[" not in texts:
-                parts = self._split_commas(_text(rest[type_index + 1:-1]))
-                constant = True
-                for part in parts:
-                    name, _, init = part.partition("=")
-                    probe = re.sub(r"\b(?:%s|true|false)\b" % "|".join(sorted(self.constants) or ["__none__"]), "1", init)
-                    probe = re.sub(r"\bto_u?int\b|\bfloat\b|\bbool\b", "", probe)
-                    constant = constant and bool(init.strip()) and bool(_CONSTANT_TOKENS.match(probe))
-                if constant:
-                    for part in parts:
-                        self.constants.add(part.partition("=")[0].strip())
-                        if type_ == "int" and part.partition("=")[2].strip().isdigit():
-                            self.constant_values[part.partition("=")[0].strip()] = int(part.partition("=")[2])
-                    return f"\nstatic constexpr {type_} {', '.join(p.strip() for p in parts)};"
-        return text
+        if _significant(raw, start) < len(raw):
+            raise TranslationError(f"unterminated declaration: {_text(raw[start:]).strip()[:60]!r}")
+        return items
 
-    @staticmethod
-    def _split_commas(text: str) -> list[str]:
-        parts, depth, current = [], 0, ""
-        for ch in text:
-            if ch in "([{":
-                depth += 1
-            elif ch in ")]}":
-                depth -= 1
-            if ch == "," and depth == 0:
-                parts.append(current); current = ""
-            else:
-                current += ch
-        if current.strip():
-            parts.append(current)
-        return parts
+    # ---- rewrite and emit, by kind
+
+    def declaration(self, item: _Item) -> str:
+        tokens = item.tokens
+        head, type_ = tokens[_significant(tokens, 0)].text, tokens[item.type].text
+        if head == "precision" or item.kind == "prototype":
+            return ""
+        first, prefix = _significant(tokens, item.type + 1), []
+        if "uniform" in item.qualifiers and type_ in _TYPES | self.structs and first < len(tokens) and tokens[first].is_op("["):
+            close = _matching(tokens, first, "[", "]")         # `uniform T[n] a, b` is `uniform T a[n], b`: b is no array here
+            first, prefix = close + 1, tokens[first:close + 1]
+        # the declarators, and in each where its `=` stands
+        parts = [(part, next((k for k, t in enumerate(part) if t.is_op("=")), len(part))) for part in _split_top_level(tokens[first:-1])]
+        if "uniform" in item.qualifiers:
+            for (part, eq) in parts:
+                name = min(_significant(part, 0) + 1, eq)
+                # (the name behind `T[n]` keeps its spelling, that of a C++ keyword too)
+                spelled = [part[name - 1]] if prefix and name else self.rewritten(part[:name])
+                spelled, prefix = spelled + self.rewritten(prefix + part[name:eq]), []
+                self.declared_uniforms.append((type_, spelled, part[eq + 1:] if eq < len(part) else None))
+            return ""
+        if item.qualifiers & {"in", "out", "varying", "attribute"}:
+            names = [self.text(part).strip() for (part, _) in parts]
+            if any(t.is_op("[", "=") for t in tokens):
+                # an array among them, which no fragment here has: the members as the array rewrite spells them, cut at the top-level
+                # commas of that text (those of `sf_arr<T,n>` included) and joined again, which keeps such a fragment's text and cache key
+                spelled = self.rewritten(tokens)
+                at = _storage(spelled)[1]
+                type_, names = spelled[at].text, [_text(run).strip() for run in _split_top_level(tokenize(_text(spelled[at + 1:-1])))]
+            unknown = [n for n in names if n.split("[")[0].strip() not in BUILTIN_MEMBERS]
+            return f"\n{type_} {', '.join(unknown)};" if unknown else ""
+        if head == "struct":
+            return self.struct(self.rewritten(tokens))
+        if "const" in item.qualifiers and type_ in ("int", "float", "bool", "uint") and not any(t.is_op("[") for t in tokens):
+            if all(self.literal(part[eq + 1:]) for (part, eq) in parts):
+                for (part, eq) in parts:
+                    name, value = part[_significant(part, 0)].text, [t.text for t in part[eq + 1:] if t.kind not in ("ws", "comment")]
+                    self.constants.add(name)
+                    if type_ == "int" and len(value) == 1 and value[0].isdigit():
+                        self.constant_values[name] = int(value[0])
+                return f"\nstatic constexpr {type_} {', '.join(self.text(part).strip() for (part, _) in parts)};"
+        return self.text(tokens)
+
+    def literal(self, tokens: list[Tok]) -> bool:
+        """An initialiser that `static constexpr` can take: numbers, `true`, `false`, earlier such constants, `float`, `bool`, `int(` and
+        `uint(`, and operators other than assignments, comparisons with `=`, `^^`, commas and brackets other than `()`"""
+        words = [t for t in tokens if t.kind not in ("ws", "comment")]
+
+        def passes(k: int, t: Tok) -> bool:
+            if t.kind == "ident":
+                return (t.text in self.constants or t.text in ("true", "false", "float", "bool") or set(t.text) <= _LITERAL_WORD
+                        or (t.text in ("int", "uint") and k + 1 < len(words) and words[k + 1].is_op("(")))
+            return t.kind == "number" or (t.kind == "op" and t.text != "^^" and set(t.text) <= _LITERAL_OPERATORS)
+        return bool(words) and all(passes(k, t) for k, t in enumerate(words))
 
     def struct(self, tokens: list[Tok]) -> str:
         """`==` and `!=` of two structs compare member by member (§5.9): C++20 writes that comparison itself"""
         words = [k for k, t in enumerate(tokens) if t.kind not in ("ws", "comment")]
-        open_ = next((k for k in words if tokens[k].kind == "op" and tokens[k].text == "{"), None)
+        open_ = next((k for k in words if tokens[k].is_op("{")), None)
         if open_ is None or len(words) < 3 or tokens[words[1]].kind != "ident" or words[2] != open_:
             return _text(tokens)
         close = _matching(tokens, open_, "{", "}")
         return _text(tokens[:close]) + f" SF_HD bool operator==(const {tokens[words[1]].text}&) const = default; " + _text(tokens[close:])
 
-    def function(self, head: list[Tok], body: list[Tok], line: int) -> str:
-        """`line`: the fragment's line of the body's opening brace. A `#line` there (and after every directive inside the body, which
-        takes lines of its own here) keeps `__LINE__` (§3.3) and the compiler's messages on the lines of the GLSL text"""
-        open_ = next(i for i, t in enumerate(head) if t.kind == "op" and t.text == "(")
-        close = _matching(head, open_, "(", ")")
-        before = head[:open_]
+    def function(self, item: _Item) -> str:
+        """A `#line` before the body (and after every directive inside it, which takes lines of its own here) keeps `__LINE__` (§3.3)
+        and the compiler's messages on the lines of the GLSL text"""
+        before = self.rewritten(item.tokens)
         return_type = next((t.text for t in before if t.kind == "ident"), "void")
-        parameters = _rewrite_parameters(head[open_ + 1:close])
-        if _text(parameters).strip() == "void":
-            parameters = []
-        body_text = self.function_body(body, return_type, line)
-        return "\nSF_HD " + _text(before).lstrip() + "(" + _text(parameters) + ")" + _text(head[close + 1:]).rstrip() + f"\n#line {line}\n" + body_text
+        runs = [[t for t in self.rewritten(run) if t.kind not in ("ws", "comment")] for run in item.parameters]
+        parameters = _rewrite_parameters(runs)
+        head = ("\nSF_HD " + _text(before).lstrip() + "(" + ("" if parameters.strip() == "void" else parameters) + ")"
+                + self.text(item.tail).rstrip() + f"\n#line {item.line}\n")
+        body = self.function_body(self.rewritten(item.body), return_type, item.line)
+        declared = [[t.text for t in run if t.text not in ("in", "out", "inout", "const")] for run in runs if run]
+        samplers = [(position, words[1]) for position, words in enumerate(declared) if len(words) == 2 and words[0] == "sampler2D"]
+        if samplers:                                               # for the tile heuristic: its taps are those of what a call passes
+            first = sum(len(piece) for piece in self.body) + len(head)
+            self.helpers.append((before[_significant(before, len(before) - 1, -1)].text, samplers, first + 1, first + len(body)))
+        return head + body
 
     def function_body(self, body: list[Tok], return_type: str, line: int) -> str:
         out = []
@@ -680,36 +701,15 @@ class _Translator:
         for word in sorted(_CPP_ONLY_KEYWORDS & names):
             if word + "_" in names:
                 raise TranslationError(f"identifiers '{word}' and '{word}_': '{word}' is a C++ keyword and is renamed to '{word}_' here; rename one of the two")
-        tokens = _rewrite_tokens(raw, self.structs, out_parameters(raw, _TYPES | self.structs))
-        k, statement = 0, []
-        lines = [1]                                                # lines[k]: the fragment's line tokens[k] starts on (the rewrites keep newlines)
-        for t in tokens:
-            lines.append(lines[-1] + t.text.count("\n"))
-        while k < len(tokens):
-            t = tokens[k]
-            if t.kind == "pp":
-                self.body.append(_text(statement)); statement = []
-                self.body.append("\n" + self.preprocessor(t.text).strip("\n") + "\n")
-            elif t.kind == "op" and t.text == ";":
-                statement.append(t)
-                self.body.append(self.declaration(statement)); statement = []
-            elif t.kind == "op" and t.text == "{":
-                end = _matching(tokens, k, "{", "}")
-                texts = [s.text for s in statement if s.kind != "ws"]
-                if "=" in texts:                                   # brace initialiser of a global: part of the statement
-                    statement.extend(tokens[k:end + 1])
-                elif texts and texts[0] == "struct":               # struct definition (up to its ';')
-                    statement.extend(tokens[k:end + 1])
-                elif "(" in texts:                                 # function definition
-                    self.body.append(self.function(statement, tokens[k:end + 1], lines[k])); statement = []
-                else:
-                    raise TranslationError(f"unexpected block after {_text(statement).strip()!r}")
-                k = end
+        items = self.cut(raw)
+        self.outs = out_parameters(items, _TYPES | self.structs)
+        for item in items:
+            if item.kind == "directive":
+                self.body.append("\n" + self.preprocessor(item.tokens[0].text).strip("\n") + "\n")
+            elif item.kind == "function":
+                self.body.append(self.function(item))
             else:
-                statement.append(t)
-            k += 1
-        if _text(statement).strip():
-            raise TranslationError(f"unterminated declaration: {_text(statement).strip()[:60]!r}")
+                self.body.append(self.text(item.tokens) if item.kind == "text" else self.declaration(item))
         return self.assemble()
 
     def _array_length(self, text: str) -> int:
@@ -727,9 +727,10 @@ class _Translator:
         seen: set[str] = set()
         next_float = 0
         free_samplers = [s for s in range(TEX_SLOTS) if s not in FIXED_SAMPLER_SLOTS.values()]
-        wanted = [(type_, name, "") for (type_, name) in self.pipeline] + self.declared_uniforms
-        declared_names = {name for (_, name, _) in self.declared_uniforms}
-        for (type_, name, default) in wanted:
+        wanted = [(type_, [Tok("ident", name)], None) for (type_, name) in self.pipeline] + self.declared_uniforms
+        declared_names = {_text(declarator).strip() for (_, declarator, _) in self.declared_uniforms}
+        for (type_, declarator, default) in wanted:
+            name = _text(declarator).strip()
             if name in seen or name in BUILTIN_MEMBERS:
                 continue
             if name not in self.identifiers and name not in declared_names:
@@ -749,10 +750,10 @@ class _Translator:
                 loads.append(f"{name} = sampler_({slot});")
                 continue
             length = None                                          # `uniform T name[N]`: N elements, bound as name[0] … name[N-1]
-            array = re.fullmatch(r"(\w+)\s*\[\s*(\w+)\s*\]", name)
-            if array:
-                name = array.group(1)
-                length = self._array_length(array.group(2))
+            words = [t.text for t in declarator if t.kind != "ws"]
+            word = lambda text: text.replace("_", "a").isalnum()       # a name or a whole number
+            if len(words) == 4 and words[1::2] == ["[", "]"] and word(words[0]) and word(words[2]):
+                name, length = words[0], self._array_length(words[2])
             elif "[" in name:
                 raise TranslationError(f"uniform {name}: only one-dimensional arrays with a literal or constant size are supported")
             if type_ not in _UNIFORM_COUNTS:
@@ -760,7 +761,9 @@ class _Translator:
             count, integer = _UNIFORM_COUNTS[type_]
             if next_float + count*(length or 1) > USER_SLOTS:
                 raise TranslationError(f"more than {USER_SLOTS} floats of uniforms")
-            defaults = _constant_initialiser(type_, count, length, default, name) if default else None
+            defaults = None
+            if default and _significant(default, 0) < len(default):
+                defaults = _constant_initialiser(type_, count, length, default, name)
 
             def load(target: str, first: int) -> str:
                 getter = "user_int_" if integer else "user_"
@@ -789,7 +792,7 @@ class _Translator:
         undefs = "".join(f"#undef {m}\n" for m in dict.fromkeys(self.macros))
         derivatives = bool(self.identifiers & {'dFdx', 'dFdy', 'fwidth'})
         audio = bool(self.identifiers & AUDIO_UNIFORMS)
-        tiled = None if derivatives else _sampler_worth_a_tile(code, [b for b in bindings if b.type == "sampler2D"])
+        tiled = None if derivatives else _sampler_worth_a_tile(code, [b for b in bindings if b.type == "sampler2D"], self.helpers)
         cpp = ("// generated by shaderflow_amd/glsl2hip.py from a GLSL fragment\n"
                + (f"#define SF_JIT_TILE_SLOT {tiled.slot}      // {tiled.name}\n" if tiled else "") +
                "#include \"jit_runtime.hpp\"\n"
@@ -810,28 +813,28 @@ class _Translator:
 _TEXTURE_CALLS = r"(?:texture|textureLod|textureOffset|textureLodOffset|textureProj|textureProjOffset|gtexture|gmtexture|stexture|astexture|agtexture|agmtexture)"
 
 
-def _closing_in_text(code: str, at: int, opening: str, closing: str) -> int:
-    """index just past the bracket that closes the one at `at`"""
-    depth = 0
-    for k in range(at, len(code)):
-        if code[k] == opening:
-            depth += 1
-        elif code[k] == closing:
-            depth -= 1
-            if depth == 0:
-                return k + 1
-    return len(code)
+def _brackets(code: str, pair: str) -> tuple[list[int], list[Tok]]:
+    """the brackets of `pair` in the emitted text, for _closing: their offsets, and they as operator tokens"""
+    found = [(m.start(), Tok("op", m.group())) for m in re.finditer(f"[{re.escape(pair)}]", code)]
+    return [at for at, _ in found], [t for _, t in found]
 
 
-def _loop_bodies(code: str) -> list[tuple[int, int]]:
+def _closing(code: str, brackets: tuple[list[int], list[Tok]], at: int) -> int:
+    """index just past the bracket that closes the one at `at`, counting `brackets` alone; len(code) if none does"""
+    offsets, tokens = brackets
+    k = _scan(tokens, bisect.bisect_right(offsets, at), 1)
+    return offsets[k] + 1 if k < len(offsets) else len(code)
+
+
+def _loop_bodies(code: str, parentheses: tuple, braces: tuple) -> list[tuple[int, int]]:
     """(first, last) text ranges of the header and body of every for / while loop"""
     ranges = []
     for match in re.finditer(r"\b(?:for|while)\s*\(", code):
-        header_end = _closing_in_text(code, match.end() - 1, "(", ")")
+        header_end = _closing(code, parentheses, match.end() - 1)
         rest = code[header_end:]
         body = header_end + len(rest) - len(rest.lstrip())
         if body < len(code) and code[body] == "{":
-            end = _closing_in_text(code, body, "{", "}")
+            end = _closing(code, braces, body)
         else:
             semicolon = code.find(";", body)
             end = len(code) if semicolon < 0 else semicolon + 1
@@ -839,9 +842,10 @@ def _loop_bodies(code: str) -> list[tuple[int, int]]:
     return ranges
 
 
-def _sampler_worth_a_tile(code: str, samplers: list[Binding]) -> Optional[Binding]:
+def _sampler_worth_a_tile(code: str, samplers: list[Binding], helpers: list[tuple]) -> Optional[Binding]:
     """The sampler a tap-heavy fragment reads most (a blur or feedback kernel: taps inside the text of a loop, or eight and more
-    written out), or None. SHADERFLOW_JIT_TILE=0 turns the tile off, =<sampler name> forces it for that sampler.
+    written out), or None. SHADERFLOW_JIT_TILE=0 turns the tile off, =<sampler name> forces it for that sampler. `helpers`: the functions
+    that take a sampler2D, (name, [(position, parameter)], first and last offset of the body in `code`).
 
     The tile costs one extra evaluation of the fragment per block (jit_runtime.hpp JitShader::setup) and never changes a
     result, so the choice is about speed only: a single tap does not pay for the probe. Taps are `texture` and the prelude's
@@ -854,81 +858,71 @@ def _sampler_worth_a_tile(code: str, samplers: list[Binding]) -> Optional[Bindin
     forced = [b for b in samplers if b.name == wish or (b.name.endswith("0x0") and b.name[:-3] == wish)]
     if forced:
         return forced[0]
-    loops = _loop_bodies(code)
+    if not samplers:
+        return None
+    parentheses = _brackets(code, "()")
+    loops = _loop_bodies(code, parentheses, _brackets(code, "{}"))
     in_loop = lambda at: any(first <= at < last for (first, last) in loops)
     weight = lambda at: 16 if in_loop(at) else 1
     tap_on = lambda names: re.compile(rf"\b{_TEXTURE_CALLS}\s*\(\s*(?:{'|'.join(map(re.escape, names))})\b")
     # helper functions that tap a sampler PARAMETER (`vec4 blur(sampler2D tex, vec2 uv) { for (…) … texture(tex, …) }`): the taps
     # count for whatever sampler a call passes in that position, once more heavily when the call itself sits in a loop
-    helpers = []                                               # (name, position of the sampler parameter, weight of its taps)
-    for definition in re.finditer(r"\bSF_HD\s+[\w:<>,]+\s+(\w+)\s*\(([^()]*)\)\s*(?:const\s*)?(?:#line \d+\s*)?\{", code):
-        body_end = _closing_in_text(code, definition.end() - 1, "{", "}")
-        for position, parameter in enumerate(_split_arguments(definition.group(2))):
-            declared = re.fullmatch(r"\s*(?:const\s+)?sampler2D\s*&?\s*(\w+)\s*", parameter)
-            if declared:
-                taps = sum(weight(m.start()) for m in tap_on([declared.group(1)]).finditer(code, definition.end(), body_end))
-                if taps:
-                    helpers.append((definition.group(1), position, taps))
+    tapping = []                                               # (name, position of the sampler parameter, weight of its taps, its calls)
+    for (helper, parameters, first, last) in helpers:
+        calls = [(call.start(), _split_top_level(tokenize(code[call.end():_closing(code, parentheses, call.end() - 1) - 1])))
+                 for call in re.finditer(rf"\b{re.escape(helper)}\s*\(", code)]
+        for (position, parameter) in parameters:
+            taps = sum(weight(m.start()) for m in tap_on([parameter]).finditer(code, first, last))
+            if taps:
+                tapping.append((position, taps, calls))
     best, best_score = None, 0
     for binding in samplers:
         names = {binding.name, binding.name[:-3] if binding.name.endswith("0x0") else binding.name}
         score = sum(weight(m.start()) for m in tap_on(names).finditer(code))
-        for (helper, position, taps) in helpers:
-            for call in re.finditer(rf"\b{re.escape(helper)}\s*\(", code):
-                arguments = _split_arguments(code[call.end():_closing_in_text(code, call.end() - 1, "(", ")") - 1])
-                if position < len(arguments) and arguments[position].strip() in names:
-                    score += taps*weight(call.start())
+        for (position, taps, calls) in tapping:
+            for (at, arguments) in calls:
+                if position < len(arguments) and _text(arguments[position]).strip() in names:
+                    score += taps*weight(at)
         if score > best_score:
             best, best_score = binding, score
     return best if best_score >= 8 else None
 
 
-_SCALAR_OF = {"float": float, "int": int, "uint": int, "bool": bool}
-
-
-def _constant_scalar(text: str, name: str) -> float:
-    """A literal arithmetic expression of a uniform initialiser → its value (`-0.5`, `2.0*3.0`, `1e-3`, `true`, `3u`)"""
-    import ast
-    cleaned = re.sub(r"(?<=[0-9.])(?:lf|LF|[fFuU])\b", "", text.strip())
-    cleaned = re.sub(r"\btrue\b", "1", re.sub(r"\bfalse\b", "0", cleaned))
-    cleaned = re.sub(r"\b(?:float|int|uint|bool)\s*\(", "(", cleaned)
+def _constant_scalar(tokens: list[Tok], name: str) -> float:
+    """A literal arithmetic expression of a uniform initialiser → its value (`-0.5`, `2.0*3.0`, `1e-3`, `true`, `3u`, `float(2)`).
+    `int(…)` and `uint(…)` are conversions with results of their own here (to_int, to_uint) and no literals"""
+    spelled = []
+    for k, t in enumerate(tokens):
+        nxt = _significant(tokens, k + 1)
+        if t.kind == "comment":
+            spelled.append("\n"*t.text.count("\n") or " ")
+        elif t.kind == "ident" and t.text in ("true", "false"):
+            spelled.append("1" if t.text == "true" else "0")
+        elif t.kind == "ident" and t.text in ("float", "bool") and nxt < len(tokens) and tokens[nxt].is_op("("):
+            spelled.append("")
+        else:
+            spelled.append(t.text)
+    cleaned = re.sub(r"(?<=[0-9.])(?:lf|LF|[fFuU])\b", "", "".join(spelled).strip())
     try:
         tree = ast.parse(cleaned, mode="eval")
     except SyntaxError:
-        raise TranslationError(f"uniform {name}: initialiser '{text}' is not a literal constant expression") from None
+        raise TranslationError(f"uniform {name}: initialiser '{_text(tokens)}' is not a literal constant expression") from None
     allowed = (ast.Expression, ast.BinOp, ast.UnaryOp, ast.Constant, ast.Add, ast.Sub, ast.Mult, ast.Div, ast.USub, ast.UAdd)
     if not all(isinstance(node, allowed) for node in ast.walk(tree)):
-        raise TranslationError(f"uniform {name}: initialiser '{text}' is not a literal constant expression")
-    import builtins                                            # this module defines its own compile()
-    return float(eval(builtins.compile(tree, "<initialiser>", "eval"), {"__builtins__": {}}))
+        raise TranslationError(f"uniform {name}: initialiser '{_text(tokens)}' is not a literal constant expression")
+    return float(eval(builtins.compile(tree, "<initialiser>", "eval"), {"__builtins__": {}}))      # (this module defines its own compile())
 
 
-def _split_arguments(text: str) -> list[str]:
-    parts, depth, current = [], 0, ""
-    for ch in text:
-        if ch in "([":
-            depth += 1
-        elif ch in ")]":
-            depth -= 1
-        if ch == "," and depth == 0:
-            parts.append(current)
-            current = ""
-        else:
-            current += ch
-    if current.strip():
-        parts.append(current)
-    return parts
-
-
-def _constant_value(type_: str, count: int, text: str, name: str) -> tuple:
+def _constant_value(type_: str, count: int, tokens: list[Tok], name: str) -> tuple:
     """`T(…)` or a scalar expression → `count` numbers (vector constructors splat a single argument, matrices put it on the diagonal)"""
-    text = text.strip()
-    constructor = re.fullmatch(rf"{type_}\s*\((.*)\)", text, re.S)
+    first, last = _significant(tokens, 0), _significant(tokens, len(tokens) - 1, -1)
+    open_ = _significant(tokens, first + 1)
+    constructor = open_ < last and tokens[first].text == type_ and type_ not in ("int", "uint") and tokens[open_].is_op("(") and tokens[last].is_op(")")
     if count == 1:
-        return (_constant_scalar(constructor.group(1) if constructor else text, name),)
+        return (_constant_scalar(tokens[open_ + 1:last] if constructor else tokens[first:last + 1], name),)
     if not constructor:
-        raise TranslationError(f"uniform {name}: initialiser '{text}' must be a {type_}(…) constructor of literals")
-    arguments = [_constant_scalar(a, name) for a in _split_arguments(constructor.group(1))]
+        raise TranslationError(f"uniform {name}: initialiser '{_text(tokens).strip()}' must be a {type_}(…) constructor of literals")
+    arguments = [_constant_scalar(a, name) for a in _split_top_level(tokens[open_ + 1:last])]
     if len(arguments) == 1:
         if type_.startswith("mat"):
             side = int(type_[3])
@@ -939,15 +933,17 @@ def _constant_value(type_: str, count: int, text: str, name: str) -> tuple:
     return tuple(arguments)
 
 
-def _constant_initialiser(type_: str, count: int, length: Optional[int], text: str, name: str) -> list[tuple]:
+def _constant_initialiser(type_: str, count: int, length: Optional[int], tokens: list[Tok], name: str) -> list[tuple]:
     """The initialiser of a uniform declaration as one tuple per element (one element for a non-array)"""
     if length is None:
-        return [_constant_value(type_, count, text, name)]
-    # (array constructors reach this point already rewritten to C++ brace lists)
-    array = re.fullmatch(rf"{type_}\s*\[\s*\w*\s*\]\s*\((.*)\)", text.strip(), re.S) or re.fullmatch(r"\{(.*)\}", text.strip(), re.S)
-    if not array:
+        return [_constant_value(type_, count, tokens, name)]
+    first, last = _significant(tokens, 0), _significant(tokens, len(tokens) - 1, -1)
+    bracket = _significant(tokens, first + 1)
+    constructor = tokens[first].text in _TYPES and bracket < last and tokens[bracket].is_op("[")         # `T[n](…)`, `T[](…)`
+    open_ = _significant(tokens, _matching(tokens, bracket, "[", "]") + 1) if constructor else first       # … and a brace list is read as well
+    if not (open_ < last and tokens[open_].is_op("(" if constructor else "{") and _scan(tokens, open_ + 1, 1) == last):
         raise TranslationError(f"uniform {name}: an array initialiser must be written {type_}[](…)")
-    elements = _split_arguments(array.group(1))
+    elements = _split_top_level(tokens[open_ + 1:last])
     if len(elements) != length:
         raise TranslationError(f"uniform {name}: {len(elements)} initialisers for {length} elements")
     return [_constant_value(type_, count, element, name) for element in elements]
