@@ -4,7 +4,6 @@
 // capi_audio.hip, the piano roll in capi_piano.hip, the video staging in capi_video.hip; host_state.hpp holds what they share.
 
 #include "launch.hpp"
-#include "launch_geometry.hpp"
 #include "visualizer_kernels.hpp"
 #include "uniform_table.hpp"
 
@@ -697,31 +696,10 @@ static int launch_render(int fragment, const RenderArgs& a, int frames, hipStrea
     using namespace sfl;
     switch (fragment) {
         case FRAG_VISUALIZER: {
-            int tw = 0, th = 0;
-            {
-                const int fast = launch_visualizer_fast(g_launch_ctx, a, 1, frames, s, true);      // identity camera, RGBA8 target, window inside the strip kernel's tile
-                if (fast != 0) return fast < 0 ? fast : SFX_OK;
-            }
-            if (visualizer_tile_applicable(a.tex[TEX_BACKGROUND])) {
-                // first choice: 64 x 8 samples per block over a 64 x 15 tile — three 512-thread blocks per CU and two staged cells per
-                // sample, against two 256-thread blocks and five cells for the 128 x 2 shape (1080p without SSAA: 8.4 -> see DESIGN §7)
-                visualizer_window_bound(a, 64, 8, tw, th);
-                if (tw > 0 && tw <= 64 && th <= 15) return render_visualizer_tiled(TILED_R_64x15_WALK8, a, frames, s, 0);
-                // sparser outputs (720p over a 1080-row background: 1.3 texels per sample): the same block shape over a tile sized per
-                // launch, as long as two blocks share a CU — the 128 x 2 shape would need a 174 x 11 window there (one 256-thread block per CU)
-                if (tw > 0 && (size_t)tw*th*48 <= 76*1024) {
-                    RenderArgs d = a;
-                    d.tile_pitch = tw; d.tile_rows = th;
-                    return render_visualizer_tiled(TILED_R_DYNAMIC_WALK8, d, frames, s, (size_t)tw*th*48);
-                }
-                visualizer_window_bound(a, 128, 2, tw, th);
-            }
-            if (tw > 0 && tw <= 128 && th <= 10) return render_visualizer_tiled(TILED_R_128x10, a, frames, s, 0);
-            if (tw > 0 && (size_t)tw*th*48 <= VIS_LDS_LIMIT) {           // a window wider than the fixed tile: tile sized per launch
-                RenderArgs d = a;
-                d.tile_pitch = tw; d.tile_rows = th;
-                return render_visualizer_tiled(TILED_R_DYNAMIC, d, frames, s, (size_t)tw*th*48);
-            }
+            // the strip kernels (identity / axis camera, RGBA8 target, window inside one of their tiles), then the LDS-tiled shapes
+            int fast = launch_visualizer_fast(g_launch_ctx, a, 1, frames, s, true);
+            if (fast == 0) fast = launch_visualizer_tiled(a, 1, frames, s, true);
+            if (fast != 0) return fast < 0 ? fast : SFX_OK;
             return render_plain(fragment, a, frames, s);
         }
         case FRAG_MULTIPASS: {
@@ -738,21 +716,47 @@ static int launch_render(int fragment, const RenderArgs& a, int frames, hipStrea
     }
 }
 
-#ifndef VIS_ROLLED_LANE_COST
-#define VIS_ROLLED_LANE_COST 2.0f                                       // (see launch_fused: the shapes of rolled cameras)
-#endif
+static int launch_fused(int fragment, const RenderArgs& a, int ssaa, int frames, hipStream_t s, bool force_generic = false) {
+    using namespace sfl;
+    if (ssaa != 1 && ssaa != 2 && ssaa != 4) return fail(SFX_E_UNSUPPORTED, "fused ssaa %d", ssaa);
+    switch (fragment) {
+        case FRAG_DEFAULT:
+            if (!force_generic) {
+                const int fast = launch_separable(SEPARABLE_DEFAULT, g_launch_ctx, a, ssaa, frames, s);
+                if (fast != 0) return fast < 0 ? fast : SFX_OK;
+            }
+            return fused_plain(fragment, a, ssaa, frames, s);
+        case FRAG_VISUALIZER:
+            if (!force_generic) {
+                int fast = launch_visualizer_fast(g_launch_ctx, a, ssaa, frames, s, false);
+                if (fast == 0) fast = launch_visualizer_tiled(a, ssaa, frames, s, false);
+                if (fast != 0) return fast < 0 ? fast : SFX_OK;
+            }
+            return fused_plain(fragment, a, ssaa, frames, s);
+        case FRAG_BARS: {
+            const int fast = force_generic ? 0 : launch_separable(SEPARABLE_BARS, g_launch_ctx, a, ssaa, frames, s);
+            if (fast != 0) return fast < 0 ? fast : SFX_OK;
+            return fused_plain(fragment, a, ssaa, frames, s);
+        }
+        case FRAG_WAVEFORM: {
+            const int fast = force_generic ? 0 : launch_separable(SEPARABLE_WAVEFORM, g_launch_ctx, a, ssaa, frames, s);
+            if (fast != 0) return fast < 0 ? fast : SFX_OK;
+            return fused_plain(fragment, a, ssaa, frames, s);
+        }
+        default: return fused_plain(fragment, a, ssaa, frames, s);
+    }
+}
 
 #ifdef SF_SECTION_TIMERS
-static int launch_fused_inner(int fragment, const RenderArgs& a, int ssaa, int frames, hipStream_t s, bool force_generic);
 // profiling builds: run the launch with section timers and print the share of wave time per section
-static int launch_fused(int fragment, const RenderArgs& a0, int ssaa, int frames, hipStream_t s, bool force_generic = false) {
+static int launch_fused_timed(int fragment, const RenderArgs& a0, int ssaa, int frames, hipStream_t s) {
     static unsigned long long* d_timers = nullptr;
     static std::vector<unsigned long long> host(SF_TIMER_ROWS*8);
     if (!d_timers) hipMalloc(&d_timers, host.size()*sizeof(unsigned long long));
     hipMemsetAsync(d_timers, 0, host.size()*sizeof(unsigned long long), s);
     RenderArgs a = a0;
     a.timers = d_timers;
-    const int rc = launch_fused_inner(fragment, a, ssaa, frames, s, force_generic);
+    const int rc = launch_fused(fragment, a, ssaa, frames, s);
     unsigned long long t[8] = {};
     hipMemcpyAsync(host.data(), d_timers, host.size()*sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
     hipStreamSynchronize(s);
@@ -774,125 +778,7 @@ static int launch_fused(int fragment, const RenderArgs& a0, int ssaa, int frames
     fprintf(stderr, "\n");
     return rc;
 }
-#define launch_fused_body launch_fused_inner
-#else
-#define launch_fused_body launch_fused
 #endif
-
-static int launch_fused_body(int fragment, const RenderArgs& a, int ssaa, int frames, hipStream_t s, bool force_generic
-#ifndef SF_SECTION_TIMERS
-                             = false
-#endif
-                             ) {
-    using namespace sfl;
-    if (ssaa != 1 && ssaa != 2 && ssaa != 4) return fail(SFX_E_UNSUPPORTED, "fused ssaa %d", ssaa);
-    switch (fragment) {
-        case FRAG_DEFAULT:
-            if (!force_generic) {
-                const int fast = launch_separable(SEPARABLE_DEFAULT, g_launch_ctx, a, ssaa, frames, s);
-                if (fast != 0) return fast < 0 ? fast : SFX_OK;
-            }
-            return fused_plain(fragment, a, ssaa, frames, s);
-        case FRAG_VISUALIZER:
-            if (!force_generic) {
-                const int fast = launch_visualizer_fast(g_launch_ctx, a, ssaa, frames, s, false);
-                if (fast != 0) return fast < 0 ? fast : SFX_OK;
-            }
-            if (!force_generic && visualizer_tile_applicable(a.tex[TEX_BACKGROUND])) {
-                // the block shades 128*ssaa x rows*ssaa samples (S == 1: 128 x 2 pixels); pick the fixed tile when its window fits
-                int tw = 0, th = 0, pitch_ss = 0, rows_ss = 0, block_px = 0, block_rows = 0;
-                tiled_fused_limits(pitch_ss, rows_ss, block_px, block_rows);
-                visualizer_window_bound(a, (ssaa == 1 ? 128 : block_px)*ssaa, (ssaa == 1 ? 2 : block_rows)*ssaa, tw, th);
-                if (ssaa == 1 && tw <= 128 && th <= 10) return fused_visualizer_tiled(TILED_F_128x10, a, ssaa, frames, s, 0);
-                if (ssaa != 1 && tw <= pitch_ss && th <= rows_ss) {
-                    // four samples per lane need more registers: 6 waves per SIMD without spills beat 8 with (8K 4xSSAA: 55 -> 63 frames/s)
-                    return fused_visualizer_tiled(ssaa == 4 ? TILED_F_SS_S4 : TILED_F_SS, a, ssaa, frames, s, 0);
-                }
-                if (ssaa == 2) {
-                    // 0.43 texel per sample (1080p output at 2x SSAA over a 1080-row background): 64 pixels x 2 rows per block see a
-                    // 63 x 10 window — a 64 x 11 tile (33 KB) keeps four 512-thread blocks on a CU, where the tile sized per launch
-                    // below holds two
-                    int tw2 = 0, th2 = 0;
-                    visualizer_window_bound(a, 64*2, 2*2, tw2, th2);
-                    if (tw2 <= 64 && th2 <= 11) return fused_visualizer_tiled(TILED_F_64x11, a, ssaa, frames, s, 0);
-                }
-                if (ssaa == 4) {
-                    // the same for 4x SSAA at 0.2-0.3 texel per sample (1080p / 720p outputs): 32 pixels x 4 rows per block, a 56 x 14 tile (37 KB)
-                    int tw4 = 0, th4 = 0;
-                    visualizer_window_bound(a, 32*4, 4*4, tw4, th4);
-                    if (tw4 <= 56 && th4 <= 14) return fused_visualizer_tiled(TILED_F_56x14, a, ssaa, frames, s, 0);
-                }
-                if (ssaa == 2 && !a.identity_camera && !a.axis_camera) {
-                    // a rolled or tilted camera: a block's window grows with the block's extent along BOTH axes, so squarer blocks
-                    // stage fewer cells per pixel (C3 rolled by 45 degrees: 64 x 2 pixels see 31 x 31 cells, 32 x 4 see 23 x 23)
-                    // (round 5: and quads that WALK two or four rows — one sample per lane left every per-block cost, the camera's ray, the
-                    // window and the staging, 56 % of a rolled launch, to be paid per sample)
-                    struct Shape { int px, rows, walk; } const shapes[] = {{128, 1, 1}, {64, 2, 1}, {32, 4, 1}, {32, 4, 4}};
-                    // (measured at C3, 17 / 45 degrees: 32 x 4 x 1: 684 / 662 frames/s, 32 x 4 x 4: 743 / 663; the two-row walks and the
-                    // 64-wide ones spill or leave blocks off their tile and lose: profiles/r05_rolled_camera.txt)
-                    int best = -1, best_tw = 0, best_th = 0;
-                    float best_cost = 0.0f;
-                    static const int only = [] { const char* e = getenv("SHADERFLOW_VIS_SHAPE"); return e ? atoi(e) : -1; }();   // A/B switch for measurements
-                    for (int k = 0; k < 4; k++) {
-                        int w = 0, h = 0;
-                        if (only >= 0 && k != only) continue;
-                        visualizer_window_bound(a, shapes[k].px*2, shapes[k].rows*shapes[k].walk*2, w, h);
-                        // an odd pitch: a cell is 12 dwords, and with the camera turned by a quarter the lanes of a wave read down a
-                        // COLUMN of cells — 16 cells per row put every one of them on the same banks (730 -> 448 frames/s at C3, 90 degrees).
-                        // (made odd BEFORE the LDS test: what is checked is what is launched)
-                        w |= 1;
-                        if ((size_t)w*h*48 > 72*1024) continue;                       // two 512-thread blocks per CU at least
-                        // cells staged per pixel + what a block pays once per LANE (ray set-up, window, barriers), in cells' worth
-                        const float cost = (float)w*(float)h/(float)(shapes[k].px*shapes[k].rows*shapes[k].walk) + VIS_ROLLED_LANE_COST/(float)shapes[k].walk;
-                        if (best < 0 || cost < best_cost) { best = k; best_cost = cost; best_tw = w; best_th = h; }
-                    }
-                    if (best >= 0) {
-                        RenderArgs d = a;
-                        d.tile_pitch = best_tw; d.tile_rows = best_th;
-                        const size_t lds = (size_t)best_tw*best_th*48;
-                        // (best == 1, 2: eight waves per SIMD, not the four of the other tiles sized per launch: 555 -> 696 frames/s at C3 rolled by 17 degrees)
-                        static const TiledFused kernels[] = {TILED_F_DYN_128, TILED_F_DYN_64x2, TILED_F_DYN_32x4, TILED_F_DYN_32x4_WALK4};
-                        return fused_visualizer_tiled(kernels[best], d, ssaa, frames, s, lds);
-                    }
-                }
-                if (ssaa != 1) {
-                    // denser backgrounds (1080p output at 2x SSAA over a 1080-row background: 0.43 texel per sample; backgrounds
-                    // larger than the output): the tile is sized per launch in dynamic LDS, and the block narrows from 128 to 64
-                    // or 32 pixels until its window leaves room for at least two blocks per CU
-                    const int rows = block_rows*ssaa;
-                    int best_px = 0, best_tw = 0, best_th = 0;
-                    for (int px : {128, 64, 32}) {
-                        visualizer_window_bound(a, px*ssaa, rows, tw, th);
-                        tw |= 1;                                                      // an odd pitch (see above), before the LDS test
-                        const size_t lds = (size_t)tw*th*48;
-                        if (lds <= VIS_LDS_LIMIT) { best_px = px; best_tw = tw; best_th = th; if (lds <= 64*1024) break; }
-                    }
-                    if (best_px) {
-                        RenderArgs d = a;
-                        d.tile_pitch = best_tw; d.tile_rows = best_th;
-                        const size_t lds = (size_t)best_tw*best_th*48;
-                        return fused_visualizer_tiled(best_px == 128 ? TILED_F_DYN_128 : (best_px == 64 ? TILED_F_DYN_64 : TILED_F_DYN_32), d, ssaa, frames, s, lds);
-                    }
-                } else if ((size_t)tw*th*48 <= VIS_LDS_LIMIT) {
-                    RenderArgs d = a;
-                    d.tile_pitch = tw; d.tile_rows = th;
-                    return fused_visualizer_tiled(TILED_F_DYN_1X, d, ssaa, frames, s, (size_t)tw*th*48);
-                }
-            }
-            return fused_plain(fragment, a, ssaa, frames, s);
-        case FRAG_BARS: {
-            const int fast = force_generic ? 0 : launch_separable(SEPARABLE_BARS, g_launch_ctx, a, ssaa, frames, s);
-            if (fast != 0) return fast < 0 ? fast : SFX_OK;
-            return fused_plain(fragment, a, ssaa, frames, s);
-        }
-        case FRAG_WAVEFORM: {
-            const int fast = force_generic ? 0 : launch_separable(SEPARABLE_WAVEFORM, g_launch_ctx, a, ssaa, frames, s);
-            if (fast != 0) return fast < 0 ? fast : SFX_OK;
-            return fused_plain(fragment, a, ssaa, frames, s);
-        }
-        default: return fused_plain(fragment, a, ssaa, frames, s);
-    }
-}
 
 // A loaded program runs the generic kernels of its own code object (PlainShader geometry, jit_runtime.hpp)
 static int launch_jit(hipFunction_t fn, const RenderArgs& a, dim3 grid, dim3 block, hipStream_t s) {
@@ -916,6 +802,9 @@ static int launch_render_p(const Program* p, const RenderArgs& a, int frames, hi
 }
 static int launch_fused_p(const Program* p, const RenderArgs& a, int ssaa, int frames, hipStream_t s) {
     g_launch_ctx = p->ctx;
+#ifdef SF_SECTION_TIMERS
+    if (p->fragment != FRAG_JIT) return launch_fused_timed(p->fragment, a, ssaa, frames, s);
+#endif
     if (p->fragment != FRAG_JIT) return launch_fused(p->fragment, a, ssaa, frames, s);
     using P = PlainShader<FRAG_DEFAULT>;
     if (ssaa == 1) { const int rows = 2*jit_rows_1x(p); return launch_jit(p->fn_fused[0], a, dim3(((a.w + 127)/128)*((a.h + rows - 1)/rows), 1, frames), dim3(256), s); }

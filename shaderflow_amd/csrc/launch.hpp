@@ -12,15 +12,12 @@ namespace sfl {
 int render_plain(int fragment, const sf::RenderArgs& a, int frames, hipStream_t s);
 int fused_plain(int fragment, const sf::RenderArgs& a, int ssaa, int frames, hipStream_t s);
 
-// launch_visualizer_tiled.hip — VisualizerShader<…> over an LDS tile (round 1's kernels: rolled / tilted cameras, windows no table kernel takes)
-enum TiledRender { TILED_R_64x15_WALK8, TILED_R_DYNAMIC_WALK8, TILED_R_128x10, TILED_R_DYNAMIC };
-enum TiledFused { TILED_F_128x10, TILED_F_SS_S4, TILED_F_SS, TILED_F_64x11, TILED_F_56x14, TILED_F_DYN_128, TILED_F_DYN_64x2, TILED_F_DYN_32x4, TILED_F_DYN_32x4_WALK4,
-                  TILED_F_DYN_64, TILED_F_DYN_32, TILED_F_DYN_1X };
-void tiled_fused_limits(int& pitch_ss, int& rows_ss, int& block_px, int& block_rows);      // the build's fixed 2x / 4x tile and block
-int render_visualizer_tiled(TiledRender shape, const sf::RenderArgs& a, int frames, hipStream_t s, size_t dynamic_lds);
-int fused_visualizer_tiled(TiledFused shape, const sf::RenderArgs& a, int ssaa, int frames, hipStream_t s, size_t dynamic_lds);
+// launch_visualizer_tiled.hip — VisualizerShader<…> over an LDS tile (round 1's kernels: rolled / tilted cameras, windows no table kernel
+// takes). The picker chooses between the unit's shapes itself; `to_screen`: the samples into the target (k_render), else fused at `ssaa`
+int launch_visualizer_tiled(const sf::RenderArgs& a, int ssaa, int frames, hipStream_t s, bool to_screen);
 
-// launch_visualizer_strip.hip — k_visualizer_axes + k_visualizer_strip<…> / k_visualizer_fast<…> (visualizer_fast.hpp)
+// launch_visualizer_strip.hip — k_visualizer_axes + k_visualizer_strip<…> / k_visualizer_fast<…> (visualizer_fast.hpp); the picker walks
+// the unit's list of instances, first fit wins. The visualizer's order: this picker, then the tiled one, then the generic kernels
 void visualizer_consts_frames(const sf::FrameDyn* dyn, int frame0, int nframes, sf::VisualizerConsts* out, hipStream_t s);
 void visualizer_bars(const float* columns, long count, float* bars, hipStream_t s);
 int launch_visualizer_fast(Context* ctx, const sf::RenderArgs& a, int ssaa, int frames, hipStream_t s, bool to_screen);

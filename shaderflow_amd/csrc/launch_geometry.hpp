@@ -1,5 +1,5 @@
-// launch_geometry.hpp — host-side bounds of the background window a block of samples needs (shared by capi.hip's choice between the
-// visualizer's kernel families and the strip unit's choice between its tiles)
+// launch_geometry.hpp — host-side bounds of the background window a block of samples needs (shared by the visualizer's two
+// pickers: launch_visualizer_tiled.hip's choice between its shapes and launch_visualizer_strip.hip's first-fit walk over its instances)
 #pragma once
 
 #include "host_state.hpp"

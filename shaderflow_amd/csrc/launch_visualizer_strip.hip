@@ -19,13 +19,58 @@ void visualizer_bars(const float* columns, long count, float* bars, hipStream_t 
     hipLaunchKernelGGL(k_visualizer_bars, dim3((unsigned)((count + 255)/256)), dim3(256), 0, s, columns, count, bars);
 }
 
-// One geometry of the fast path: the tables for it, then the kernel. STRIP_S == 0: k_visualizer_fast (a quad of lanes per pixel,
-// 2x SSAA); otherwise k_visualizer_strip<PITCH, ROWS, STRIP_S, WALK, WAVES, CG> (lanes walk strips of their column; 2x or 4x SSAA
-// fused with the resolve, or STRIP_S == 1: the samples to an RGBA8 iScreen).
-template <int PITCH, int ROWS, int STRIP_S, int WALK, int WAVES, int CG = (STRIP_S ? 8/STRIP_S : 4), bool HALF = (STRIP_S == 1)>
-static int launch_visualizer_tables_and_kernel(Context* ctx, const RenderArgs& a, int frames, hipStream_t s) {
-    constexpr int COLS = STRIP_S ? 64*CG : 256;                       // sample columns per block
-    constexpr int BLOCK_ROWS = STRIP_S ? (8/CG)*WALK : 2;             // sample rows per block
+// One instance of the fast path. STRIP_S == 0: k_visualizer_fast (a quad of lanes per pixel, 2x SSAA); otherwise
+// k_visualizer_strip<PITCH, ROWS, STRIP_S, WALK, WAVES, CG, HALF> (lanes walk strips of their column; 2x or 4x SSAA fused with the
+// resolve, or STRIP_S == 1: the samples to an RGBA8 iScreen). HALF: float16 cells in three planes (visualizer_fast.hpp).
+template <int PITCH_, int ROWS_, int STRIP_S_, int WALK_, int WAVES_, int CG_ = (STRIP_S_ ? 8/STRIP_S_ : 4), bool HALF_ = (STRIP_S_ == 1)>
+struct Strip {
+    static constexpr int PITCH = PITCH_, ROWS = ROWS_, STRIP_S = STRIP_S_, WALK = WALK_, WAVES = WAVES_, CG = CG_;
+    static constexpr bool HALF = HALF_;
+    static constexpr int SSAA = STRIP_S ? STRIP_S : 2;                // the supersampling factor it serves (1: to the screen)
+    static constexpr int COLS = STRIP_S ? 64*CG : 256;                // sample columns per block
+    static constexpr int BLOCK_ROWS = STRIP_S ? (8/CG)*WALK : 2;      // sample rows per block
+};
+template <class... INSTANCES> struct Strips {};
+
+// The instances by supersampling factor, in the order they are tried: the first whose tile holds a block's window takes the launch.
+// no SSAA: 0.87 texel per sample at 1080p over a 1080-row background — nothing to share along a strip, but the tables, the folded tap
+// pairs and the speculated post-processing still apply
+using Strips1x = Strips<
+    Strip<66, 22, 1, 2, 4, 1>,                  // strips of two rows over 66 x 22 (two blocks per CU)
+    Strip<66, 15, 1, 1, 6, 1>>;                 // 64 columns x 8 rows per block over a 66 x 15 tile (three blocks per CU)
+// float16 cells: where the lanes of a wave read DIFFERENT cells the kernel is bound by LDS bandwidth and half the bytes win — 1080p 2x
+// 7 200 -> 7 970, 1440p 2x 4 480 -> 4 920, 720p 2x 9 430 -> 13 270 frames/s (profiles/r03_variants.txt); at 4K 2x the lanes share
+// their cells and plain float32 multiply-adds are cheaper
+using Strips2x = Strips<
+    // nine rows: the longest strip that stays inside 64 VGPRs (ten spill), +2 % over eight. 6 waves is what the kernel HAS: 51.8 KB of LDS
+    // per block = three blocks = six waves per SIMD (78 registers); asking for 8 only made the compiler say so on every build
+    Strip<72, 12, 2, 9, 6, 4, false>,
+    // denser outputs (1080p or 1440p at 2x SSAA over a 1080-row background: up to 0.43 texel per sample): strips of six rows, the
+    // longest whose 120-cell-wide tile still leaves two blocks per CU
+    Strip<120, 13, 2, 6, 4, 4, true>,
+    // sparser still (720p at 2x SSAA: 0.65 texel per sample): 128 columns x 12 rows per block, strips of three, 92 x 16 tile
+    Strip<92, 16, 2, 3, 4, 2, true>,
+    Strip<72, 10, 0, 0, 8>>;                    // the quad kernel; SHADERFLOW_VIS_FAST=1 skips the three strips above
+using Strips4x = Strips<
+    // 8K at 4x over a 1080-row background (0.0625 texel per sample): a block's window is 17 cells wide — on a 20-cell pitch its staging loop
+    // has no idle half (round 6's tile sweep, profiles/r06_c4_tile_sweep.txt: 292.0 -> 295.9 frames/s, the same bytes); wider windows
+    // (smaller outputs, larger backgrounds) keep the 40-cell pitch
+    Strip<20, 13, 4, 10, 6, 2, false>,
+    Strip<40, 13, 4, 10, 6, 2, false>,
+    Strip<40, 14, 4, 6, 8, 2, false>,           // 1080p at 4x SSAA: the same tile width with strips of six rows
+    Strip<56, 16, 4, 6, 6, 2, false>>;          // 720p at 4x SSAA (0.32 texel per sample)
+// A/B builds (tools/variants.sh, tools/experiments/c4_tile_sweep.sh): -DVIS_STRIP_TRY_FIRST="20, 13, 4, 10, 6, 2, false" names one more
+// instance by its template arguments; it is tried in front of the list of its own factor. Unset, nothing is compiled for it.
+#ifdef VIS_STRIP_TRY_FIRST
+using StripsFirst = Strips<Strip<VIS_STRIP_TRY_FIRST>>;
+#else
+using StripsFirst = Strips<>;
+#endif
+
+// the tables for an instance, then its kernel
+template <class I> static int launch_visualizer_tables_and_kernel(Context* ctx, const RenderArgs& a, int frames, hipStream_t s) {
+    constexpr int PITCH = I::PITCH, ROWS = I::ROWS, STRIP_S = I::STRIP_S, WALK = I::WALK, WAVES = I::WAVES, CG = I::CG, COLS = I::COLS, BLOCK_ROWS = I::BLOCK_ROWS;
+    constexpr bool HALF = I::HALF;
     VisTables t;
     t.blocks_x = (a.wr + COLS - 1)/COLS; t.blocks_y = (a.hr + BLOCK_ROWS - 1)/BLOCK_ROWS;
     t.block_columns = COLS; t.block_rows = BLOCK_ROWS; t.tile_pitch = PITCH; t.tile_rows = ROWS;
@@ -100,20 +145,27 @@ static int launch_visualizer_tables_and_kernel(Context* ctx, const RenderArgs& a
     return 1;
 }
 
+// One step of the first-fit walk: the instance launches when the window of its block fits its tile. `plain`: the 2x strips stand aside.
+template <class I> static int try_strip(Context* ctx, const RenderArgs& a, int ssaa, int frames, hipStream_t s, bool plain) {
+    if (I::SSAA != ssaa || (plain && I::STRIP_S == 2)) return 0;
+    int tw = 0, th = 0;
+    visualizer_window_bound(a, I::COLS, I::BLOCK_ROWS, tw, th);
+    return tw <= I::PITCH && th <= I::ROWS ? launch_visualizer_tables_and_kernel<I>(ctx, a, frames, s) : 0;
+}
+template <class... I> static int first_fit(Strips<I...>, Context* ctx, const RenderArgs& a, int ssaa, int frames, hipStream_t s, bool plain) {
+    int rc = 0;
+    (void)(... || ((rc = try_strip<I>(ctx, a, ssaa, frames, s, plain)) != 0));
+    return rc;
+}
+
 // ---- the fast visualizer path (visualizer_fast.hpp) -----------------------------------------------------------------------
 // Identity camera, unorm8 bilinear background, 2x or 4x SSAA, the window of a block inside one of the compiled tiles, and a blur
 // whose axis lines fit their slots at the largest radius the launch can see. Returns 1 when it launched, 0 when the configuration
 // is not its own (the caller then takes VisualizerShader), < 0 on errors.
-#ifndef VIS_FAST
-#define VIS_FAST 1
-#endif
-#ifndef VIS_FAST_WALK
-#define VIS_FAST_WALK 8
-#endif
 int launch_visualizer_fast(Context* ctx, const RenderArgs& a0, int ssaa, int frames, hipStream_t s, bool to_screen) {
     // fused: 2x or 4x SSAA into the RGB8 frame; to_screen: the samples themselves into an RGBA8 iScreen (the two-pass configuration)
     if (to_screen ? (ssaa != 1 || a0.out_dtype != DT_U8 || a0.out_components != 4) : (ssaa != 2 && ssaa != 4)) return 0;
-    if (!VIS_FAST || !ctx || !(a0.identity_camera || a0.axis_camera) || !visualizer_tile_applicable(a0.tex[TEX_BACKGROUND])) return 0;
+    if (!ctx || !(a0.identity_camera || a0.axis_camera) || !visualizer_tile_applicable(a0.tex[TEX_BACKGROUND])) return 0;
     const char* toggle = getenv("SHADERFLOW_VIS_FAST");              // A/B switch for measurements: 0 = round 1's kernels, 1 = k_visualizer_fast
     if (toggle && atoi(toggle) == 0) return 0;
     const Tex& bg = a0.tex[TEX_BACKGROUND];
@@ -137,116 +189,13 @@ int launch_visualizer_fast(Context* ctx, const RenderArgs& a0, int ssaa, int fra
     const float ax = intensity*a.bg_scale_x*(float)bg.width;
     const float reach_line = (fabsf(a.tap_x[0]) + 9.0f*fabsf(a.tap_x[1] - a.tap_x[0]))*ax;
     if (!(2.0f*reach_line + 1.0e-3f < (float)(VIS_LINE_CELLS - 1))) return 0;
-    auto fits = [&](int columns, int rows, int pitch, int tile_rows) {
-        int tw = 0, th = 0;
-        visualizer_window_bound(a, columns, rows, tw, th);
-        return tw <= pitch && th <= tile_rows;
-    };
-    // build knobs of the strip kernel (tools/variants.sh): rows a lane walks at 2x / 4x SSAA, rows of cells of the tiles, resident waves per SIMD
-#ifndef VIS_STRIP_WALK2
-#define VIS_STRIP_WALK2 (VIS_FAST_WALK == 8 ? 9 : VIS_FAST_WALK)     // nine rows: the longest strip that stays inside 64 VGPRs (ten spill), +2 % over eight
-#endif
-#ifndef VIS_STRIP_WALK4
-#define VIS_STRIP_WALK4 (VIS_FAST_WALK == 8 ? 10 : VIS_FAST_WALK)
-#endif
-#ifndef VIS_STRIP_ROWS2
-#define VIS_STRIP_ROWS2 (VIS_STRIP_WALK2 <= 4 ? 10 : (VIS_STRIP_WALK2 <= 6 ? 11 : 12))
-#endif
-#ifndef VIS_STRIP_ROWS4
-#define VIS_STRIP_ROWS4 13
-#endif
-#ifndef VIS_STRIP_PITCH2
-#define VIS_STRIP_PITCH2 72
-#endif
-#ifndef VIS_STRIP_WAVES2
-#define VIS_STRIP_WAVES2 6                                             // what the kernel HAS: 51.8 KB of LDS per block = three blocks = six waves per SIMD (78 registers); asking for 8 only made the compiler say so on every build
-#endif
-#ifndef VIS_STRIP_WAVES4
-#define VIS_STRIP_WAVES4 6
-#endif
-    constexpr int WALK2 = VIS_STRIP_WALK2, WALK4 = VIS_STRIP_WALK4;
     const bool plain = toggle && atoi(toggle) == 1;                   // force the quad-per-pixel kernel
-    if (ssaa == 1) {
-        // no SSAA: 0.87 texel per sample at 1080p over a 1080-row background — nothing to share along a strip, but the tables, the
-        // folded tap pairs and the speculated post-processing still apply. 64 columns x 8 rows per block over a 66 x 15 tile
-        // (three blocks per CU), or strips of two rows over 66 x 22 (two)
-#ifndef VIS_STRIP_WALK1
-#define VIS_STRIP_WALK1 2
-#endif
-#ifdef VIS_STRIP_ROWS1                                               // (A/B builds: longer strips without SSAA, tools/variants.sh)
-        if (fits(64, 8*VIS_STRIP_WALK1, 66, VIS_STRIP_ROWS1)) return launch_visualizer_tables_and_kernel<66, VIS_STRIP_ROWS1, 1, VIS_STRIP_WALK1, VIS_STRIP_WAVES1, 1>(ctx, a, frames, s);
-#endif
-        if (VIS_STRIP_WALK1 == 2 && fits(64, 16, 66, 22)) return launch_visualizer_tables_and_kernel<66, 22, 1, 2, 4, 1>(ctx, a, frames, s);
-        if (fits(64, 8, 66, 15)) return launch_visualizer_tables_and_kernel<66, 15, 1, 1, 6, 1>(ctx, a, frames, s);
-    } else if (ssaa == 2) {
-#ifndef VIS_STRIP_HALF2
-#define VIS_STRIP_HALF2 false
-#endif
-// float16 cells (visualizer_fast.hpp): where the lanes of a wave read DIFFERENT cells the kernel is bound by LDS bandwidth and
-// half the bytes win — 1080p 2x 7 200 -> 7 970, 1440p 2x 4 480 -> 4 920, 720p 2x 9 430 -> 13 270 frames/s (profiles/r03_variants.txt);
-// at 4K 2x the lanes share their cells and plain float32 multiply-adds are cheaper
-#ifndef VIS_DENSE_HALF
-#define VIS_DENSE_HALF true
-#endif
-#ifndef VIS_SPARSE_HALF
-#define VIS_SPARSE_HALF true
-#endif
-#ifndef VIS_STRIP_HALF4
-#define VIS_STRIP_HALF4 false
-#endif
-#ifndef VIS_MID4_HALF
-#define VIS_MID4_HALF false
-#endif
-#ifndef VIS_SPARSE4_HALF
-#define VIS_SPARSE4_HALF false
-#endif
-        if (VIS_FAST_WALK > 0 && !plain && fits(256, 2*WALK2, VIS_STRIP_PITCH2, VIS_STRIP_ROWS2)) return launch_visualizer_tables_and_kernel<VIS_STRIP_PITCH2, VIS_STRIP_ROWS2, 2, WALK2, VIS_STRIP_WAVES2, 4, VIS_STRIP_HALF2>(ctx, a, frames, s);
-        // denser outputs (1080p or 1440p at 2x SSAA over a 1080-row background: up to 0.43 texel per sample): strips of six rows
-        // over a 120 x 13 tile, two blocks per CU
-#ifndef VIS_DENSE_WALK
-#define VIS_DENSE_WALK 6                                              // the longest strip whose 120-cell-wide tile still leaves two blocks per CU
-#endif
-#ifndef VIS_DENSE_ROWS
-#define VIS_DENSE_ROWS 13
-#endif
-        if (VIS_FAST_WALK > 0 && !plain && fits(256, 2*VIS_DENSE_WALK, 120, VIS_DENSE_ROWS)) return launch_visualizer_tables_and_kernel<120, VIS_DENSE_ROWS, 2, VIS_DENSE_WALK, 4, 4, VIS_DENSE_HALF>(ctx, a, frames, s);
-        // sparser still (720p at 2x SSAA: 0.65 texel per sample): 128 columns x 12 rows per block, strips of three, 92 x 16 tile
-#ifndef VIS_SPARSE_WALK
-#define VIS_SPARSE_WALK 3
-#endif
-#ifndef VIS_SPARSE_ROWS
-#define VIS_SPARSE_ROWS 16
-#endif
-        if (VIS_FAST_WALK > 0 && !plain && fits(128, 4*VIS_SPARSE_WALK, 92, VIS_SPARSE_ROWS)) return launch_visualizer_tables_and_kernel<92, VIS_SPARSE_ROWS, 2, VIS_SPARSE_WALK, 4, 2, VIS_SPARSE_HALF>(ctx, a, frames, s);
-        if (fits(256, 2, 72, 10)) return launch_visualizer_tables_and_kernel<72, 10, 0, 0, 8>(ctx, a, frames, s);
-    } else if (VIS_FAST_WALK > 0) {
-#ifdef VIS4_SWEEP_WALK                                               // (A/B builds: BASELINE config 4's LDS-tile sweep — tools/experiments/c4_tile_sweep.sh)
-        if (fits(64*VIS4_SWEEP_CG, (8/VIS4_SWEEP_CG)*VIS4_SWEEP_WALK, VIS4_SWEEP_PITCH, VIS4_SWEEP_ROWS))
-            return launch_visualizer_tables_and_kernel<VIS4_SWEEP_PITCH, VIS4_SWEEP_ROWS, 4, VIS4_SWEEP_WALK, VIS4_SWEEP_WAVES, VIS4_SWEEP_CG, false>(ctx, a, frames, s);
-#endif
-        // 8K at 4x over a 1080-row background (0.0625 texel per sample): a block's window is 17 cells wide — on a 20-cell pitch its staging loop
-        // has no idle half (round 6's tile sweep, profiles/r06_c4_tile_sweep.txt: 292.0 -> 295.9 frames/s, the same bytes); wider windows
-        // (smaller outputs, larger backgrounds) keep the 40-cell pitch
-        if (fits(128, 4*WALK4, 20, VIS_STRIP_ROWS4)) return launch_visualizer_tables_and_kernel<20, VIS_STRIP_ROWS4, 4, WALK4, VIS_STRIP_WAVES4, 2, VIS_STRIP_HALF4>(ctx, a, frames, s);
-        if (fits(128, 4*WALK4, 40, VIS_STRIP_ROWS4)) return launch_visualizer_tables_and_kernel<40, VIS_STRIP_ROWS4, 4, WALK4, VIS_STRIP_WAVES4, 2, VIS_STRIP_HALF4>(ctx, a, frames, s);
-        // 1080p at 4x SSAA: the same tile width with strips of six rows
-#ifndef VIS_MID4_WALK
-#define VIS_MID4_WALK 6
-#endif
-#ifndef VIS_MID4_ROWS
-#define VIS_MID4_ROWS 14
-#endif
-#ifndef VIS_SPARSE4_WALK
-#define VIS_SPARSE4_WALK 6
-#endif
-#ifndef VIS_SPARSE4_ROWS
-#define VIS_SPARSE4_ROWS 16
-#endif
-        if (WALK4 != VIS_MID4_WALK && fits(128, 4*VIS_MID4_WALK, 40, VIS_MID4_ROWS)) return launch_visualizer_tables_and_kernel<40, VIS_MID4_ROWS, 4, VIS_MID4_WALK, 8, 2, VIS_MID4_HALF>(ctx, a, frames, s);
-        // 720p at 4x SSAA (0.32 texel per sample)
-        if (fits(128, 4*VIS_SPARSE4_WALK, 56, VIS_SPARSE4_ROWS)) return launch_visualizer_tables_and_kernel<56, VIS_SPARSE4_ROWS, 4, VIS_SPARSE4_WALK, 6, 2, VIS_SPARSE4_HALF>(ctx, a, frames, s);
+    if (const int first = first_fit(StripsFirst{}, ctx, a, ssaa, frames, s, plain)) return first;
+    switch (ssaa) {
+        case 1: return first_fit(Strips1x{}, ctx, a, ssaa, frames, s, plain);
+        case 2: return first_fit(Strips2x{}, ctx, a, ssaa, frames, s, plain);
+        default: return first_fit(Strips4x{}, ctx, a, ssaa, frames, s, plain);
     }
-    return 0;
 }
 
 }  // namespace sfl

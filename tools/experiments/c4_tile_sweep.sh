@@ -22,11 +22,12 @@ d = np.abs(a - b); print('vs the shipped geometry: max |d| =', d.max(), ' identi
   exit 0
 fi
 rm -f build/variants/lib_c4_*.so
-# name: pixels per block (wide x tall) — CG, WALK, tile pitch x rows (cells), waves per SIMD asked for
-tools/variants.sh "c4_16x8:-DVIS4_SWEEP_CG=1 -DVIS4_SWEEP_WALK=4 -DVIS4_SWEEP_PITCH=16 -DVIS4_SWEEP_ROWS=13 -DVIS4_SWEEP_WAVES=8" \
-                  "c4_16x16:-DVIS4_SWEEP_CG=1 -DVIS4_SWEEP_WALK=8 -DVIS4_SWEEP_PITCH=16 -DVIS4_SWEEP_ROWS=15 -DVIS4_SWEEP_WAVES=8" \
-                  "c4_32x8:-DVIS4_SWEEP_CG=2 -DVIS4_SWEEP_WALK=8 -DVIS4_SWEEP_PITCH=20 -DVIS4_SWEEP_ROWS=13 -DVIS4_SWEEP_WAVES=8" \
-                  "c4_32x12:-DVIS4_SWEEP_CG=2 -DVIS4_SWEEP_WALK=12 -DVIS4_SWEEP_PITCH=20 -DVIS4_SWEEP_ROWS=14 -DVIS4_SWEEP_WAVES=4" \
-                  "c4_32x10_p20:-DVIS4_SWEEP_CG=2 -DVIS4_SWEEP_WALK=10 -DVIS4_SWEEP_PITCH=20 -DVIS4_SWEEP_ROWS=13 -DVIS4_SWEEP_WAVES=6" \
-                  "c4_64x5:-DVIS4_SWEEP_CG=4 -DVIS4_SWEEP_WALK=10 -DVIS4_SWEEP_PITCH=28 -DVIS4_SWEEP_ROWS=12 -DVIS4_SWEEP_WAVES=6" \
-                  "c4_64x4:-DVIS4_SWEEP_CG=4 -DVIS4_SWEEP_WALK=8 -DVIS4_SWEEP_PITCH=28 -DVIS4_SWEEP_ROWS=12 -DVIS4_SWEEP_WAVES=8"
+# name: pixels per block (wide x tall) — the instance the strip unit tries first (launch_visualizer_strip.hip VIS_STRIP_TRY_FIRST):
+# tile pitch, tile rows (cells), 4x SSAA, WALK, waves per SIMD asked for, CG, float32 cells
+tools/variants.sh "c4_16x8:-DVIS_STRIP_TRY_FIRST=16,13,4,4,8,1,false" \
+                  "c4_16x16:-DVIS_STRIP_TRY_FIRST=16,15,4,8,8,1,false" \
+                  "c4_32x8:-DVIS_STRIP_TRY_FIRST=20,13,4,8,8,2,false" \
+                  "c4_32x12:-DVIS_STRIP_TRY_FIRST=20,14,4,12,4,2,false" \
+                  "c4_32x10_p20:-DVIS_STRIP_TRY_FIRST=20,13,4,10,6,2,false" \
+                  "c4_64x5:-DVIS_STRIP_TRY_FIRST=28,12,4,10,6,4,false" \
+                  "c4_64x4:-DVIS_STRIP_TRY_FIRST=28,12,4,8,8,4,false"
