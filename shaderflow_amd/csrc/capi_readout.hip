@@ -4,6 +4,7 @@
 // textures, programs and the render dispatch, capi_audio.hip the audio plans and the tape.)
 
 #include "host_state.hpp"
+#include "lane_pump.hpp"
 #include "ring_segments.hpp"
 
 #include <hsa/hsa.h>
@@ -77,7 +78,7 @@ static int context_copy_streams(Context* c) {
     return SFX_OK;
 }
 
-// Frames leave device memory through `EngineLanes`: two device-to-host copies in flight, each on an SDMA engine NAMED by this library.
+// Frames leave device memory through `EngineLanes`: up to four device-to-host copies in flight, each on an SDMA engine NAMED by this library.
 //
 // Not hipMemcpyAsync on a copy stream (rounds 1-3): the runtime picks an engine per stream — the lowest one free at that moment, then
 // sticky — and the sixteen engines of an MI355X are far from equal for device-to-host traffic (tools/ubench_sdma_engines.hip,
@@ -104,76 +105,56 @@ static hsa_status_t collect_agents(hsa_agent_t agent, void* data) {
     return HSA_STATUS_SUCCESS;
 }
 
-// the agents of a frame's two ends, from the pointers themselves; engines from HSA's recommendation. Once per context.
-static EngineCopy* engine_copy(Context* c, const void* host, const void* device) {
+// The agents of a copy's two ends, from the pointers themselves, and two SDMA engines for that ordered pair. Once per context and kind:
+//   read-out (`peer` false): `target` is the ring's host memory. SHADERFLOW_READOUT other than "engine" keeps HIP's copy streams.
+//   peer copy (sharded export, "device-sdma"): `target` lies in a window another process exported (sfx_peer_open) — its owner is another
+//     GPU of the node (or, in the one-GPU tests, this one). On the node's fully connected fabric every peer has its own xGMI link and
+//     the runtime pairs links with SDMA engines, so NAMING them keeps two copies of one rank on the engines of ITS link instead of on
+//     whichever engine is idle (hipMemcpyAsync's lottery). OPT-IN (SHADERFLOW_PEER=engine) since round 6: the named-engine
+//     route has only ever copied into its own process' window on ONE GPU. Until it has run between two real GPUs the default is HIP's
+//     copy streams, which every ROCm release exercises; bench.py's "sdma" legs ask for the engines explicitly after their preflight.
+static EngineCopy* engine_copy(Context* c, const void* target, const void* device, bool peer) {
     static std::mutex lock;
     std::lock_guard<std::mutex> guard(lock);
-    if (c->engines) return c->engines->usable ? c->engines : nullptr;
-    EngineCopy* e = c->engines = new EngineCopy();
-    const char* route = getenv("SHADERFLOW_READOUT");
-    if (route && strcmp(route, "engine")) return nullptr;
+    EngineCopy*& cached = peer ? c->peer_engines : c->engines;
+    if (cached) return cached->usable ? cached : nullptr;
+    EngineCopy* e = cached = new EngineCopy();
+    const char* route = getenv(peer ? "SHADERFLOW_PEER" : "SHADERFLOW_READOUT");
+    if (route ? strcmp(route, "engine") != 0 : peer) return nullptr;
     if (hsa_init() != HSA_STATUS_SUCCESS) return nullptr;             // reference-counted: HIP holds the runtime open already
-    hsa_amd_pointer_info_t info{}; info.size = sizeof(info);
-    if (hsa_amd_pointer_info(device, &info, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS || info.type == HSA_EXT_POINTER_TYPE_UNKNOWN) return nullptr;
-    e->gpu = info.agentOwner;
-    std::pair<std::vector<hsa_agent_t>, std::vector<hsa_agent_t>> agents;
-    if (hsa_iterate_agents(collect_agents, &agents) != HSA_STATUS_SUCCESS || agents.second.empty()) return nullptr;
-    bool is_gpu = false;
-    for (hsa_agent_t a : agents.first) is_gpu |= (a.handle == e->gpu.handle);
-    if (!is_gpu) return nullptr;
-    e->cpu = agents.second[0];
-    hsa_amd_pointer_info_t host_info{}; host_info.size = sizeof(host_info);
-    if (hsa_amd_pointer_info(host, &host_info, nullptr, nullptr, nullptr) == HSA_STATUS_SUCCESS)
-        for (hsa_agent_t a : agents.second) if (a.handle == host_info.agentOwner.handle) e->cpu = a;      // the socket the ring lives on
-    uint32_t free_mask = 0, preferred = 0;
-    // (informative only: a busy engine still takes the copy into its queue — the call must work, the mask need not be non-zero)
-    if (hsa_amd_memory_copy_engine_status(e->cpu, e->gpu, &free_mask) != HSA_STATUS_SUCCESS && hsa_amd_memory_get_preferred_copy_engine(e->cpu, e->gpu, &preferred) != HSA_STATUS_SUCCESS) return nullptr;
-    if (hsa_amd_memory_get_preferred_copy_engine(e->cpu, e->gpu, &preferred) != HSA_STATUS_SUCCESS) preferred = 0;
-    uint32_t pick = __builtin_popcount(preferred) >= 2 ? preferred : 0x3u;
+    hsa_amd_pointer_info_t here{}, there{};
+    here.size = sizeof(here); there.size = sizeof(there);
+    if (hsa_amd_pointer_info(device, &here, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS || here.type == HSA_EXT_POINTER_TYPE_UNKNOWN) return nullptr;
+    const bool target_seen = hsa_amd_pointer_info(target, &there, nullptr, nullptr, nullptr) == HSA_STATUS_SUCCESS;
+    std::pair<std::vector<hsa_agent_t>, std::vector<hsa_agent_t>> agents;   // GPUs, CPUs
+    if (hsa_iterate_agents(collect_agents, &agents) != HSA_STATUS_SUCCESS) return nullptr;
+    auto among = [](const std::vector<hsa_agent_t>& list, hsa_agent_t agent) { for (hsa_agent_t a : list) if (a.handle == agent.handle) return true; return false; };
+    e->gpu = here.agentOwner;
+    if (!among(agents.first, e->gpu)) return nullptr;
+    if (peer) {                                                      // the GPU that owns the window
+        if (!target_seen || there.type == HSA_EXT_POINTER_TYPE_UNKNOWN || !among(agents.first, there.agentOwner)) return nullptr;
+        e->cpu = there.agentOwner;
+    } else {                                                         // the socket the ring lives on, else the first
+        if (agents.second.empty()) return nullptr;
+        e->cpu = target_seen && among(agents.second, there.agentOwner) ? there.agentOwner : agents.second[0];
+    }
+    uint32_t preferred = 0, free_mask = 0, pick;
+    const bool recommended = hsa_amd_memory_get_preferred_copy_engine(e->cpu, e->gpu, &preferred) == HSA_STATUS_SUCCESS;
+    const bool status = hsa_amd_memory_copy_engine_status(e->cpu, e->gpu, &free_mask) == HSA_STATUS_SUCCESS;
+    if (!recommended) preferred = 0;
+    if (peer) {
+        pick = preferred ? preferred : status ? free_mask : 0;
+        if (!pick) return nullptr;                                    // no engine serves the pair (HSA's own choice would be a blit kernel)
+    } else {
+        // (the status is informative only: a busy engine still takes the copy into its queue — a call must work, the mask need not be non-zero)
+        if (!recommended && !status) return nullptr;
+        pick = __builtin_popcount(preferred) >= 2 ? preferred : 0x3u;
+    }
     e->engine[0] = pick & (~pick + 1u);                              // lowest set bit
     const uint32_t rest = pick & (pick - 1u);
     e->engine[1] = rest ? (rest & (~rest + 1u)) : e->engine[0];
     int a = -1, b = -1;
-    if (const char* named = getenv("SHADERFLOW_SDMA_ENGINES")) if (sscanf(named, "%d,%d", &a, &b) == 2 && a >= 0 && a < 16 && b >= 0 && b < 16) { e->engine[0] = 1u << a; e->engine[1] = 1u << b; }
-    e->usable = true;
-    return e;
-}
-
-// The same for a PEER copy (sharded export, "device-sdma"): the destination is a window another process exported (sfx_peer_open) — its
-// owner is another GPU of the node (or, in the one-GPU tests, this one). The engines are the ones HSA recommends for that ordered
-// pair of agents: on the node's fully connected fabric every peer has its own xGMI link and the runtime pairs links with SDMA
-// engines, so NAMING them keeps two copies of one rank on the engines of ITS link instead of on whichever engine is idle
-// (hipMemcpyAsync's lottery). SHADERFLOW_PEER_ENGINES=a,b overrides, SHADERFLOW_PEER=hip keeps HIP's copy streams.
-static EngineCopy* peer_engine_copy(Context* c, const void* remote, const void* local) {
-    static std::mutex lock;
-    std::lock_guard<std::mutex> guard(lock);
-    if (c->peer_engines) return c->peer_engines->usable ? c->peer_engines : nullptr;
-    EngineCopy* e = c->peer_engines = new EngineCopy();
-    // OPT-IN (SHADERFLOW_PEER=engine) since round 6: the named-engine route has only ever copied into its own process' window on ONE
-    // GPU. Until it has run between two real GPUs the default is HIP's copy streams (hipMemcpyAsync on the context's probed copy streams),
-    // which every ROCm release exercises; bench.py's "sdma" legs ask for the engines explicitly after their collective preflight.
-    const char* route = getenv("SHADERFLOW_PEER");
-    if (!route || strcmp(route, "engine")) return nullptr;
-    if (hsa_init() != HSA_STATUS_SUCCESS) return nullptr;
-    hsa_amd_pointer_info_t here{}, there{};
-    here.size = sizeof(here); there.size = sizeof(there);
-    if (hsa_amd_pointer_info(local, &here, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS || here.type == HSA_EXT_POINTER_TYPE_UNKNOWN) return nullptr;
-    if (hsa_amd_pointer_info(remote, &there, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS || there.type == HSA_EXT_POINTER_TYPE_UNKNOWN) return nullptr;
-    e->gpu = here.agentOwner; e->cpu = there.agentOwner;            // (`cpu` = the destination's agent: the GPU that owns the window)
-    std::pair<std::vector<hsa_agent_t>, std::vector<hsa_agent_t>> agents;
-    if (hsa_iterate_agents(collect_agents, &agents) != HSA_STATUS_SUCCESS) return nullptr;
-    bool source_known = false, target_known = false;
-    for (hsa_agent_t a : agents.first) { source_known |= (a.handle == e->gpu.handle); target_known |= (a.handle == e->cpu.handle); }
-    if (!source_known || !target_known) return nullptr;
-    uint32_t preferred = 0, free_mask = 0;
-    if (hsa_amd_memory_get_preferred_copy_engine(e->cpu, e->gpu, &preferred) != HSA_STATUS_SUCCESS) preferred = 0;
-    if (!preferred && hsa_amd_memory_copy_engine_status(e->cpu, e->gpu, &free_mask) == HSA_STATUS_SUCCESS) preferred = free_mask;
-    if (!preferred) return nullptr;                                   // no engine serves the pair (HSA's own choice would be a blit kernel)
-    e->engine[0] = preferred & (~preferred + 1u);
-    const uint32_t rest = preferred & (preferred - 1u);
-    e->engine[1] = rest ? (rest & (~rest + 1u)) : e->engine[0];
-    int a = -1, b = -1;
-    if (const char* named = getenv("SHADERFLOW_PEER_ENGINES")) if (sscanf(named, "%d,%d", &a, &b) == 2 && a >= 0 && a < 16 && b >= 0 && b < 16) { e->engine[0] = 1u << a; e->engine[1] = 1u << b; }
+    if (const char* named = getenv(peer ? "SHADERFLOW_PEER_ENGINES" : "SHADERFLOW_SDMA_ENGINES")) if (sscanf(named, "%d,%d", &a, &b) == 2 && a >= 0 && a < 16 && b >= 0 && b < 16) { e->engine[0] = 1u << a; e->engine[1] = 1u << b; }
     e->usable = true;
     return e;
 }
@@ -233,7 +214,7 @@ struct EngineLanes {
     void resolve(Context* context, const void* host, const void* device, bool peer = false) {
         if (resolved) return;
         resolved = true; c = context;
-        e = peer ? peer_engine_copy(context, host, device) : engine_copy(context, host, device);
+        e = engine_copy(context, host, device, peer);
         kind = peer ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         if (e) for (auto& signal : done) if (hsa_signal_create(0, 0, nullptr, &signal) != HSA_STATUS_SUCCESS) { e = nullptr; break; }
         if (!e) (void)context_copy_streams(context);                  // the lanes are HIP copy streams then
@@ -374,40 +355,35 @@ struct PeerCopier {
 
 static void peer_copier(PeerCopier* p) {
     hipSetDevice(p->ctx->device);
-    int in_lane[EngineLanes::LANES] = {-1, -1, -1, -1}, next = 0;
-    auto finish = [&](int lane) {
-        if (in_lane[lane] < 0) return;
-        const bool ok = p->lanes.finish(lane);
-        { std::lock_guard<std::mutex> lock(p->mutex); if (!ok) p->error = 1; p->pending[in_lane[lane]]--; }
-        in_lane[lane] = -1;
-        p->idle.notify_all();
-    };
-    for (;;) {
-        PeerCopier::Job job;
-        {
+    using Job = PeerCopier::Job;
+    struct Hooks {
+        PeerCopier* p;
+        bool take(Job& job, bool sleep) {
             std::unique_lock<std::mutex> lock(p->mutex);
-            if (p->queue.empty()) {
-                lock.unlock();
-                for (int k = 0; k < EngineLanes::LANES; k++) finish((next + k) % EngineLanes::LANES);
-                lock.lock();
-                p->wake.wait(lock, [&] { return p->stop || !p->queue.empty(); });
-                if (p->queue.empty()) return;
-            }
+            if (sleep) p->wake.wait(lock, [&] { return p->stop || !p->queue.empty(); });
+            if (p->queue.empty()) return false;
             job = p->queue.front(); p->queue.pop_front();
+            return true;
         }
-        for (int lane = 0; lane < EngineLanes::LANES; lane++) if (in_lane[lane] >= 0 && p->lanes.landed(lane)) finish(lane);
-        const bool rendered = wait_frame_ready(p->ready[job.tag]);   // the source is complete on the render stream (false: its event reports an error — nothing is copied)
-        finish(next);
-        p->lanes.resolve(p->ctx, job.dst, job.src, true);
-        if (!rendered || !p->lanes.issue(next, job.dst, job.src, job.nbytes)) {
-            std::lock_guard<std::mutex> lock(p->mutex);
-            p->error = 1; p->pending[job.tag]--;
+        bool ready(const Job& job) {                                 // the source is complete on the render stream (false: its event reports an error — nothing is copied)
+            const bool rendered = wait_frame_ready(p->ready[job.tag]);
+            p->lanes.resolve(p->ctx, job.dst, job.src, true);
+            return rendered;
+        }
+        LaneIssue issue(int lane, const Job& job) { return p->lanes.issue(lane, job.dst, job.src, job.nbytes) ? LaneIssue::issued : LaneIssue::failed; }
+        void landed(const Job& job, bool ok) {
+            { std::lock_guard<std::mutex> lock(p->mutex); if (!ok) p->error = 1; p->pending[job.tag]--; }
             p->idle.notify_all();
-            continue;
         }
-        in_lane[next] = job.tag;
-        next = (next + 1) % EngineLanes::LANES;
-    }
+        bool failed(const Job& job) { landed(job, false); return true; }
+    } hooks{p};
+    lane_pump<Job>(p->lanes, EngineLanes::LANES, true, hooks);       // (early reports: a tag's count may fall in any order)
+}
+
+// a ring or copier that is going away leaves the list sfx_device_free asks
+static void readouts_forget(Context* c, void* object) {
+    auto& list = c->readouts;
+    list.erase(std::remove_if(list.begin(), list.end(), [&](const std::pair<void*, void (*)(void*)>& e) { return e.first == object; }), list.end());
 }
 
 static void peer_stop(Context* c) {
@@ -418,7 +394,7 @@ static void peer_stop(Context* c) {
     if (p->worker.joinable()) p->worker.join();
     p->lanes.release();
     for (auto& e : p->ready) if (e) hipEventDestroy(e);
-    { auto& list = c->readouts; list.erase(std::remove_if(list.begin(), list.end(), [&](const std::pair<void*, void (*)(void*)>& e) { return e.first == p; }), list.end()); }
+    readouts_forget(c, p);
     delete p;
     c->peer = nullptr;
 }
@@ -505,7 +481,7 @@ struct Ring : Object {
     std::vector<void*> staging;                                     // device copies of texture reads (sfx_ring_read_async), allocated on first use
     std::vector<hipEvent_t> ready;                                  // per slot: recorded on the render stream when the slot's frame is complete
     hipEvent_t fences[2];
-    // copier: waits for a frame on the host, copies it on an engine lane (two in flight), marks the slot copied
+    // copier: waits for a frame on the host, copies it on an engine lane (up to four in flight), marks the slot copied
     struct CopyJob { int slot; const void* source; hipEvent_t ready; long frame; };
     std::thread copier;
     std::deque<CopyJob> copy_queue;
@@ -545,69 +521,54 @@ constexpr uint32_t RING_GAP_MAX = 64;               // sfx_ring_segments: the mo
 
 static void ring_copier(Ring* r) {
     hipSetDevice(r->ctx->device);
-    int in_lane[EngineLanes::LANES] = {-1, -1, -1, -1}, next = 0;
-    auto finish = [&](int lane) {
-        if (in_lane[lane] < 0) return;
-        const bool ok = r->lanes.finish(lane);
-        { std::lock_guard<std::mutex> lock(r->mutex); if (!ok) r->copy_error = 1; r->copying[in_lane[lane]] = 0; }
-        in_lane[lane] = -1;
-        r->idle.notify_all();
-    };
-    // frames that have landed are handed to the writer at once, not when their lane comes round again (a continuously fed queue
-    // never runs empty, and the copier is about to block on the NEXT frame's render)
-    auto release_landed = [&] { for (int lane = 0; lane < r->lane_count; lane++) if (in_lane[lane] >= 0 && r->lanes.landed(lane)) finish(lane); };
-    for (;;) {
-        Ring::CopyJob job;
-        {
+    using Job = Ring::CopyJob;
+    struct Hooks {
+        Ring* r;
+        bool take(Job& job, bool sleep) {
             std::unique_lock<std::mutex> lock(r->mutex);
-            if (r->copy_queue.empty()) {                             // nothing to issue: let what is in flight land (in issue order), then sleep
-                lock.unlock();
-                for (int k = 0; k < r->lane_count; k++) finish((next + k) % r->lane_count);
-                lock.lock();
-                r->copy_wake.wait(lock, [&] { return r->stop || !r->copy_queue.empty(); });
-                if (r->copy_queue.empty()) return;
-            }
+            if (sleep) r->copy_wake.wait(lock, [&] { return r->stop || !r->copy_queue.empty(); });
+            if (r->copy_queue.empty()) return false;
             job = r->copy_queue.front(); r->copy_queue.pop_front();
+            return true;
         }
-        static const bool trace = getenv("SHADERFLOW_RING_TRACE") != nullptr;
-        const auto t0 = std::chrono::steady_clock::now();
-        release_landed();
-        const bool rendered = wait_frame_ready(job.ready);           // the frame is complete on the render stream (false: its event reports an error — the slot is failed, not filled)
-        const auto t1 = std::chrono::steady_clock::now();
-        release_landed();
-        finish(next);                                                // the lane's previous copy
-        const auto t2 = std::chrono::steady_clock::now();
-        if (trace) fprintf(stderr, "ring copier: slot %d event wait %.0f us, lane finish %.0f us\n", job.slot, std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count());
-        r->lanes.resolve(r->ctx, r->host[job.slot], job.source);
-        char* landing = (char*)r->host[job.slot];
-        const char* source = (const char*)job.source;
-        size_t nbytes = r->frame_bytes;
-        if (r->sized && rendered) {
-            // the header on this lane, to the end; then the payload of exactly the length it names, behind it
-            uint32_t header[3] = {0, 0, 0};
-            const bool read = r->lanes.issue(next, landing, source, SINK_HEADER) && r->lanes.finish(next);
-            if (read) memcpy(header, landing, sizeof header);
-            const bool fits = read && header[0] == SINK_MAGIC && header[2] == 0 && header[1] > 0 && header[1] <= r->frame_bytes - SINK_HEADER;
-            if (!fits) {
-                std::lock_guard<std::mutex> lock(r->mutex);
-                if (!read) r->copy_error = 1; else if (r->unfit_frame < 0) r->unfit_frame = job.frame;
-                r->payload[job.slot] = 0; r->copying[job.slot] = 0;
-                r->idle.notify_all();
-                continue;
+        bool ready(const Job& job) {                                 // the frame is complete on the render stream (false: its event reports an error — the slot is failed, not filled)
+            static const bool trace = getenv("SHADERFLOW_RING_TRACE") != nullptr;
+            const auto t0 = std::chrono::steady_clock::now();
+            const bool rendered = wait_frame_ready(job.ready);
+            if (trace) fprintf(stderr, "ring copier: slot %d event wait %.0f us\n", job.slot, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+            r->lanes.resolve(r->ctx, r->host[job.slot], job.source);
+            return rendered;
+        }
+        LaneIssue issue(int lane, const Job& job) {
+            char* landing = (char*)r->host[job.slot];
+            const char* source = (const char*)job.source;
+            size_t nbytes = r->frame_bytes;
+            if (r->sized) {
+                // the header on this lane, to the end; then the payload of exactly the length it names, behind it
+                uint32_t header[3] = {0, 0, 0};
+                if (!r->lanes.issue(lane, landing, source, SINK_HEADER) || !r->lanes.finish(lane)) return LaneIssue::failed;
+                memcpy(header, landing, sizeof header);
+                if (header[0] != SINK_MAGIC || header[2] != 0 || header[1] == 0 || header[1] > r->frame_bytes - SINK_HEADER) {
+                    { std::lock_guard<std::mutex> lock(r->mutex); if (r->unfit_frame < 0) r->unfit_frame = job.frame; r->payload[job.slot] = 0; r->copying[job.slot] = 0; }
+                    r->idle.notify_all();
+                    return LaneIssue::skipped;                       // no error: the next wait reports the frame, the ring goes on
+                }
+                { std::lock_guard<std::mutex> lock(r->mutex); r->payload[job.slot] = header[1]; }
+                landing += SINK_HEADER; source += SINK_HEADER; nbytes = header[1];
             }
-            { std::lock_guard<std::mutex> lock(r->mutex); r->payload[job.slot] = header[1]; }
-            landing += SINK_HEADER; source += SINK_HEADER; nbytes = header[1];
+            return r->lanes.issue(lane, landing, source, nbytes) ? LaneIssue::issued : LaneIssue::failed;
         }
-        if (!rendered || !r->lanes.issue(next, landing, source, nbytes)) {
-            std::lock_guard<std::mutex> lock(r->mutex);
-            r->copy_error = 1; r->copying[job.slot] = 0;
-            if (r->sized) r->payload[job.slot] = 0;
+        void landed(const Job& job, bool ok) {
+            { std::lock_guard<std::mutex> lock(r->mutex); if (!ok) r->copy_error = 1; r->copying[job.slot] = 0; }
             r->idle.notify_all();
-            continue;
         }
-        in_lane[next] = job.slot;
-        next = (next + 1) % r->lane_count;
-    }
+        bool failed(const Job& job) {
+            { std::lock_guard<std::mutex> lock(r->mutex); r->copy_error = 1; r->copying[job.slot] = 0; if (r->sized) r->payload[job.slot] = 0; }
+            r->idle.notify_all();
+            return true;
+        }
+    } hooks{r};
+    lane_pump<Job>(r->lanes, r->lane_count, true, hooks);            // (early reports: a slot is released on its own, in any order)
 }
 
 static void ring_writer(Ring* r) {
@@ -909,7 +870,7 @@ extern "C" int sfx_ring_destroy(sfx_handle h) {
     if (r->writer.joinable()) r->writer.join();
     hipSetDevice(r->ctx->device);
     r->lanes.release();
-    { auto& list = r->ctx->readouts; list.erase(std::remove_if(list.begin(), list.end(), [&](const std::pair<void*, void (*)(void*)>& e) { return e.first == r; }), list.end()); }
+    readouts_forget(r->ctx, r);
     for (int k = 0; k < r->slots; k++) { hipHostFree(r->host[k]); hipEventDestroy(r->ready[k]); }
     for (void* p : r->staging) if (p) hipFree(p);
     for (auto& f : r->fences) hipEventDestroy(f);

@@ -58,7 +58,6 @@ struct Context : Object {
     struct EngineCopy* engines = nullptr;                           // agents and SDMA engines of the read-out (EngineLanes); null until first use
     struct EngineCopy* peer_engines = nullptr;                      // … of the peer copies (PeerCopier)
     struct PeerCopier* peer = nullptr;                              // the sharded export's peer copies: a thread that issues them on named engines
-    // peer copies of the sharded export's "device-sdma" mode: the copy streams, an event per lane (sfx_peer_*)
 };
 extern thread_local Context* g_launch_ctx;               // the context whose program is being launched (scratch owner)
 

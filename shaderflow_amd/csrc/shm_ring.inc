@@ -32,15 +32,15 @@ struct ShmRing : Object {
     bool owner, registered = false, unlinked = false;
     ShmHeader* header = nullptr;
     char* base = nullptr;
-    // producer: the publisher thread waits for a pushed frame on the host, copies it on an engine lane (two in flight, as the pinned
-    // ring does: EngineLanes, capi_readout.hip) and publishes it when it has landed
+    // producer: the publisher thread waits for a pushed frame on the host, copies it on an engine lane (two in flight: lane_pump on
+    // EngineLanes, capi_readout.hip) and publishes it when it has landed
     std::vector<hipEvent_t> ready;               // per slot: recorded on the render stream when the slot's frame is complete
     std::vector<const void*> sources;            // per slot: where the frame lives on the device
     EngineLanes lanes;
     void* bounce = nullptr;                      // pinned staging when the segment cannot be registered for DMA
     ptrdiff_t dma_delta = 0;                     // registered slots: device-visible address minus host address
     uint64_t pushed = 0;
-    int copy_error = 0;
+    std::atomic<int> copy_error{0};              // raised by the publisher thread, read by sfx_shm_push
     std::thread publisher;
     std::mutex mutex;
     std::condition_variable wake, idle;
@@ -95,57 +95,45 @@ template <class F> static bool shm_wait(ShmRing* r, F ready, double seconds = sh
 
 static void shm_publisher(ShmRing* r) {
     hipSetDevice(r->ctx->device);
-    int64_t in_lane[2] = {-1, -1};
-    int next = 0;
-    uint64_t issued = 0;
-    auto finish = [&](int lane) {
-        if (in_lane[lane] < 0) return;
-        const uint64_t frame = (uint64_t)in_lane[lane];
-        if (!r->lanes.finish(lane)) {                                // the copy failed: the slot does not hold the frame — never publish it
-            { std::lock_guard<std::mutex> lock(r->mutex); r->copy_error = 1; r->published = frame + 1; }   // (local bookkeeping only: nobody waits for it for ever)
-            r->header->failed.store(1, std::memory_order_release);
-            in_lane[lane] = -1;
-            r->idle.notify_all();
-            return;
-        }
-        if (r->bounce) memcpy(shm_slot(r, r->rank, frame), (char*)r->bounce + (frame % r->slots)*r->frame_stride, r->frame_bytes);
-        r->header->rank[r->rank].produced.store(frame + 1, std::memory_order_release);
-        {
-            std::lock_guard<std::mutex> lock(r->mutex);
-            r->published = frame + 1;
-        }
-        in_lane[lane] = -1;
-        r->idle.notify_all();
-    };
-    for (;;) {
-        {
+    struct Hooks {                                                   // (a job is a frame's number)
+        ShmRing* r;
+        uint64_t issued = 0;
+        int slot(uint64_t frame) const { return (int)(frame % r->slots); }
+        char* target(uint64_t frame) const { return r->bounce ? (char*)r->bounce + (size_t)slot(frame)*r->frame_stride : shm_slot(r, r->rank, frame) + r->dma_delta; }
+        bool take(uint64_t& frame, bool sleep) {
             std::unique_lock<std::mutex> lock(r->mutex);
-            if (issued >= r->queued) {                               // nothing to issue: let what is in flight land (in issue order), then sleep
-                lock.unlock();
-                finish(next); finish(next ^ 1);
-                lock.lock();
-                r->wake.wait(lock, [&] { return r->stop || issued < r->queued; });
-                if (issued >= r->queued) return;
-            }
+            if (sleep) r->wake.wait(lock, [&] { return r->stop || issued < r->queued; });
+            if (issued >= r->queued) return false;
+            frame = issued++;
+            return true;
         }
-        const uint64_t frame = issued;
-        const int slot = (int)(frame % r->slots);
-        const bool rendered = wait_frame_ready(r->ready[slot]);      // the frame is complete on the render stream (false: its event reports an error — the ring fails)
-        finish(next);
-        char* target = r->bounce ? (char*)r->bounce + (size_t)slot*r->frame_stride : shm_slot(r, r->rank, frame) + r->dma_delta;
-        r->lanes.resolve(r->ctx, target, r->sources[slot]);
-        if (!rendered || !r->lanes.issue(next, target, r->sources[slot], r->frame_bytes)) {
+        bool ready(uint64_t frame) {                                 // the frame is complete on the render stream (false: its event reports an error — the ring fails)
+            const bool rendered = wait_frame_ready(r->ready[slot(frame)]);
+            r->lanes.resolve(r->ctx, target(frame), r->sources[slot(frame)]);
+            return rendered;
+        }
+        LaneIssue issue(int lane, uint64_t frame) { return r->lanes.issue(lane, target(frame), r->sources[slot(frame)], r->frame_bytes) ? LaneIssue::issued : LaneIssue::failed; }
+        void landed(uint64_t frame, bool ok) {
+            if (ok) {
+                if (r->bounce) memcpy(shm_slot(r, r->rank, frame), (char*)r->bounce + (frame % r->slots)*r->frame_stride, r->frame_bytes);
+                r->header->rank[r->rank].produced.store(frame + 1, std::memory_order_release);
+            } else {                                                 // the copy failed: the slot does not hold the frame — never publish it
+                r->copy_error = 1;
+                r->header->failed.store(1, std::memory_order_release);
+            }
+            { std::lock_guard<std::mutex> lock(r->mutex); r->published = frame + 1; }   // (failed: local bookkeeping only — nobody waits for it for ever)
+            r->idle.notify_all();
+        }
+        bool failed(uint64_t) {                                      // the ring has failed for every rank: the thread ends
             r->copy_error = 1;
             r->header->failed.store(1, std::memory_order_release);  // everybody stops waiting for this rank's frames
-            std::lock_guard<std::mutex> lock(r->mutex);
-            r->published = r->queued;
+            { std::lock_guard<std::mutex> lock(r->mutex); r->published = r->queued; }
             r->idle.notify_all();
-            return;
+            return false;
         }
-        in_lane[next] = (int64_t)frame;
-        next ^= 1;
-        issued++;
-    }
+    } hooks{r};
+    // no early reports: `produced` is a counter that must rise in frame order, so frames are published strictly in issue order
+    lane_pump<uint64_t>(r->lanes, 2, false, hooks);
 }
 
 static void shm_writer(ShmRing* r) {
@@ -326,7 +314,7 @@ extern "C" int sfx_shm_destroy(sfx_handle h) {
     if (r->publisher.joinable()) r->publisher.join();
     if (r->writer.joinable()) { r->header->failed.store(1, std::memory_order_release); r->writer.join(); }
     r->lanes.release();
-    { auto& list = r->ctx->readouts; list.erase(std::remove_if(list.begin(), list.end(), [&](const std::pair<void*, void (*)(void*)>& e) { return e.first == r; }), list.end()); }
+    readouts_forget(r->ctx, r);
     if (r->registered) hipHostUnregister(shm_slot(r, r->rank, 0));
     if (r->bounce) hipHostFree(r->bounce);
     for (auto& e : r->ready) hipEventDestroy(e);

@@ -149,10 +149,12 @@ def sink_frames(payloads, capacity, bad=()):
     return frames
 
 
-@pytest.mark.parametrize("framing", [0, 1])
-def test_sized_ring(framing, tmp_path):
-    """Seven sink frames of different payload lengths (one of length 1, one odd) through a three-slot sized ring into a file: exact, in
-    order, framed and padded as asked; the sizes agree; a frame whose status says overflow fails the wait with its number, once"""
+@pytest.mark.parametrize("framing, slots", [pytest.param(0, 3, id="0"), pytest.param(1, 3, id="1"), pytest.param(0, 2, id="0-2slots"), pytest.param(1, 2, id="1-2slots"),
+                                            pytest.param(0, 5, id="0-5slots"), pytest.param(1, 5, id="1-5slots")])
+def test_sized_ring(framing, slots, tmp_path):
+    """Seven sink frames of different payload lengths (one of length 1, one odd) through a sized ring of three slots (two lanes), of two
+    (one lane) and of five (four lanes: a header read on every one) into a file: exact, in order, framed and padded as asked; the sizes
+    agree; a frame whose status says overflow fails the wait with its number, once"""
     import ctypes as C
 
     import torch
@@ -161,7 +163,7 @@ def test_sized_ring(framing, tmp_path):
     rng = np.random.default_rng(9)
     payloads = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (1, 7, 100, 768, 33, 2, 500)]
     ring = N.Handle()
-    N.check(N.lib().sfx_ring_create_sized(context.handle, capacity, 3, framing, C.byref(ring)))
+    N.check(N.lib().sfx_ring_create_sized(context.handle, capacity, slots, framing, C.byref(ring)))
     try:
         device = torch.from_numpy(sink_frames(payloads, capacity)).cuda()
         torch.cuda.synchronize()
@@ -174,6 +176,8 @@ def test_sized_ring(framing, tmp_path):
         sizes = (C.c_uint32*16)()
         N.check(N.lib().sfx_ring_sizes(ring, sizes, 16, C.byref(count)))
         assert list(sizes[:count.value]) == [len(p) for p in payloads]
+        if slots < 3:
+            return      # (three frames in one call would take a slot twice, and that slot's wait may meet the unfit frame inside the call)
         # frames 7…9 of the ring, the middle one marked as not fitting
         device = torch.from_numpy(sink_frames(payloads[:3], capacity, bad=(1,))).cuda()
         torch.cuda.synchronize()
