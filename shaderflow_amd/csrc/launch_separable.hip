@@ -14,10 +14,13 @@ namespace sfl {
 #ifndef LAYERED_FAST
 #define LAYERED_FAST 1
 #endif
+static bool layered_fast_off() {                                     // A/B switch for measurements, read once
+    static const bool off = [] { const char* e = getenv("SHADERFLOW_LAYERED_FAST"); return e && atoi(e) == 0; }();
+    return off;
+}
 int launch_multipass_layer1(Context* ctx, const RenderArgs& a, int frames, hipStream_t s) {
     const Tex& first = a.tex[TEX_HISTORY];
-    static const bool off = [] { const char* e = getenv("SHADERFLOW_LAYERED_FAST"); return e && atoi(e) == 0; }();     // A/B switch for measurements
-    if (!LAYERED_FAST || off || !ctx || a.u.iLayer != 1 || !first.data || first.dtype != DT_U8 || first.components != 4 || first.filter != FILTER_LINEAR) return 0;
+    if (!LAYERED_FAST || layered_fast_off() || !ctx || a.u.iLayer != 1 || !first.data || first.dtype != DT_U8 || first.components != 4 || first.filter != FILTER_LINEAR) return 0;
     if (!ctx->multipass_taps) {
         MultipassTaps table;
         multipass_tap_table(table, 5.0f, 8, 8);                     // multipass.frag:41 blur(iScreen0x0, astuv, 5, 8, 8)
@@ -38,9 +41,8 @@ int launch_multipass_layer1(Context* ctx, const RenderArgs& a, int frames, hipSt
     return 1;
 }
 int launch_motionblur_layer1(Context*, const RenderArgs& a, int frames, hipStream_t s) {
-    static const bool off = [] { const char* e = getenv("SHADERFLOW_LAYERED_FAST"); return e && atoi(e) == 0; }();
     const int temporal = (int)a.u.user[USER_SCREEN_TEMPORAL];
-    if (!LAYERED_FAST || off || a.u.iLayer != 1 || temporal < 1 || temporal > TEX_HISTORY_DEPTH) return 0;
+    if (!LAYERED_FAST || layered_fast_off() || a.u.iLayer != 1 || temporal < 1 || temporal > TEX_HISTORY_DEPTH) return 0;
     const Tex& first = a.tex[TEX_HISTORY];
     MotionblurArgs m{};
     m.temporal = temporal;
@@ -57,7 +59,36 @@ int launch_motionblur_layer1(Context*, const RenderArgs& a, int frames, hipStrea
     return 1;
 }
 
-// ---- bars.frag / waveform.frag with per-frame column and row tables (separable_fast.hpp) ---------------------------------------
+// ---- bars.frag / waveform.frag / default.glsl with per-frame column and row tables (separable_fast.hpp) -------------------------
+// An instance of k_separable_fused, written once beside its launch: a block walks CHUNKS times ROWS rows of 256 pixels, and the grid follows
+template <int KIND, int ROWS, int CHUNKS = 1, bool TWO_PASS = false> struct Fused {
+    static constexpr int rows = ROWS, chunks = CHUNKS;
+    static void launch(const RenderArgs& a, const SepTables& t, int frames, hipStream_t s) {
+        hipLaunchKernelGGL((k_separable_fused<KIND, ROWS, CHUNKS, TWO_PASS>), dim3((a.w + SEP_PIXELS - 1)/SEP_PIXELS, (a.h + ROWS*CHUNKS - 1)/(ROWS*CHUNKS), frames), dim3(SEP_PIXELS), 0, s, a, t);
+    }
+};
+// the first of INSTANCES that walks `rows` rows `chunks` times
+template <class... INSTANCES> static void launch_fused(int rows, int chunks, const RenderArgs& a, const SepTables& t, int frames, hipStream_t s) {
+    (void)((INSTANCES::rows == rows && INSTANCES::chunks == chunks ? (INSTANCES::launch(a, t, frames, s), true) : false) || ...);
+}
+// Which instance a launch gets. Blocks of a launch whose blocks walk `rows` rows of a frame `blocks_x` blocks wide:
+constexpr long fused_blocks(int blocks_x, int h, int frames, int rows) { return (long)blocks_x*((h + rows - 1)/rows)*frames; }
+// enough of them (a single 1080p frame is 272 blocks of 32 rows: it takes 8) for the long walk of its kind, 16 rows for default.glsl, 32 for bars / waveform
+constexpr long FUSED_ENOUGH_BLOCKS = 2048, FUSED_BLOCKS_TO_SPARE = 8192;
+// default.glsl with blocks to spare, where a block is asked to make several walks (SEP_CHUNKS_DEFAULT > 1; with 1 this rung IS the next one)
+constexpr int fused_chunks(int kind, int blocks_x, int h, int frames) {
+    return (kind == SEP_DEFAULT && SEP_CHUNKS_DEFAULT > 1 && fused_blocks(blocks_x, h, frames, SEP_ROWS_DEFAULT*SEP_CHUNKS_DEFAULT) >= FUSED_BLOCKS_TO_SPARE) ? SEP_CHUNKS_DEFAULT : 1;
+}
+constexpr int fused_rows(int kind, int blocks_x, int h, int frames) {
+    const int long_walk = (kind == SEP_DEFAULT) ? SEP_ROWS_DEFAULT : SEP_ROWS_LARGE;
+    return (fused_chunks(kind, blocks_x, h, frames) > 1 || fused_blocks(blocks_x, h, frames, long_walk) >= FUSED_ENOUGH_BLOCKS) ? long_walk : SEP_ROWS_SMALL;
+}
+// (worked out by hand from the ladder this function replaced; SEP_ROWS_DEFAULT_N = 16)
+static_assert(SEP_ROWS_DEFAULT != 16 || (fused_rows(SEP_DEFAULT, 15, 2160, 60) == 16 && fused_rows(SEP_DEFAULT, 15, 2160, 1) == 8), "4K: 60 frames per launch walk 16 rows, one frame (2 025 blocks) walks 8");
+static_assert(SEP_ROWS_DEFAULT != 16 || (fused_rows(SEP_DEFAULT, 3, 10933, 1) == 16 && fused_rows(SEP_DEFAULT, 3, 10912, 1) == 8), "2 052 blocks of 16 rows against 2 046");
+static_assert(fused_rows(SEP_BARS, 3, 21829, 1) == 32 && fused_rows(SEP_BARS, 3, 21824, 1) == 8 && fused_rows(SEP_BARS, 30, 4320, 1) == 32, "2 049 blocks of 32 rows against 2 046; 8K");
+static_assert(fused_rows(SEP_WAVEFORM, 15, 2160, 1) == 8, "a 4K frame is 1 020 blocks of 32 rows");
+
 // 1 launched, 0 not this path's configuration (the caller takes PlainShader), < 0 error.
 template <int KIND> static int launch_separable_t(Context* ctx, const RenderArgs& a, int ssaa, int frames, hipStream_t s) {
     if (!ctx || ssaa != 2) return 0;
@@ -99,26 +130,24 @@ template <int KIND> static int launch_separable_t(Context* ctx, const RenderArgs
         }
     }
     g_last_kernel = std::string("k_separable_fused<") + (KIND == SEP_BARS ? "bars" : (KIND == SEP_WAVEFORM ? "waveform" : "default")) + ">";
-    const int blocks_x = (a.w + SEP_PIXELS - 1)/SEP_PIXELS;
     // default.glsl's singular line (separable_fast.hpp k_default_singular), behind whichever kernels rendered the frames
     struct SingularLine { const RenderArgs& a; int frames; hipStream_t s; bool armed;
                           ~SingularLine() { if (armed) hipLaunchKernelGGL(k_default_singular, dim3((a.wr + a.hr + 255)/256, frames), dim3(256), 0, s, a); } } singular{a, frames, s, KIND == SEP_DEFAULT};
+    const int blocks_x = (a.w + SEP_PIXELS - 1)/SEP_PIXELS;
+    const int rows = fused_rows(KIND, blocks_x, a.h, frames), chunks = fused_chunks(KIND, blocks_x, a.h, frames);
     if constexpr (KIND == SEP_DEFAULT) {
-        // the smooth tier first, four pixels per lane; what it writes it marks, and the second pass skips
         if (quads) {
+            // the smooth tier first, four pixels per lane; what it writes it marks, and the second pass skips
             hipLaunchKernelGGL(k_default_quads, dim3(done_blocks, (a.h + 4*DQ_ROWS*DQ_WALKS - 1)/(4*DQ_ROWS*DQ_WALKS), frames), dim3(256), 0, s, a, t);
-            hipLaunchKernelGGL((k_separable_fused<KIND, SEP_ROWS_DEFAULT, 1, true>), dim3(blocks_x, (a.h + SEP_ROWS_DEFAULT - 1)/SEP_ROWS_DEFAULT, frames), dim3(SEP_PIXELS), 0, s, a, t);
-            return 1;
+            Fused<KIND, SEP_ROWS_DEFAULT, 1, true>::launch(a, t, frames, s);
+        } else if constexpr (SEP_CHUNKS_DEFAULT > 1) {
+            launch_fused<Fused<KIND, SEP_ROWS_DEFAULT, SEP_CHUNKS_DEFAULT>, Fused<KIND, SEP_ROWS_DEFAULT>, Fused<KIND, SEP_ROWS_SMALL>>(rows, chunks, a, t, frames, s);
+        } else {
+            launch_fused<Fused<KIND, SEP_ROWS_DEFAULT>, Fused<KIND, SEP_ROWS_SMALL>>(rows, chunks, a, t, frames, s);
         }
+    } else {
+        launch_fused<Fused<KIND, SEP_ROWS_LARGE>, Fused<KIND, SEP_ROWS_SMALL>>(rows, chunks, a, t, frames, s);
     }
-    if (KIND == SEP_DEFAULT && (long)blocks_x*((a.h + SEP_ROWS_DEFAULT*SEP_CHUNKS_DEFAULT - 1)/(SEP_ROWS_DEFAULT*SEP_CHUNKS_DEFAULT))*frames >= 8192)
-        hipLaunchKernelGGL((k_separable_fused<KIND, SEP_ROWS_DEFAULT, SEP_CHUNKS_DEFAULT>), dim3(blocks_x, (a.h + SEP_ROWS_DEFAULT*SEP_CHUNKS_DEFAULT - 1)/(SEP_ROWS_DEFAULT*SEP_CHUNKS_DEFAULT), frames), dim3(SEP_PIXELS), 0, s, a, t);
-    else if (KIND == SEP_DEFAULT && (long)blocks_x*((a.h + SEP_ROWS_DEFAULT - 1)/SEP_ROWS_DEFAULT)*frames >= 2048)
-        hipLaunchKernelGGL((k_separable_fused<KIND, SEP_ROWS_DEFAULT>), dim3(blocks_x, (a.h + SEP_ROWS_DEFAULT - 1)/SEP_ROWS_DEFAULT, frames), dim3(SEP_PIXELS), 0, s, a, t);
-    else if ((long)blocks_x*((a.h + SEP_ROWS_LARGE - 1)/SEP_ROWS_LARGE)*frames >= 2048)
-        hipLaunchKernelGGL((k_separable_fused<KIND, SEP_ROWS_LARGE>), dim3(blocks_x, (a.h + SEP_ROWS_LARGE - 1)/SEP_ROWS_LARGE, frames), dim3(SEP_PIXELS), 0, s, a, t);
-    else
-        hipLaunchKernelGGL((k_separable_fused<KIND, SEP_ROWS_SMALL>), dim3(blocks_x, (a.h + SEP_ROWS_SMALL - 1)/SEP_ROWS_SMALL, frames), dim3(SEP_PIXELS), 0, s, a, t);
     return 1;
 }
 

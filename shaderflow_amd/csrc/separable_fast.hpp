@@ -139,6 +139,31 @@ __global__ __launch_bounds__(256) void k_separable_axis(const RenderArgs a, cons
     (column ? t.columns + (long)frame*a.wr : t.rows + (long)frame*a.hr)[index] = e;
 }
 
+// ---- what the kernels below share about a frame's rows ------------------------------------------------------------------------------
+// Four RGB8 pixels of a row = twelve bytes = one `global_store_dwordx3`. Non-temporal (`... nt`): nobody on the device reads a frame
+// back, so its lines need not stay in the L2 — bars 308 -> 261 us per 60 frames of 4K (5.7 TB/s written = 0.71 of the HBM roof),
+// waveform 293 -> 289 (its time is the special rows around the wave, not the stores)
+typedef uint32_t Triple __attribute__((ext_vector_type(3), aligned(4)));
+__device__ __forceinline__ void store_four_pixels(uint8_t* at, uint32_t d0, uint32_t d1, uint32_t d2) { __builtin_nontemporal_store(Triple{d0, d1, d2}, (Triple*)at); }
+// four pixels, each R | G << 8 | B << 16 with a clear high byte, as their three dwords R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+struct FourPixels { uint32_t d0, d1, d2; };
+__device__ __forceinline__ FourPixels pack_four_pixels(const uint32_t p[4]) { return FourPixels{p[0] | (p[1] << 24), (p[1] >> 8) | (p[2] << 16), (p[2] >> 16) | (p[3] << 8)}; }
+// may the block of 256 pixels at x0 leave as such stores? a full block of a frame whose rows are whole dwords, at a dword (`out`: the frame's first byte)
+__device__ __forceinline__ bool packed_stores(const RenderArgs& a, int x0, const void* out) {
+    return x0 + 256 <= a.w && (a.w & 3) == 0 && ((uintptr_t)out & 3) == 0 && (a.out_frame_stride & 3) == 0;
+}
+// waveform.frag: every channel of a sample is 1 or 0.2, so a pixel's byte is a function of WHICH of its four samples are inside
+// the wave: sixteen blocks, resolved once per thread block by the chain every kernel uses (ends in a barrier: every thread calls it)
+__device__ __forceinline__ void build_inside_lut(uint8_t* lut, int tid, int subsample) {
+    if (tid < 16) {
+        uint32_t pattern[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) pattern[k] = unorm8(((tid >> k) & 1) ? 1.0f : 0.2f);
+        lut[tid] = (uint8_t)resolve_channel_any<2>(pattern, subsample, 0);
+    }
+    __syncthreads();
+}
+
 // default.glsl:19-26, the two-dimensional part of one point in two halves: the hue wheel by polar angle (as 0.3 + hsv2rgb, :22) and
 // the ring `width` = 2e-4/circle² by radius; `hue_shift` = 2*TAU*iTau - PI/4 (:22), per frame
 struct DefaultHue { float red, green, blue; };
@@ -230,6 +255,68 @@ __device__ __forceinline__ bool default_shares_hue(float width, float len, float
 #ifndef SEP_DEFAULT_FLOAT_MEAN
 #define SEP_DEFAULT_FLOAT_MEAN 1        // 0: every pixel of the shared tier resolved from its four quantised samples (round 3), for A/B
 #endif
+
+// ---- default.glsl's SMOOTH TIER (round 4), the one formula of k_separable_fused<default> and k_default_quads -----------------------
+// Where one evaluation of the polar terms may serve several rows, a pixel is resolved from MEANS in float: mean_k vig_k*(base_k + w_k*hue)
+// over its four samples k = (column i, row j) with vig_k = min(c_i*r_j, 1) is, up to terms far below the quantisation step,
+//     min(mean_j r_j * mean_i c_i*base_i, mean_i base_i)  +  min(mean_i c_i * mean_j r_j, 1) * w(pixel centre) * hue
+// — the products factorise exactly, the clamp differs only where some of the four products exceed 1 and others do not (the middle of
+// the frame, where they differ by 1e-4), the covariance of vig and w inside a pixel is second order (< 0.005 LSB at the frame's edge).
+// Column means live in registers for the walk, row means in the row table (.w): ≈ 20 operations per pixel. Against the reference,
+// which quantises each sample: the mean of four roundings is within 1/2 of the mean, so the bytes are roundings of numbers within
+// 1/2 (+ 0.03) of each other — at most ONE apart, the bound of every fused kernel (no sample saturates here: |circle| > 0.1 keeps the
+// ring term under 0.03).
+// A pixel column: gluv.x at its centre, half the sample spacing, and its means: of the vignette's column factor (`cz`), of that factor
+// times the checkerboard under the EVEN sample rows (`g0`) and of that checkerboard alone (`b0`). (Few registers across a walk — the
+// fused kernel lives at 64: the odd rows' means are (0.20 + 0.22)*255 times the column mean minus the even rows', smooth_terms.)
+struct DefaultColumnMeans { float cx, half_reach, cz, g0, b0; };
+__device__ __forceinline__ DefaultColumnMeans default_column_means(const float4 c0, const float4 c1) {
+    // the checkerboard under a sample: (column parity ^ row parity) ? 0.22 : 0.20 (default.glsl:4-8)
+    const bool odd0 = (__float_as_int(c0.y) & 1) != 0, odd1 = (__float_as_int(c1.y) & 1) != 0;
+    const float even_rows0 = odd0 ? DEFAULT_ODD : DEFAULT_EVEN, even_rows1 = odd1 ? DEFAULT_ODD : DEFAULT_EVEN;
+    return DefaultColumnMeans{0.5f*(c0.x + c1.x), 0.5f*sf::abs(c1.x - c0.x), 0.5f*(c0.z + c1.z), 0.5f*fmaf(c0.z, even_rows0, c1.z*even_rows1), 0.5f*(even_rows0 + even_rows1)};
+}
+__device__ __forceinline__ bool default_column_outside(const float4 c0, const float4 c1) { return (__float_as_int(c0.w) | __float_as_int(c1.w)) != 0; }   // camera.glsl:83
+// May the samples within `reach` of the point where `ring` was evaluated share that ONE evaluation of the polar terms? For the rows
+// within `rows_reach` row steps of that point, in this pixel column: reach = default_rows_reach
+__device__ __forceinline__ float default_rows_reach(const DefaultColumnMeans& m, float rows_reach, float row_step) { return m.half_reach + rows_reach*row_step; }
+__device__ __forceinline__ bool default_may_share(const DefaultRing& ring, float reach) {
+    return default_shares_slope(ring, reach) && default_shares_hue(1.5f*ring.width, ring.len, reach);
+}
+// What a group of rows in one square of the checkerboard's rows (`odd_rows`: which) takes from such an evaluation: `ground_of_rows`,
+// `base_of_rows` = the means of the group's rows: the disc's, or the checkerboard's by the parity its sample rows share; the ring's
+// width by the slope along y at `group_y`, w(y) = offset + slope_y*y (`offset` = the width at gluv.y = 0), halved for a pixel's two sample rows
+struct DefaultSmoothTerms { float ground_of_rows, base_of_rows, half_slope, offset; };
+__device__ __forceinline__ DefaultSmoothTerms default_smooth_terms(const DefaultRing& ring, float slope_y, float group_y, bool odd_rows, const DefaultColumnMeans& m) {
+    const bool disc = ring.circle < 0.0f;
+    DefaultSmoothTerms out;
+    out.ground_of_rows = disc ? DEFAULT_DISC*m.cz : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD)*m.cz - m.g0 : m.g0);
+    out.base_of_rows = disc ? DEFAULT_DISC : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD) - m.b0 : m.b0);
+    out.half_slope = 0.5f*slope_y; out.offset = fmaf(-slope_y, group_y, ring.width*255.0f);
+    return out;
+}
+// The ring's width (times 255) at a pixel's centre, in the two forms the callers have — they round differently, so each keeps its own:
+// a row of a smooth group from its two sample rows' gluv.y through the group's terms, or (general_row) from the pixel's centre directly
+__device__ __forceinline__ float default_width_by_rows(const DefaultSmoothTerms& s, float y0, float y1) { return fmaf(s.half_slope, y0, fmaf(s.half_slope, y1, s.offset)); }
+__device__ __forceinline__ float default_width_at_centre(const DefaultRing& ring, float slope_y, float cy, float group_y) { return fmaf(slope_y, cy - group_y, ring.width*255.0f); }
+// The pixel of the row whose vignette mean is `row_w` (the row entry's .w): its three channels times 255. `one_square`: both sample
+// columns in one square of the checkerboard's columns, where min(r*c*B, B) = B*min(r*c, 1) saves the multiply
+struct DefaultChannels { float red, green, blue; };
+// (`width255`: one of the two forms above, as a function — evaluated after the vignette, where the callers had it: k_default_quads
+// lives at 128 registers exactly and spills when the order changes)
+template <class WIDTH>
+__device__ __forceinline__ DefaultChannels default_smooth_pixel(const DefaultColumnMeans& m, float row_w, WIDTH width255, const DefaultSmoothTerms& s, const DefaultHue& hue, bool one_square) {
+    const float vignette = clamp01(m.cz*row_w);
+    const float ring = width255()*vignette;
+    const float ground = one_square ? s.base_of_rows*vignette : __builtin_fminf(row_w*s.ground_of_rows, s.base_of_rows);
+    return DefaultChannels{fmaf(ring, hue.red, ground), fmaf(ring, hue.green, ground), fmaf(ring, hue.blue, ground)};
+}
+__device__ __forceinline__ uint32_t default_smooth_rgb(const DefaultChannels& colour) {
+    uint32_t rgb = __builtin_amdgcn_cvt_pk_u8_f32(colour.red, 0u, 0u);
+    rgb = __builtin_amdgcn_cvt_pk_u8_f32(colour.green, 1u, rgb);
+    return __builtin_amdgcn_cvt_pk_u8_f32(colour.blue, 2u, rgb);
+}
+
 // which samples of the 2 x 2 block at sample row j0 are inside the runs of its two columns (bit y*2 + x, the block's texel order)
 __device__ __forceinline__ bool row_in_run(int run, int j) { return (unsigned)(j - (run & 0xffff)) < ((unsigned)run >> 16); }
 __device__ __forceinline__ int wave_pattern(int run0, int run1, int j0) {
@@ -241,6 +328,313 @@ __device__ __forceinline__ int rows_of_pair(int below, int j0) { const int n = b
 __device__ __forceinline__ uint32_t blue_texel(float below, float ramp, float one_minus_y) {
     return __builtin_amdgcn_cvt_pk_u8_f32((below + ramp*one_minus_y)*255.0f, 2u, 0u);
 }
+__device__ __forceinline__ uint32_t waveform_pixel(const float4 c0, const float4 c1, int j0, const uint8_t* lut) {
+    return (uint32_t)lut[wave_pattern(__float_as_int(c0.x), __float_as_int(c1.x), j0)]
+         | ((uint32_t)lut[wave_pattern(__float_as_int(c0.y), __float_as_int(c1.y), j0)] << 8)
+         | ((uint32_t)lut[wave_pattern(__float_as_int(c0.z), __float_as_int(c1.z), j0)] << 16);
+}
+
+// ---- what a block of k_separable_fused knows when its rows begin (separable_walk), and the three row bodies ---------------------------
+// A row body owns its per-block prologue (its constructor), its state across a walk, and says how one walk of SEP_ROWS rows fills
+// `staged`: begin_walk (false: nothing of this walk is left to write — block-uniform, the walk is skipped), fill, and written_elsewhere
+// (rows of the walk some other kernel wrote: only default.glsl's second pass has any).
+struct SepBlock {
+    const RenderArgs& a; const SepTables& t;
+    const float4* rows;                                                // the frame's row entries
+    const float4 c0, c1;                                               // the two column entries of this thread's pixel
+    const int frame, tid;
+};
+
+// bars.frag / waveform.frag: a walk is its rows one by one
+template <int SEP_ROWS>
+struct BarsRows {
+    const SepBlock& b;
+    __device__ __forceinline__ BarsRows(const SepBlock& block) : b(block) {}
+    static constexpr bool one_walk_in_a_loop = false;
+    __device__ __forceinline__ bool begin_walk(bool, int) { return true; }
+    __device__ __forceinline__ bool written_elsewhere(int) const { return false; }
+    __device__ __forceinline__ void fill(uint32_t (*staged)[SEP_PIXELS], int block_row) {
+        const float4 c0 = b.c0, c1 = b.c1;
+#pragma unroll
+        for (int r = 0; r < SEP_ROWS; r++) {
+            const int py = block_row*SEP_ROWS + r, j0 = 2*py;
+            if (py >= b.a.h) break;
+            const float4 r0 = b.rows[2*py], r1 = b.rows[2*py + 1];        // block-uniform: scalar loads
+            // red and green are 0 or 1 per supersample: the resolve of such a block is exact in every step — the sum of the four
+            // texels/255 is their count, count/4 is exact, and the unorm8 write of it is RN(count*63.75) for either kernel size
+            // (the 1-tap kernel's weights are 0.25 each) — so the byte is a function of how many of the pixel's four samples lie
+            // below the column's height: min(max(T - first row, 0), 2) per column.
+            const int red = rows_of_pair(__float_as_int(c0.x), j0) + rows_of_pair(__float_as_int(c1.x), j0);
+            const int green = rows_of_pair(__float_as_int(c0.y), j0) + rows_of_pair(__float_as_int(c1.y), j0);
+            // blue adds the ramp 0.4*(sum)*(1 - astuv.y) (bars.frag:17): the generic chain on that channel alone, resolve_channel_any on
+            // the four texels. BY DESIGN not k_separable_runs' blue_mean (below), the integer mean of the four bytes: the two differ by
+            // 1 LSB on ties (tests/test_gpu_pixels.py same_as_generic), and this kernel is the one that equals the generic kernel's bytes.
+            const int t0 = __float_as_int(c0.z), t1 = __float_as_int(c1.z);
+            uint32_t block[4];                                             // texel order y*2 + x (render_kernels.hpp)
+            block[0] = blue_texel((j0 < t0) ? 1.0f : 0.0f, c0.w, r0.y); block[1] = blue_texel((j0 < t1) ? 1.0f : 0.0f, c1.w, r0.y);
+            block[2] = blue_texel((j0 + 1 < t0) ? 1.0f : 0.0f, c0.w, r1.y); block[3] = blue_texel((j0 + 1 < t1) ? 1.0f : 0.0f, c1.w, r1.y);
+            const uint32_t rgb = __builtin_amdgcn_cvt_pk_u8_f32((float)red*63.75f, 0u, resolve_channel_any<2>(block, b.a.subsample, 16) << 16);
+            staged[r][b.tid] = __builtin_amdgcn_cvt_pk_u8_f32((float)green*63.75f, 1u, rgb);
+        }
+    }
+};
+template <int SEP_ROWS>
+struct WaveformRows {
+    const SepBlock& b;
+    const uint8_t* inside_lut;
+    __device__ __forceinline__ WaveformRows(const SepBlock& block) : b(block) {
+        __shared__ uint8_t lut[16];
+        inside_lut = lut;
+        build_inside_lut(lut, b.tid, b.a.subsample);
+    }
+    static constexpr bool one_walk_in_a_loop = false;
+    __device__ __forceinline__ bool begin_walk(bool, int) { return true; }
+    __device__ __forceinline__ bool written_elsewhere(int) const { return false; }
+    __device__ __forceinline__ void fill(uint32_t (*staged)[SEP_PIXELS], int block_row) {
+#pragma unroll
+        for (int r = 0; r < SEP_ROWS; r++) {
+            const int py = block_row*SEP_ROWS + r;
+            if (py >= b.a.h) break;
+            staged[r][b.tid] = waveform_pixel(b.c0, b.c1, 2*py, inside_lut);
+        }
+    }
+};
+
+// default.glsl: the walk in groups of four rows, by the tiers of SEP_DEFAULT_TOLERANCE (above). (A row of the tiers is ~3 KB of code:
+// it exists once, in a loop.) TWO_PASS: the instance that runs after k_default_quads and reads that kernel's marks — a template
+// argument because even the untaken branches on a null map cost the one-pass kernel 3 %.
+template <int SEP_ROWS, bool TWO_PASS>
+struct DefaultRows {
+    static_assert(SEP_ROWS % 4 == 0, "the walk is made of groups of four rows");
+    static constexpr bool one_walk_in_a_loop = true;
+    const SepBlock& b;
+    float hue_shift;                                                   // default.glsl:22, per frame
+    bool odd_column0, odd_column1, outside;
+    bool wave_one_square;                                              // wave-uniform: both sample columns of every lane in one square of the checkerboard's columns
+    DefaultColumnMeans m;
+    // across a walk. The group's first row evaluates the polar terms at the point in the middle of the group's (or the walk's) samples:
+    int smooth_until = 0;                                              // wave-uniform: rows [r, smooth_until) of the walk are smooth for every lane of the wave
+    int shared_until = 0;                                              // rows below this one use this lane's group_ring / group_hue / group_slope (at group_y)
+    int wheel_until = 0;                                               // rows below this one move group_wheel by their own angle instead of taking an arctangent
+    float group_wheel = 0.0f, group_y = 0.0f;
+    DefaultRing group_ring = {}; DefaultHue group_hue = {}; DefaultSlope group_slope = {};
+    unsigned done_mask = 0u;                                           // TWO_PASS: the walk's groups of four rows that k_default_quads has written
+
+    __device__ __forceinline__ DefaultRows(const SepBlock& block) : b(block) {
+        const float tau = b.a.dyn ? b.a.dyn[b.a.frame0 + b.frame].iTau : b.a.u.iTau;
+        hue_shift = (2.0f*TAU*tau) - (PI/4.0f);                         // the generic chain's operations
+        odd_column0 = (__float_as_int(b.c0.y) & 1) != 0; odd_column1 = (__float_as_int(b.c1.y) & 1) != 0;
+        outside = default_column_outside(b.c0, b.c1);
+        wave_one_square = __builtin_amdgcn_ballot_w64(odd_column0 == odd_column1) == __builtin_amdgcn_ballot_w64(true);
+        m = default_column_means(b.c0, b.c1);
+    }
+    __device__ __forceinline__ bool begin_walk(bool again, int block_row) {
+        if (again) { smooth_until = 0; shared_until = 0; wheel_until = 0; }
+        // default.glsl in two passes: the groups of four rows k_default_quads has already written (block-uniform: a block's 256 pixels are
+        // one wave of that kernel)
+        done_mask = 0u;
+        if constexpr (TWO_PASS) {
+            if (b.t.done) {
+                const uint8_t* done = b.t.done + ((long)b.frame*b.t.done_groups + (block_row*SEP_ROWS)/4)*b.t.done_blocks + blockIdx.x;
+#pragma unroll
+                for (int g = 0; g < SEP_ROWS/4; g++)
+                    if ((int)block_row*SEP_ROWS + 4*g < b.a.h && done[(long)g*b.t.done_blocks]) done_mask |= 1u << g;
+                done_mask = __builtin_amdgcn_readfirstlane(done_mask);
+                const int groups_here = (min((int)block_row*SEP_ROWS + SEP_ROWS, b.a.h) - (int)block_row*SEP_ROWS + 3)/4;
+                if (done_mask == (1u << groups_here) - 1u) return false;   // (no barrier is skipped by only some threads: the mask is the block's)
+            }
+        }
+        return true;
+    }
+    __device__ __forceinline__ bool written_elsewhere(int r) const { return TWO_PASS && ((done_mask >> (r >> 2)) & 1u); }
+
+    // one row of a smooth group from its two row entries and the group's terms: eleven vector operations and nothing scalar — a wave
+    // issues one instruction of ANY kind per turn, so the selects and branches on the rows' parity that used to sit here cost as much as
+    // the arithmetic (347 scalar against 470 vector instructions per wave)
+    __device__ __forceinline__ uint32_t smooth_row(const float4 r0, const float4 r1, const bool one_square, const DefaultSmoothTerms& terms) const {
+        return default_smooth_rgb(default_smooth_pixel(m, r0.w, [&] { return default_width_by_rows(terms, r0.x, r1.x); }, terms, group_hue, one_square));
+    }
+    // the hue wheel's coordinate at the centre of a pixel of walk row r: from the group's, or by itself
+    __device__ __forceinline__ float wheel_at(int r, float cy) const {
+        if (r < wheel_until) {
+            const float moved = fmaf((3.0f/PI)*m.cx*__builtin_amdgcn_rcpf(group_ring.len*group_ring.len), cy - group_y, group_wheel);
+            return moved - 6.0f*::floorf(moved*(1.0f/6.0f));
+        }
+        return default_wheel(m.cx, cy, hue_shift);
+    }
+    // one row by the tiers that look at every pixel by itself
+    __device__ __forceinline__ uint32_t general_row(int r, const float4 r0, const float4 r1) const {
+        const float4 c0 = b.c0, c1 = b.c1;
+        const float cx = m.cx;
+        uint32_t rgb = 0u;
+        const bool group_shares = r < shared_until;
+        // the sample's checkerboard colour by the parities of its column and row; the row's side is block-uniform (scalar selects)
+        const float even0 = (__float_as_int(r0.y) & 1) ? DEFAULT_ODD : DEFAULT_EVEN, odd0 = (__float_as_int(r0.y) & 1) ? DEFAULT_EVEN : DEFAULT_ODD;
+        const float even1 = (__float_as_int(r1.y) & 1) ? DEFAULT_ODD : DEFAULT_EVEN, odd1 = (__float_as_int(r1.y) & 1) ? DEFAULT_EVEN : DEFAULT_ODD;
+        // (functions, not arrays: evaluated where a tier uses them — the tier that resolves from means does not)
+        auto board_of = [&](int k) -> float { return (k & 1 ? odd_column1 : odd_column0) ? (k & 2 ? odd1 : odd0) : (k & 2 ? even1 : even0); };
+        auto vignette_of = [&](int k) -> float { return clamp01((k & 1 ? c1.z : c0.z)*(k & 2 ? r1.z : r0.z)); };
+        const float cy = 0.5f*(r0.x + r1.x);
+        const float off = 0.5f*(sf::abs(c1.x - c0.x) + sf::abs(r1.x - r0.x));
+        DefaultRing centre = group_ring;
+        DefaultHue hue = group_hue;
+        DefaultSlope slope = group_slope;
+        float slope_y = group_y;
+        bool shared = group_shares;
+        if (!group_shares) {
+            centre = default_ring(cx, cy);
+            // the same test for the pixel alone: its reach is a seventh of the group's, so half of the band that four rows cannot
+            // share (0.05 < |circle| < 0.1 at 4K) is served by one evaluation per pixel instead of four
+            shared = default_may_share(centre, off);
+            if (shared) { hue = default_wheel_colours(wheel_at(r, cy)); slope = default_slope(centre, cx, cy); slope_y = cy; }
+        }
+        DefaultBytes bytes = {0u, 0u, 0u};
+        bool meaned = false;
+        if (shared) {                                             // one ring and one hue for the samples, the ring's width to first order
+            const float lower = fmaf(slope.y, r0.x - slope_y, centre.width*255.0f), upper = fmaf(slope.y, r1.x - slope_y, centre.width*255.0f);
+            const float side = slope.x*(0.5f*(c1.x - c0.x));
+            const bool disc = centre.circle < 0.0f;
+#if SEP_DEFAULT_FLOAT_MEAN
+            // the pixel from MEANS, as a smooth row does, with the ring's width at the pixel's centre (default_width_at_centre) — twelve
+            // operations, no per-sample board or vignette. Within one of the reference like every float mean (no sample
+            // saturates in a shared tier: |circle| > 0.05 keeps the ring term under 0.1).
+            if (!outside && (((__float_as_int(r0.y) ^ __float_as_int(r1.y)) & 1) == 0)) {
+                const DefaultSmoothTerms terms = default_smooth_terms(centre, slope.y, slope_y, (__float_as_int(r0.y) & 1) != 0, m);
+                rgb = default_smooth_rgb(default_smooth_pixel(m, r0.w, [&] { return default_width_at_centre(centre, slope.y, cy, slope_y); }, terms, hue, false));
+                meaned = true;
+            }
+#endif
+            if (!meaned) {
+                default_colour<0>(bytes, hue, lower - side, disc ? DEFAULT_DISC : board_of(0), vignette_of(0));
+                default_colour<1>(bytes, hue, lower + side, disc ? DEFAULT_DISC : board_of(1), vignette_of(1));
+                default_colour<2>(bytes, hue, upper - side, disc ? DEFAULT_DISC : board_of(2), vignette_of(2));
+                default_colour<3>(bytes, hue, upper + side, disc ? DEFAULT_DISC : board_of(3), vignette_of(3));
+            }
+        } else {                                                  // the ring per sample; the hue at the centre if it may be, else per sample
+            const float ux[4] = {c0.x, c1.x, c0.x, c1.x}, uy[4] = {r0.x, r0.x, r1.x, r1.x};
+            DefaultRing ring[4];
+            float widest = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) { ring[k] = default_ring(ux[k], uy[k]); widest = __builtin_fmaxf(widest, ring[k].width); }
+            float width255[4], base255[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) { width255[k] = ring[k].width*255.0f; base255[k] = (ring[k].circle < 0.0f) ? DEFAULT_DISC : board_of(k); }
+            if (centre.len > 8.0f*off) {
+                const float wheel = wheel_at(r, cy);
+                if (default_shares_hue(widest, centre.len, off)) {
+                    hue = default_wheel_colours(wheel);
+                    default_colour<0>(bytes, hue, width255[0], base255[0], vignette_of(0)); default_colour<1>(bytes, hue, width255[1], base255[1], vignette_of(1));
+                    default_colour<2>(bytes, hue, width255[2], base255[2], vignette_of(2)); default_colour<3>(bytes, hue, width255[3], base255[3], vignette_of(3));
+                } else {
+                    // on the ring the glow is wide enough to show the hue turning inside a pixel: the centre's wheel coordinate
+                    // moved by each sample's own angle (one atan2 per pixel instead of four)
+                    const float turn = (3.0f/PI)*__builtin_amdgcn_rcpf(centre.len*centre.len);
+                    const float along = cx*(0.5f*(r1.x - r0.x))*turn, across = cy*(0.5f*(c1.x - c0.x))*turn;   // x dy, y dx
+                    default_colour<0>(bytes, default_hue_beside(wheel, across - along), width255[0], base255[0], vignette_of(0));
+                    default_colour<1>(bytes, default_hue_beside(wheel, -across - along), width255[1], base255[1], vignette_of(1));
+                    default_colour<2>(bytes, default_hue_beside(wheel, across + along), width255[2], base255[2], vignette_of(2));
+                    default_colour<3>(bytes, default_hue_beside(wheel, along - across), width255[3], base255[3], vignette_of(3));
+                }
+            } else {                                              // next to the origin: every sample by itself
+                default_colour<0>(bytes, default_hue(ux[0], uy[0], hue_shift), width255[0], base255[0], vignette_of(0));
+                default_colour<1>(bytes, default_hue(ux[1], uy[1], hue_shift), width255[1], base255[1], vignette_of(1));
+                default_colour<2>(bytes, default_hue(ux[2], uy[2], hue_shift), width255[2], base255[2], vignette_of(2));
+                default_colour<3>(bytes, default_hue(ux[3], uy[3], hue_shift), width255[3], base255[3], vignette_of(3));
+            }
+        }
+        if (outside) {                                            // camera.glsl:83 / default.glsl:14-16, per column: 0.15 grey = byte 38
+            const uint32_t keep = ((__float_as_int(c0.w) != 0) ? 0u : 0x00ff00ffu) | ((__float_as_int(c1.w) != 0) ? 0u : 0xff00ff00u);
+            const uint32_t grey = 0x26262626u & ~keep;
+            bytes.red = (bytes.red & keep) | grey; bytes.green = (bytes.green & keep) | grey; bytes.blue = (bytes.blue & keep) | grey;
+        }
+        // final.glsl's mean of the four RGBA8 texels as an INTEGER mean per channel, (sum + 2) >> 2 with the sum of a register's
+        // four bytes from v_sad_u8: what resolve_channel's float chain gives except on ties (sum = 2 mod 4), which its rounding
+        // noise decides either way — 1 LSB, like every approximation of this kernel (8 instructions instead of 60)
+        if (!meaned)
+            rgb = (__builtin_amdgcn_sad_u8(bytes.red, 0u, 2u) >> 2) | ((__builtin_amdgcn_sad_u8(bytes.green, 0u, 2u) >> 2) << 8)
+                | ((__builtin_amdgcn_sad_u8(bytes.blue, 0u, 2u) >> 2) << 16);
+        return rgb;
+    }
+    // the rest of this lane's evaluation at cy (group_ring is made there already), for the walk's rows below `until`
+    __device__ __forceinline__ void evaluate_group(float cy, int until) {
+        group_hue = default_hue(m.cx, cy, hue_shift); group_slope = default_slope(group_ring, m.cx, cy); group_y = cy; shared_until = until;
+    }
+    __device__ __forceinline__ void fill(uint32_t (*staged)[SEP_PIXELS], int block_row) {
+        const RenderArgs& a = b.a; const float4* rows = b.rows; const int tid = b.tid;
+#pragma unroll 1
+        for (int r = 0; r < SEP_ROWS; r += 4) {
+            const int py = block_row*SEP_ROWS + r;
+            if (py >= a.h) break;
+            if (written_elsewhere(r)) continue;                           // by k_default_quads
+            const float4 r0 = rows[2*py], r1 = rows[2*py + 1];            // block-uniform: scalar loads
+            const float row_step = sf::abs(r1.x - r0.x);
+            if (r >= smooth_until) {
+                // THE SMOOTH TIER where every lane of the wave may share its evaluation. One evaluation serves the WHOLE walk of a full
+                // block when the test holds over its sixteen rows (|circle| > 0.3 at 4K: two thirds of the frame), else four rows at a
+                // time; rows whose two sample rows sit in different squares of the checkerboard, and waves with a lane that fails,
+                // take the tiers of general_row.
+                bool whole_walk = false;
+                if (r == 0 && (int)block_row*SEP_ROWS + SEP_ROWS <= a.h && SEP_ROWS > 4) {
+                    const float cy = 0.5f*(rows[2*py + SEP_ROWS - 1].x + rows[2*py + SEP_ROWS].x);
+                    const float reach = default_rows_reach(m, (float)SEP_ROWS - 0.5f, row_step);
+                    group_ring = default_ring(m.cx, cy);
+                    if (__builtin_amdgcn_ballot_w64(!outside && default_may_share(group_ring, reach)) == __builtin_amdgcn_ballot_w64(true)) {
+                        evaluate_group(cy, SEP_ROWS); smooth_until = SEP_ROWS; whole_walk = true;
+                    }
+                }
+                if (!whole_walk) {
+                    const bool attempted = py + 3 < a.h;
+                    float cy = 0.0f;
+                    bool fine = false;
+                    if (attempted) {
+                        cy = 0.5f*(rows[2*py + 3].x + rows[2*py + 4].x);
+                        const float reach = default_rows_reach(m, 3.5f, row_step);
+                        group_ring = default_ring(m.cx, cy);
+                        if (default_may_share(group_ring, reach)) { evaluate_group(cy, r + 4); fine = !outside; }
+                    }
+                    if (__builtin_amdgcn_ballot_w64(fine) == __builtin_amdgcn_ballot_w64(true)) smooth_until = r + 4;
+                    else if (attempted) {
+                        // the group's rows go through the tiers of general_row, pixel by pixel: ONE arctangent for the four rows of a lane,
+                        // at the group's middle; a row moves the wheel by its own angle x*dy/len² (default_hue_beside: second order
+                        // in dy/len, < 1e-5 of the wheel where the ring lives), unless the lane sits next to the origin
+                        const float reach = default_rows_reach(m, 3.5f, row_step);
+                        group_wheel = default_wheel(m.cx, cy, hue_shift);
+                        group_y = cy;
+                        wheel_until = (group_ring.len > 16.0f*reach) ? r + 4 : 0;
+                    }
+                }
+            }
+            if (r < smooth_until && py + 3 < a.h) {
+                // the group's eight row entries in one fetch (a fetch per row is a round trip to the L2 in front of fifteen operations)
+                float4 e[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) e[k] = rows[2*py + k];
+                // (the eight sample rows in one square of the checkerboard's rows — 66 groups in 67 at 4K; the others go below)
+                int mixed = 0;
+#pragma unroll
+                for (int k = 1; k < 8; k++) mixed |= __float_as_int(e[k].y) ^ __float_as_int(e[0].y);
+                if ((mixed & 1) == 0) {
+                    const DefaultSmoothTerms terms = default_smooth_terms(group_ring, group_slope.y, group_y, (__float_as_int(e[0].y) & 1) != 0, m);
+                    if (wave_one_square) {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) staged[r + k][tid] = smooth_row(e[2*k], e[2*k + 1], true, terms);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) staged[r + k][tid] = smooth_row(e[2*k], e[2*k + 1], false, terms);
+                    }
+                    continue;
+                }
+            }
+#pragma unroll 1
+            for (int k = 0; k < 4; k++) {
+                if (py + k >= a.h) break;
+                const float4 q0 = rows[2*(py + k)], q1 = rows[2*(py + k) + 1];
+                staged[r + k][tid] = general_row(r + k, q0, q1);
+            }
+        }
+    }
+};
+
 
 #ifndef SEP_WAVES
 #define SEP_WAVES 8                     // waves per SIMD asked of the compiler (tools/variants.sh: 4 halves the occupancy, to tell latency from issue)
@@ -257,334 +651,26 @@ constexpr int sep_waves(int sep_rows) {
 // does not retire before its stores are acknowledged — microseconds under load — and a block that makes one walk spends that time
 // holding its registers and LDS: default.glsl's smooth frames ran at 3.7 TB/s with their waves 87 % idle, and neither fewer
 // instructions nor fewer LDS operations moved them.)
-// (TWO_PASS: default.glsl after k_default_quads — the instance that reads that kernel's marks; a template argument because even
-// the untaken branches on a null map cost the one-pass kernel 3 %)
-template <int KIND, int SEP_ROWS, int CHUNKS = 1, bool TWO_PASS = false>
-__global__ __launch_bounds__(SEP_PIXELS) __attribute__((amdgpu_waves_per_eu(sep_waves(SEP_ROWS)))) void k_separable_fused(const RenderArgs a, const SepTables t) {
+// The row walk, written once for the three row bodies (BODY: BarsRows, WaveformRows, DefaultRows above): the column entries, the walks,
+// the staged rows, the barrier and the two store tails.
+template <int SEP_ROWS, int CHUNKS, class BODY>
+__device__ __forceinline__ void separable_walk(const RenderArgs& a, const SepTables& t) {
     // a pixel is staged as ONE dword (red in the low byte): 64 lanes write 64 consecutive banks in one pass. (As three byte stores per
     // pixel — lanes sharing dwords — the LDS' write port bounded the smooth frames of default.glsl: 6.4 us where issue asks for 4.)
     __shared__ __attribute__((aligned(16))) uint32_t staged[SEP_ROWS][SEP_PIXELS];
     const int frame = blockIdx.z;
     const int tid = threadIdx.x;
     const int px = blockIdx.x*SEP_PIXELS + tid;
-#ifdef SEP_LDS_PAD                                                     // tools/variants.sh: LDS nobody uses, to cap the blocks per CU (latency or issue?)
-    __shared__ uint32_t occupancy_pad[SEP_LDS_PAD/4];
-    if (a.w < 0) occupancy_pad[tid] = (uint32_t)tid;
-#endif
     const float4* columns = t.columns + (long)frame*a.wr;
-    const float4* rows = t.rows + (long)frame*a.hr;
     const int i0 = (2*px < a.wr) ? 2*px : a.wr - 1, i1 = (2*px + 1 < a.wr) ? 2*px + 1 : a.wr - 1;
-    const float4 c0 = columns[i0], c1 = columns[i1];
-    // waveform.frag: every channel of a sample is 1 or 0.2, so a pixel's byte is a function of WHICH of its four samples are inside
-    // the wave: sixteen blocks, resolved once per thread block by the chain every kernel uses
-    __shared__ uint8_t inside_lut[16];
-    if constexpr (KIND == SEP_WAVEFORM) {
-        if (tid < 16) {
-            uint32_t pattern[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) pattern[k] = unorm8(((tid >> k) & 1) ? 1.0f : 0.2f);
-            inside_lut[tid] = (uint8_t)resolve_channel_any<2>(pattern, a.subsample, 0);
-        }
-        __syncthreads();
-    }
-    const float tau = a.dyn ? a.dyn[a.frame0 + frame].iTau : a.u.iTau;
-    const float hue_shift = (2.0f*TAU*tau) - (PI/4.0f);               // default.glsl:22, the generic chain's operations
-    (void)hue_shift;
-    const bool odd_column0 = (__float_as_int(c0.y) & 1) != 0, odd_column1 = (__float_as_int(c1.y) & 1) != 0;   // default.glsl only
-    const bool outside = (__float_as_int(c0.w) | __float_as_int(c1.w)) != 0;
-    const float cx = 0.5f*(c0.x + c1.x);
-    // smooth tier of default.glsl: the pixel column's means (see the row loop)
-    // (few registers across the walk — the kernel lives at 64: the odd rows' means are (0.20 + 0.22)*255 times the column mean minus the
-    // even rows', what a group needs beyond that it derives when it begins)
-    float smooth_cz = 0.0f, smooth_g0 = 0.0f, smooth_b0 = 0.0f;
-    int smooth_until = 0;                                              // wave-uniform: rows [r, smooth_until) of the walk are smooth for every lane of the wave
-    const bool wave_one_square = __builtin_amdgcn_ballot_w64(odd_column0 == odd_column1) == __builtin_amdgcn_ballot_w64(true);
-    if constexpr (KIND == SEP_DEFAULT) {
-        // the checkerboard under a sample: (column parity ^ row parity) ? 0.22 : 0.20 (default.glsl:4-8)
-        const float even_rows0 = odd_column0 ? DEFAULT_ODD : DEFAULT_EVEN, even_rows1 = odd_column1 ? DEFAULT_ODD : DEFAULT_EVEN;
-        smooth_cz = 0.5f*(c0.z + c1.z);
-        smooth_g0 = 0.5f*fmaf(c0.z, even_rows0, c1.z*even_rows1);
-        smooth_b0 = 0.5f*(even_rows0 + even_rows1);
-    }
-    (void)smooth_cz; (void)smooth_g0; (void)smooth_b0; (void)smooth_until; (void)wave_one_square;
-    float group_wheel = 0.0f; int wheel_until = 0; (void)group_wheel; (void)wheel_until;
-    int shared_until = 0; bool attempted = false; (void)attempted; DefaultRing group_ring = {}; DefaultHue group_hue = {}; DefaultSlope group_slope = {}; float group_y = 0.0f;
-    (void)odd_column0; (void)odd_column1; (void)outside; (void)cx; (void)shared_until; (void)group_ring; (void)group_hue; (void)group_slope; (void)group_y;
-#pragma unroll 1
-    for (int chunk = 0; chunk < CHUNKS; chunk++) {
+    const SepBlock block = {a, t, t.rows + (long)frame*a.hr, columns[i0], columns[i1], frame, tid};
+    BODY body(block);
+    auto walk = [&](const int chunk) -> bool {                        // false: the frame has no such walk, nor any below it
         const int block_row = blockIdx.y*CHUNKS + chunk;               // which walk of the frame
-        if (block_row*SEP_ROWS >= a.h) break;
-        if (chunk) {
-            __syncthreads();                                           // the previous walk's rows have left the LDS
-            smooth_until = 0; shared_until = 0; attempted = false; wheel_until = 0;
-        }
-        // default.glsl in two passes: the groups of four rows k_default_quads has already written (block-uniform: a block's 256 pixels are
-        // one wave of that kernel)
-        unsigned done_mask = 0u;
-        if constexpr (KIND == SEP_DEFAULT && TWO_PASS) {
-            if (t.done) {
-                const uint8_t* done = t.done + ((long)frame*t.done_groups + (block_row*SEP_ROWS)/4)*t.done_blocks + blockIdx.x;
-#pragma unroll
-                for (int g = 0; g < SEP_ROWS/4; g++)
-                    if ((int)block_row*SEP_ROWS + 4*g < a.h && done[(long)g*t.done_blocks]) done_mask |= 1u << g;
-                done_mask = __builtin_amdgcn_readfirstlane(done_mask);
-                const int groups_here = (min((int)block_row*SEP_ROWS + SEP_ROWS, a.h) - (int)block_row*SEP_ROWS + 3)/4;
-                if (done_mask == (1u << groups_here) - 1u) continue;    // nothing left of this walk (no barrier is skipped by only some threads: the mask is the block's)
-            }
-        }
-        if constexpr (KIND == SEP_DEFAULT) {
-            // default.glsl: the walk in groups of four rows. (A row of the tiers below is ~3 KB of code: it exists once, in a loop.)
-            static_assert(SEP_ROWS % 4 == 0, "the walk is made of groups of four rows");
-            auto stage = [&](int r, uint32_t rgb) {
-                staged[r][tid] = rgb;
-            };
-            // one row of a smooth group from its two row entries (see the group's prologue): eleven vector operations and nothing
-            // scalar — a wave issues one instruction of ANY kind per turn, so the selects and branches on the rows' parity that used to
-            // sit here cost as much as the arithmetic (347 scalar against 470 vector instructions per wave)
-            // (`offset` = the ring's width at gluv.y = 0 by the group's slope: w(y) = offset + slope.y*y; `ground_of_rows`, `base_of_rows` =
-            // the means of the group's rows: the disc's, or the checkerboard's by the parity its eight sample rows share)
-            auto smooth_row = [&](const float4 r0, const float4 r1, const bool one_square, const float ground_of_rows, const float base_of_rows, const float half_slope, const float offset) -> uint32_t {
-#ifdef SEP_STUB_SMOOTH                                                 // tools/variants.sh: what do the smooth rows' operations cost?
-                return __float_as_uint(r0.x + smooth_cz) & 0xffffffu;
-#endif
-                const float vignette = clamp01(smooth_cz*r0.w);
-                const float ring = fmaf(half_slope, r0.x, fmaf(half_slope, r1.x, offset))*vignette;
-                const float ground = one_square ? base_of_rows*vignette                       // min(r*c*B, B) = B*min(r*c, 1)
-                                                : __builtin_fminf(r0.w*ground_of_rows, base_of_rows);
-                uint32_t rgb = __builtin_amdgcn_cvt_pk_u8_f32(fmaf(ring, group_hue.red, ground), 0u, 0u);
-                rgb = __builtin_amdgcn_cvt_pk_u8_f32(fmaf(ring, group_hue.green, ground), 1u, rgb);
-                return __builtin_amdgcn_cvt_pk_u8_f32(fmaf(ring, group_hue.blue, ground), 2u, rgb);
-            };
-            // one row by the tiers that look at every pixel by itself
-            auto general_row = [&](int r, const float4 r0, const float4 r1) -> uint32_t {
-                uint32_t rgb = 0u;
-                // the hue wheel's coordinate at the pixel's centre: from the group's, or by itself
-                auto wheel_at = [&](float cy) -> float {
-                    if (r < wheel_until) {
-                        const float moved = fmaf((3.0f/PI)*cx*__builtin_amdgcn_rcpf(group_ring.len*group_ring.len), cy - group_y, group_wheel);
-                        return moved - 6.0f*::floorf(moved*(1.0f/6.0f));
-                    }
-                    return default_wheel(cx, cy, hue_shift);
-                };
-                const bool group_shares = r < shared_until;
-                // the sample's checkerboard colour by the parities of its column and row; the row's side is block-uniform (scalar selects)
-                const float even0 = (__float_as_int(r0.y) & 1) ? DEFAULT_ODD : DEFAULT_EVEN, odd0 = (__float_as_int(r0.y) & 1) ? DEFAULT_EVEN : DEFAULT_ODD;
-                const float even1 = (__float_as_int(r1.y) & 1) ? DEFAULT_ODD : DEFAULT_EVEN, odd1 = (__float_as_int(r1.y) & 1) ? DEFAULT_EVEN : DEFAULT_ODD;
-                // (functions, not arrays: evaluated where a tier uses them — the tier that resolves from means does not)
-                auto board_of = [&](int k) -> float { return (k & 1 ? odd_column1 : odd_column0) ? (k & 2 ? odd1 : odd0) : (k & 2 ? even1 : even0); };
-                auto vignette_of = [&](int k) -> float { return clamp01((k & 1 ? c1.z : c0.z)*(k & 2 ? r1.z : r0.z)); };
-                const float cy = 0.5f*(r0.x + r1.x);
-                const float off = 0.5f*(sf::abs(c1.x - c0.x) + sf::abs(r1.x - r0.x));
-                DefaultRing centre = group_ring;
-                DefaultHue hue = group_hue;
-                DefaultSlope slope = group_slope;
-                float slope_y = group_y;
-                bool shared = group_shares;
-                if (!group_shares) {
-                    centre = default_ring(cx, cy);
-                    // the same test for the pixel alone: its reach is a seventh of the group's, so half of the band that four rows cannot
-                    // share (0.05 < |circle| < 0.1 at 4K) is served by one evaluation per pixel instead of four
-                    shared = default_shares_slope(centre, off) && default_shares_hue(1.5f*centre.width, centre.len, off);
-#ifdef SEP_STUB_UNSHARED                                               // tools/variants.sh: what does the per-sample tier cost? (wrong pixels in the band)
-                    shared = true;
-#endif
-                    if (shared) { hue = default_wheel_colours(wheel_at(cy)); slope = default_slope(centre, cx, cy); slope_y = cy; }
-                }
-                DefaultBytes bytes = {0u, 0u, 0u};
-                bool meaned = false;
-                if (shared) {                                             // one ring and one hue for the samples, the ring's width to first order
-                    const float lower = fmaf(slope.y, r0.x - slope_y, centre.width*255.0f), upper = fmaf(slope.y, r1.x - slope_y, centre.width*255.0f);
-                    const float side = slope.x*(0.5f*(c1.x - c0.x));
-                    const bool disc = centre.circle < 0.0f;
-#if SEP_DEFAULT_FLOAT_MEAN
-                    // the pixel from MEANS, as a smooth row does (see the group's prologue), with the ring's width at the pixel's centre:
-                    // mean_k vig_k*(base_k + w_k*hue) = min(r*G, B) + min(c*r, 1)*w(centre)*hue up to second-order terms — twelve
-                    // operations, no per-sample board or vignette. Within one of the reference like every float mean (no sample
-                    // saturates in a shared tier: |circle| > 0.05 keeps the ring term under 0.1).
-                    if (!outside && (((__float_as_int(r0.y) ^ __float_as_int(r1.y)) & 1) == 0)) {
-                        const bool odd_rows = (__float_as_int(r0.y) & 1) != 0;
-                        const float vignette = clamp01(smooth_cz*r0.w);
-                        const float ring = fmaf(slope.y, cy - slope_y, centre.width*255.0f)*vignette;
-                        const float ground = __builtin_fminf(r0.w*(disc ? DEFAULT_DISC*smooth_cz : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD)*smooth_cz - smooth_g0 : smooth_g0)), disc ? DEFAULT_DISC : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD) - smooth_b0 : smooth_b0));
-                        rgb = __builtin_amdgcn_cvt_pk_u8_f32(fmaf(ring, hue.red, ground), 0u, 0u);
-                        rgb = __builtin_amdgcn_cvt_pk_u8_f32(fmaf(ring, hue.green, ground), 1u, rgb);
-                        rgb = __builtin_amdgcn_cvt_pk_u8_f32(fmaf(ring, hue.blue, ground), 2u, rgb);
-                        meaned = true;
-                    }
-#endif
-                    if (!meaned) {
-                    default_colour<0>(bytes, hue, lower - side, disc ? DEFAULT_DISC : board_of(0), vignette_of(0));
-                    default_colour<1>(bytes, hue, lower + side, disc ? DEFAULT_DISC : board_of(1), vignette_of(1));
-                    default_colour<2>(bytes, hue, upper - side, disc ? DEFAULT_DISC : board_of(2), vignette_of(2));
-                    default_colour<3>(bytes, hue, upper + side, disc ? DEFAULT_DISC : board_of(3), vignette_of(3));
-                    }
-                } else {                                                  // the ring per sample; the hue at the centre if it may be, else per sample
-                    const float ux[4] = {c0.x, c1.x, c0.x, c1.x}, uy[4] = {r0.x, r0.x, r1.x, r1.x};
-                    DefaultRing ring[4];
-                    float widest = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) { ring[k] = default_ring(ux[k], uy[k]); widest = __builtin_fmaxf(widest, ring[k].width); }
-                    float width255[4], base255[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) { width255[k] = ring[k].width*255.0f; base255[k] = (ring[k].circle < 0.0f) ? DEFAULT_DISC : board_of(k); }
-                    if (centre.len > 8.0f*off) {
-                        const float wheel = wheel_at(cy);
-                        if (default_shares_hue(widest, centre.len, off)) {
-                            hue = default_wheel_colours(wheel);
-                            default_colour<0>(bytes, hue, width255[0], base255[0], vignette_of(0)); default_colour<1>(bytes, hue, width255[1], base255[1], vignette_of(1));
-                            default_colour<2>(bytes, hue, width255[2], base255[2], vignette_of(2)); default_colour<3>(bytes, hue, width255[3], base255[3], vignette_of(3));
-                        } else {
-                            // on the ring the glow is wide enough to show the hue turning inside a pixel: the centre's wheel coordinate
-                            // moved by each sample's own angle (one atan2 per pixel instead of four)
-                            const float turn = (3.0f/PI)*__builtin_amdgcn_rcpf(centre.len*centre.len);
-                            const float along = cx*(0.5f*(r1.x - r0.x))*turn, across = cy*(0.5f*(c1.x - c0.x))*turn;   // x dy, y dx
-                            default_colour<0>(bytes, default_hue_beside(wheel, across - along), width255[0], base255[0], vignette_of(0));
-                            default_colour<1>(bytes, default_hue_beside(wheel, -across - along), width255[1], base255[1], vignette_of(1));
-                            default_colour<2>(bytes, default_hue_beside(wheel, across + along), width255[2], base255[2], vignette_of(2));
-                            default_colour<3>(bytes, default_hue_beside(wheel, along - across), width255[3], base255[3], vignette_of(3));
-                        }
-                    } else {                                              // next to the origin: every sample by itself
-                        default_colour<0>(bytes, default_hue(ux[0], uy[0], hue_shift), width255[0], base255[0], vignette_of(0));
-                        default_colour<1>(bytes, default_hue(ux[1], uy[1], hue_shift), width255[1], base255[1], vignette_of(1));
-                        default_colour<2>(bytes, default_hue(ux[2], uy[2], hue_shift), width255[2], base255[2], vignette_of(2));
-                        default_colour<3>(bytes, default_hue(ux[3], uy[3], hue_shift), width255[3], base255[3], vignette_of(3));
-                    }
-                }
-                if (outside) {                                            // camera.glsl:83 / default.glsl:14-16, per column: 0.15 grey = byte 38
-                    const uint32_t keep = ((__float_as_int(c0.w) != 0) ? 0u : 0x00ff00ffu) | ((__float_as_int(c1.w) != 0) ? 0u : 0xff00ff00u);
-                    const uint32_t grey = 0x26262626u & ~keep;
-                    bytes.red = (bytes.red & keep) | grey; bytes.green = (bytes.green & keep) | grey; bytes.blue = (bytes.blue & keep) | grey;
-                }
-                // final.glsl's mean of the four RGBA8 texels as an INTEGER mean per channel, (sum + 2) >> 2 with the sum of a register's
-                // four bytes from v_sad_u8: what resolve_channel's float chain gives except on ties (sum = 2 mod 4), which its rounding
-                // noise decides either way — 1 LSB, like every approximation of this kernel (8 instructions instead of 60)
-                if (!meaned)
-                    rgb = (__builtin_amdgcn_sad_u8(bytes.red, 0u, 2u) >> 2) | ((__builtin_amdgcn_sad_u8(bytes.green, 0u, 2u) >> 2) << 8)
-                        | ((__builtin_amdgcn_sad_u8(bytes.blue, 0u, 2u) >> 2) << 16);
-                return rgb;
-            };
-#pragma unroll 1
-            for (int r = 0; r < SEP_ROWS; r += 4) {
-                const int py = block_row*SEP_ROWS + r;
-                if (py >= a.h) break;
-                if (TWO_PASS && ((done_mask >> (r >> 2)) & 1u)) continue;  // written by k_default_quads
-                const float4 r0 = rows[2*py], r1 = rows[2*py + 1];        // block-uniform: scalar loads
-                // rows in groups of four: the group's first row evaluates the polar terms at the point in the middle of its sixteen samples
-                // and, where default_shares_slope / default_shares_hue allow, the four rows use them (`shared_until` = the first block row
-                // they no longer serve)
-                if (r >= smooth_until) {
-                    // THE SMOOTH TIER (round 4). Where every lane of the wave may share one evaluation of the polar terms, the pixel is
-                    // resolved from MEANS in float: mean_k vig_k*(base_k + w_k*hue) over its four samples k = (column i, row j) with
-                    // vig_k = min(c_i*r_j, 1) is, up to terms far below the quantisation step,
-                    //     min(mean_j r_j * mean_i c_i*base_i, mean_i base_i)  +  min(mean_i c_i * mean_j r_j, 1) * w(pixel centre) * hue
-                    // — the products factorise exactly, the clamp differs only where some of the four products exceed 1 and others do not
-                    // (the middle of the frame, where they differ by 1e-4), the covariance of vig and w inside a pixel is second order
-                    // (< 0.005 LSB at the frame's edge). Column means live in registers for the walk, row means in the row table (.w):
-                    // ≈ 20 operations per pixel. Against the reference, which quantises each sample: the mean of four roundings is within
-                    // 1/2 of the mean, so the bytes are roundings of numbers within 1/2 (+ 0.03) of each other — at most ONE apart, the
-                    // bound of every fused kernel (no sample saturates here: |circle| > 0.1 keeps the ring term under 0.03).
-                    // One evaluation serves the WHOLE walk of a full block when the test holds over its sixteen rows (|circle| > 0.3 at 4K:
-                    // two thirds of the frame), else four rows at a time; rows whose two sample rows sit in different squares of the
-                    // checkerboard, and waves with a lane that fails, take the tiers below.
-                    bool whole_walk = false;
-                    if (r == 0 && (int)block_row*SEP_ROWS + SEP_ROWS <= a.h && SEP_ROWS > 4) {
-                        const float cy = 0.5f*(rows[2*py + SEP_ROWS - 1].x + rows[2*py + SEP_ROWS].x);
-                        const float reach = 0.5f*sf::abs(c1.x - c0.x) + ((float)SEP_ROWS - 0.5f)*sf::abs(r1.x - r0.x);
-                        group_ring = default_ring(cx, cy);
-                        const bool fine = !outside && default_shares_slope(group_ring, reach) && default_shares_hue(1.5f*group_ring.width, group_ring.len, reach);
-                        if (__builtin_amdgcn_ballot_w64(fine) == __builtin_amdgcn_ballot_w64(true)) {
-                            group_hue = default_hue(cx, cy, hue_shift); group_slope = default_slope(group_ring, cx, cy); group_y = cy;
-                            shared_until = SEP_ROWS; smooth_until = SEP_ROWS; whole_walk = true;
-                        }
-                    }
-                    if (!whole_walk) {
-                        attempted = py + 3 < a.h;
-                        bool fine = false;
-                        if (attempted) {
-                            const float cy = 0.5f*(rows[2*py + 3].x + rows[2*py + 4].x);
-                            const float reach = 0.5f*sf::abs(c1.x - c0.x) + 3.5f*sf::abs(r1.x - r0.x);
-                            group_ring = default_ring(cx, cy);
-                            if (default_shares_slope(group_ring, reach) && default_shares_hue(1.5f*group_ring.width, group_ring.len, reach)) {
-                                group_hue = default_hue(cx, cy, hue_shift); group_slope = default_slope(group_ring, cx, cy); group_y = cy; shared_until = r + 4;
-                                fine = !outside;
-                            }
-                        }
-                        if (__builtin_amdgcn_ballot_w64(fine) == __builtin_amdgcn_ballot_w64(true)) smooth_until = r + 4;
-                        else if (attempted) {
-                            // the group's rows go through the tiers below, pixel by pixel: ONE arctangent for the four rows of a lane,
-                            // at the group's middle; a row moves the wheel by its own angle x*dy/len² (default_hue_beside: second order
-                            // in dy/len, < 1e-5 of the wheel where the ring lives), unless the lane sits next to the origin
-                            const float cy = 0.5f*(rows[2*py + 3].x + rows[2*py + 4].x);
-                            const float reach = 0.5f*sf::abs(c1.x - c0.x) + 3.5f*sf::abs(r1.x - r0.x);
-                            group_wheel = default_wheel(cx, cy, hue_shift);
-                            group_y = cy;
-                            wheel_until = (group_ring.len > 16.0f*reach) ? r + 4 : 0;
-                        }
-                    }
-                }
-                if (r < smooth_until && py + 3 < a.h) {
-                    // the group's eight row entries in one fetch (a fetch per row is a round trip to the L2 in front of fifteen operations)
-                    float4 e[8];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) e[k] = rows[2*py + k];
-                    // (the eight sample rows in one square of the checkerboard's rows — 66 groups in 67 at 4K; the others go below)
-                    int mixed = 0;
-#pragma unroll
-                    for (int k = 1; k < 8; k++) mixed |= __float_as_int(e[k].y) ^ __float_as_int(e[0].y);
-                    if ((mixed & 1) == 0) {
-                        const bool odd_rows = (__float_as_int(e[0].y) & 1) != 0;
-                        const bool disc = group_ring.circle < 0.0f;
-                        const float ground_of_rows = disc ? DEFAULT_DISC*smooth_cz : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD)*smooth_cz - smooth_g0 : smooth_g0);
-                        const float base_of_rows = disc ? DEFAULT_DISC : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD) - smooth_b0 : smooth_b0);
-                        const float half_slope = 0.5f*group_slope.y, offset = fmaf(-group_slope.y, group_y, group_ring.width*255.0f);
-                        if (wave_one_square) {                          // wave-uniform: both sample columns of every lane in one square of the checkerboard's columns
-#pragma unroll
-                            for (int k = 0; k < 4; k++) stage(r + k, smooth_row(e[2*k], e[2*k + 1], true, ground_of_rows, base_of_rows, half_slope, offset));
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 4; k++) stage(r + k, smooth_row(e[2*k], e[2*k + 1], false, ground_of_rows, base_of_rows, half_slope, offset));
-                        }
-                        continue;
-                    }
-                }
-#pragma unroll 1
-                for (int k = 0; k < 4; k++) {
-                    if (py + k >= a.h) break;
-                    const float4 q0 = rows[2*(py + k)], q1 = rows[2*(py + k) + 1];
-                    stage(r + k, general_row(r + k, q0, q1));
-                }
-            }
-        } else {
-#pragma unroll
-        for (int r = 0; r < SEP_ROWS; r++) {
-            const int py = block_row*SEP_ROWS + r;
-            if (py >= a.h) break;
-            const float4 r0 = rows[2*py], r1 = rows[2*py + 1];            // block-uniform: scalar loads
-            uint32_t block[4];                                             // texel order y*2 + x (render_kernels.hpp)
-            uint32_t rgb;                                                  // the output pixel, red in the low byte
-            if constexpr (KIND == SEP_BARS) {
-                // red and green are 0 or 1 per supersample: the resolve of such a block is exact in every step — the sum of the four
-                // texels/255 is their count, count/4 is exact, and the unorm8 write of it is RN(count*63.75) for either kernel size
-                // (the 1-tap kernel's weights are 0.25 each) — so the byte is a function of how many of the pixel's four samples lie
-                // below the column's height: min(max(T - first row, 0), 2) per column.
-                const int j0 = 2*py;
-                const int red = rows_of_pair(__float_as_int(c0.x), j0) + rows_of_pair(__float_as_int(c1.x), j0);
-                const int green = rows_of_pair(__float_as_int(c0.y), j0) + rows_of_pair(__float_as_int(c1.y), j0);
-                // blue adds the ramp 0.4*(sum)*(1 - astuv.y) (bars.frag:17): the generic chain on that channel alone
-                const int t0 = __float_as_int(c0.z), t1 = __float_as_int(c1.z);
-                block[0] = blue_texel((j0 < t0) ? 1.0f : 0.0f, c0.w, r0.y); block[1] = blue_texel((j0 < t1) ? 1.0f : 0.0f, c1.w, r0.y);
-                block[2] = blue_texel((j0 + 1 < t0) ? 1.0f : 0.0f, c0.w, r1.y); block[3] = blue_texel((j0 + 1 < t1) ? 1.0f : 0.0f, c1.w, r1.y);
-                rgb = __builtin_amdgcn_cvt_pk_u8_f32((float)red*63.75f, 0u, resolve_channel_any<2>(block, a.subsample, 16) << 16);
-                rgb = __builtin_amdgcn_cvt_pk_u8_f32((float)green*63.75f, 1u, rgb);
-            } else if constexpr (KIND == SEP_WAVEFORM) {
-                const int j0 = 2*py;
-                rgb = (uint32_t)inside_lut[wave_pattern(__float_as_int(c0.x), __float_as_int(c1.x), j0)]
-                    | ((uint32_t)inside_lut[wave_pattern(__float_as_int(c0.y), __float_as_int(c1.y), j0)] << 8)
-                    | ((uint32_t)inside_lut[wave_pattern(__float_as_int(c0.z), __float_as_int(c1.z), j0)] << 16);
-            }
-            staged[r][tid] = rgb;
-        }
-        }
+        if (block_row*SEP_ROWS >= a.h) return false;
+        if (chunk) __syncthreads();                                    // the previous walk's rows have left the LDS
+        if (!body.begin_walk(chunk != 0, block_row)) return true;
+        body.fill(staged, block_row);
         __syncthreads();
         uint8_t* out = (uint8_t*)a.out + (long)frame*a.out_frame_stride;
         // a full-width block of a frame whose rows are whole dwords: a lane packs four staged pixels into their twelve bytes (three
@@ -592,40 +678,52 @@ __global__ __launch_bounds__(SEP_PIXELS) __attribute__((amdgpu_waves_per_eu(sep_
         // Wave `v` takes rows v, v + 4, ...: the row and its address are SCALAR (as a function of the thread index the compiler spent
         // twenty vector operations per pass on 64-bit products — a sixth of a smooth wave's instructions).
         const int x0 = blockIdx.x*SEP_PIXELS;
-        if (x0 + SEP_PIXELS <= a.w && (a.w & 3) == 0 && ((uintptr_t)out & 3) == 0 && (a.out_frame_stride & 3) == 0) {
+        if (packed_stores(a, x0, out)) {
             const int rows_here = min(SEP_ROWS, a.h - (int)block_row*SEP_ROWS);
-            typedef uint32_t Triple __attribute__((ext_vector_type(3), aligned(4)));
             const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
             uint8_t* const block_out = out + (long)x0*3;                  // block-uniform
             const uint32_t lane_bytes = (uint32_t)lane*12u;
 #pragma unroll
             for (int i = 0; i < SEP_ROWS/4; i++) {
                 const int r = wave + 4*i;
-                if (r < rows_here && !(TWO_PASS && ((done_mask >> (r >> 2)) & 1u))) {
+                if (r < rows_here && !body.written_elsewhere(r)) {
                     const int py = block_row*SEP_ROWS + r;
                     const uint4 p = *(const uint4*)&staged[r][4*lane];
                     uint8_t* row = block_out + (long)(a.top_down ? a.h - 1 - py : py)*a.w*3;
-#ifdef SEP_STUB_STORES                                                 // tools/variants.sh: what do the stores cost? (one lane in 64 stores)
-                    if (lane == (p.x & 63u) + 64u) continue;
-                    if (lane != 0) continue;
-#endif
-                    __builtin_nontemporal_store(Triple{__builtin_amdgcn_perm(p.y, p.x, 0x04020100u), __builtin_amdgcn_perm(p.z, p.y, 0x05040201u),
-                                                       __builtin_amdgcn_perm(p.w, p.z, 0x06050402u)}, (Triple*)(row + lane_bytes));
+                    store_four_pixels(row + lane_bytes, __builtin_amdgcn_perm(p.y, p.x, 0x04020100u), __builtin_amdgcn_perm(p.z, p.y, 0x05040201u),
+                                      __builtin_amdgcn_perm(p.w, p.z, 0x06050402u));
                 }
             }
-            continue;
+            return true;
         }
         const int pixels_here = min(SEP_PIXELS, a.w - x0);
 #pragma unroll 1
         for (int r = 0; r < SEP_ROWS; r++) {
             const int py = block_row*SEP_ROWS + r;
-            if (py < a.h && tid < pixels_here && !(TWO_PASS && ((done_mask >> (r >> 2)) & 1u))) {
+            if (py < a.h && tid < pixels_here && !body.written_elsewhere(r)) {
                 uint8_t* pixel = out + (long)(a.top_down ? a.h - 1 - py : py)*a.w*3 + (long)(x0 + tid)*3;
                 const uint32_t rgb = staged[r][tid];
                 pixel[0] = (uint8_t)rgb; pixel[1] = (uint8_t)(rgb >> 8); pixel[2] = (uint8_t)(rgb >> 16);
             }
         }
+        return true;
+    };
+    // (BODY::one_walk_in_a_loop: around one walk the loop of one turn changes what the compiler emits, and each body keeps what it
+    // had: without it default.glsl's 16-row instance loses 0.6 % of the Basic scene (profiles/separable_refactor_bench.txt), with it
+    // the compiler hoists waveform's unrolled comparisons in front of the walk and its instances take 20 registers instead of 16)
+    if constexpr (CHUNKS == 1 && !BODY::one_walk_in_a_loop) walk(0);
+    else {
+#pragma unroll 1
+        for (int chunk = 0; chunk < CHUNKS; chunk++) if (!walk(chunk)) break;
     }
+}
+template <int KIND, int SEP_ROWS, bool TWO_PASS> struct SepRows { using type = DefaultRows<SEP_ROWS, TWO_PASS>; };
+template <int SEP_ROWS> struct SepRows<SEP_BARS, SEP_ROWS, false> { using type = BarsRows<SEP_ROWS>; };
+template <int SEP_ROWS> struct SepRows<SEP_WAVEFORM, SEP_ROWS, false> { using type = WaveformRows<SEP_ROWS>; };
+template <int KIND, int SEP_ROWS, int CHUNKS = 1, bool TWO_PASS = false>
+__global__ __launch_bounds__(SEP_PIXELS) __attribute__((amdgpu_waves_per_eu(sep_waves(SEP_ROWS)))) void k_separable_fused(const RenderArgs a, const SepTables t) {
+    static_assert(KIND == SEP_DEFAULT || !TWO_PASS, "two passes are default.glsl's");
+    separable_walk<SEP_ROWS, CHUNKS, typename SepRows<KIND, SEP_ROWS, TWO_PASS>::type>(a, t);
 }
 
 // ---- default.glsl's smooth tier, four pixels per lane (round 5) ---------------------------------------------------------------------
@@ -648,15 +746,13 @@ constexpr int DQ_ROWS = 16;                                            // rows o
 #ifndef DQ_WAVES
 #define DQ_WAVES 4                                                     // 128 registers, no spill: 5 waves spill 15, 6 spill 33 and lose a quarter (profiles/r05_basic_quads.txt)
 #endif
-struct DefaultQuadPixel { float cx, half_reach, cz, g0, b0; };        // a pixel column: gluv.x at its centre, half the sample spacing, the column means of the smooth tier
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES))) void k_default_quads(const RenderArgs a, const SepTables t) {
     const int frame = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int y_wave = (blockIdx.y*4 + wave)*DQ_ROWS*DQ_WALKS;
     if (y_wave >= a.h) return;
     const int bx = blockIdx.x;
-    const bool full_block = bx*256 + 256 <= a.w && (a.w & 3) == 0 && (a.out_frame_stride & 3) == 0 && (((uintptr_t)a.out) & 3) == 0;
-    if (!full_block) {                                                 // a partial block of columns: the other kernel's
+    if (!packed_stores(a, bx*256, a.out)) {                            // a partial block of columns: the other kernel's
         const int groups = (min(y_wave + DQ_ROWS*DQ_WALKS, a.h) - y_wave + 3)/4;
         uint8_t* done = t.done + ((long)frame*t.done_groups + y_wave/4)*t.done_blocks + bx;
         for (int g = lane; g < groups; g += 64) done[(long)g*t.done_blocks] = 0;
@@ -667,19 +763,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES)))
     const float4* rows = t.rows + (long)frame*a.hr;
     const float tau = a.dyn ? a.dyn[a.frame0 + frame].iTau : a.u.iTau;
     const float hue_shift = (2.0f*TAU*tau) - (PI/4.0f);               // default.glsl:22
-    DefaultQuadPixel pixel[4];
+    DefaultColumnMeans pixel[4];
     bool outside = false;
 #pragma unroll
     for (int p = 0; p < 4; p++) {
         const float4 c0 = columns[2*p], c1 = columns[2*p + 1];
-        const bool odd0 = (__float_as_int(c0.y) & 1) != 0, odd1 = (__float_as_int(c1.y) & 1) != 0;
-        const float even_rows0 = odd0 ? DEFAULT_ODD : DEFAULT_EVEN, even_rows1 = odd1 ? DEFAULT_ODD : DEFAULT_EVEN;
-        pixel[p].cx = 0.5f*(c0.x + c1.x);
-        pixel[p].half_reach = 0.5f*sf::abs(c1.x - c0.x);
-        pixel[p].cz = 0.5f*(c0.z + c1.z);
-        pixel[p].g0 = 0.5f*fmaf(c0.z, even_rows0, c1.z*even_rows1);
-        pixel[p].b0 = 0.5f*(even_rows0 + even_rows1);
-        outside = outside || ((__float_as_int(c0.w) | __float_as_int(c1.w)) != 0);
+        pixel[p] = default_column_means(c0, c1);
+        outside = outside || default_column_outside(c0, c1);
     }
     uint8_t* out = (uint8_t*)a.out + (long)frame*a.out_frame_stride + (long)px0*3;
     const long pitch = (long)a.w*3;
@@ -692,9 +782,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES)))
         bool fine = !outside;
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            const float reach = pixel[p].half_reach + rows_reach*row_step;
+            const float reach = default_rows_reach(pixel[p], rows_reach, row_step);
             ring[p] = default_ring(pixel[p].cx, cy);
-            fine = fine && default_shares_slope(ring[p], reach) && default_shares_hue(1.5f*ring[p].width, ring[p].len, reach);
+            fine = fine && default_may_share(ring[p], reach);
         }
         if (__builtin_amdgcn_ballot_w64(fine) != everybody) return false;
 #pragma unroll
@@ -729,15 +819,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES)))
         if (lane == 0) done[(long)g*t.done_blocks] = smooth ? 1 : 0;
         if (!smooth) continue;
         const bool odd_rows = (__float_as_int(e[0].y) & 1) != 0;
-        float ground_of_rows[4], base_of_rows[4], half_slope[4], offset[4];
+        DefaultSmoothTerms terms[4];
 #pragma unroll
-        for (int p = 0; p < 4; p++) {
-            const bool disc = ring[p].circle < 0.0f;
-            ground_of_rows[p] = disc ? DEFAULT_DISC*pixel[p].cz : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD)*pixel[p].cz - pixel[p].g0 : pixel[p].g0);
-            base_of_rows[p] = disc ? DEFAULT_DISC : (odd_rows ? (DEFAULT_EVEN + DEFAULT_ODD) - pixel[p].b0 : pixel[p].b0);
-            half_slope[p] = 0.5f*slope_y[p];
-            offset[p] = fmaf(-slope_y[p], group_y, ring[p].width*255.0f);
-        }
+        for (int p = 0; p < 4; p++) terms[p] = default_smooth_terms(ring[p], slope_y[p], group_y, odd_rows, pixel[p]);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             // the row's three values in VECTOR registers: a full-rate form with a scalar source issues at half rate (profiles/r05_ubench_valu_sgpr.txt)
@@ -746,21 +830,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQ_WAVES)))
             asm("v_mov_b32 %0, %1" : "=v"(y1) : "s"(e[2*k + 1].x));
             asm("v_mov_b32 %0, %1" : "=v"(rw) : "s"(e[2*k].w));
             uint32_t d0 = 0u, d1 = 0u, d2 = 0u;                       // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-            float red[4], green[4], blue[4];
+            DefaultChannels c[4];
 #pragma unroll
-            for (int p = 0; p < 4; p++) {
-                const float vignette = clamp01(pixel[p].cz*rw);
-                const float glow = fmaf(half_slope[p], y0, fmaf(half_slope[p], y1, offset[p]))*vignette;
-                const float ground = __builtin_fminf(rw*ground_of_rows[p], base_of_rows[p]);
-                red[p] = fmaf(glow, hue[p].red, ground); green[p] = fmaf(glow, hue[p].green, ground); blue[p] = fmaf(glow, hue[p].blue, ground);
-            }
-            d0 = __builtin_amdgcn_cvt_pk_u8_f32(red[0], 0u, d0); d0 = __builtin_amdgcn_cvt_pk_u8_f32(green[0], 1u, d0); d0 = __builtin_amdgcn_cvt_pk_u8_f32(blue[0], 2u, d0);
-            d0 = __builtin_amdgcn_cvt_pk_u8_f32(red[1], 3u, d0); d1 = __builtin_amdgcn_cvt_pk_u8_f32(green[1], 0u, d1); d1 = __builtin_amdgcn_cvt_pk_u8_f32(blue[1], 1u, d1);
-            d1 = __builtin_amdgcn_cvt_pk_u8_f32(red[2], 2u, d1); d1 = __builtin_amdgcn_cvt_pk_u8_f32(green[2], 3u, d1); d2 = __builtin_amdgcn_cvt_pk_u8_f32(blue[2], 0u, d2);
-            d2 = __builtin_amdgcn_cvt_pk_u8_f32(red[3], 1u, d2); d2 = __builtin_amdgcn_cvt_pk_u8_f32(green[3], 2u, d2); d2 = __builtin_amdgcn_cvt_pk_u8_f32(blue[3], 3u, d2);
+            for (int p = 0; p < 4; p++) c[p] = default_smooth_pixel(pixel[p], rw, [&] { return default_width_by_rows(terms[p], y0, y1); }, terms[p], hue[p], false);
+            d0 = __builtin_amdgcn_cvt_pk_u8_f32(c[0].red, 0u, d0); d0 = __builtin_amdgcn_cvt_pk_u8_f32(c[0].green, 1u, d0); d0 = __builtin_amdgcn_cvt_pk_u8_f32(c[0].blue, 2u, d0);
+            d0 = __builtin_amdgcn_cvt_pk_u8_f32(c[1].red, 3u, d0); d1 = __builtin_amdgcn_cvt_pk_u8_f32(c[1].green, 0u, d1); d1 = __builtin_amdgcn_cvt_pk_u8_f32(c[1].blue, 1u, d1);
+            d1 = __builtin_amdgcn_cvt_pk_u8_f32(c[2].red, 2u, d1); d1 = __builtin_amdgcn_cvt_pk_u8_f32(c[2].green, 3u, d1); d2 = __builtin_amdgcn_cvt_pk_u8_f32(c[2].blue, 0u, d2);
+            d2 = __builtin_amdgcn_cvt_pk_u8_f32(c[3].red, 1u, d2); d2 = __builtin_amdgcn_cvt_pk_u8_f32(c[3].green, 2u, d2); d2 = __builtin_amdgcn_cvt_pk_u8_f32(c[3].blue, 3u, d2);
             const int y = py + k;
-            typedef uint32_t Triple __attribute__((ext_vector_type(3), aligned(4)));
-            __builtin_nontemporal_store(Triple{d0, d1, d2}, (Triple*)(out + (long)(a.top_down ? a.h - 1 - y : y)*pitch));
+            store_four_pixels(out + (long)(a.top_down ? a.h - 1 - y : y)*pitch, d0, d1, d2);
         }
     }
     }
@@ -804,11 +882,6 @@ __device__ __forceinline__ uint32_t bars_pixel(const float4 c0, const float4 c1,
                                     c0.w, c1.w, omy0, omy1);
     return count_byte(red) | (count_byte(green) << 8) | (blue << 16);
 }
-__device__ __forceinline__ uint32_t waveform_pixel(const float4 c0, const float4 c1, int j0, const uint8_t* lut) {
-    return (uint32_t)lut[wave_pattern(__float_as_int(c0.x), __float_as_int(c1.x), j0)]
-         | ((uint32_t)lut[wave_pattern(__float_as_int(c0.y), __float_as_int(c1.y), j0)] << 8)
-         | ((uint32_t)lut[wave_pattern(__float_as_int(c0.z), __float_as_int(c1.z), j0)] << 16);
-}
 // the first pixel row >= `from` at which the row pair (2 py, 2 py + 1) meets the boundary `t` (a row count) of a column
 __device__ __forceinline__ int special_after(int t, int from, int best) {
     const int s = t >> 1;
@@ -831,15 +904,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == SEP
     __shared__ uint8_t inside_lut[16];
     const int frame = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if constexpr (KIND == SEP_WAVEFORM) {
-        if (tid < 16) {
-            uint32_t pattern[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) pattern[k] = unorm8(((tid >> k) & 1) ? 1.0f : 0.2f);
-            inside_lut[tid] = (uint8_t)resolve_channel_any<2>(pattern, a.subsample, 0);
-        }
-        __syncthreads();
-    }
+    if constexpr (KIND == SEP_WAVEFORM) build_inside_lut(inside_lut, tid, a.subsample);
     const int y_first = blockIdx.y*(4*SEP_RUN_ROWS) + wave*SEP_RUN_ROWS;
     if (y_first >= a.h) return;
     const int y_last = min(y_first + SEP_RUN_ROWS, a.h);
@@ -886,7 +951,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == SEP
                 }
             }
         }
-        d0 = p[0] | (p[1] << 24); d1 = (p[1] >> 8) | (p[2] << 16); d2 = (p[2] >> 16) | (p[3] << 8);
+        const FourPixels run = pack_four_pixels(p);
+        d0 = run.d0; d1 = run.d1; d2 = run.d2;
         next = best;
     };
     if (active) rebuild(y_first); else next = 0x7fffffff;
@@ -907,7 +973,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == SEP
                     const float4 c0 = columns[2*k], c1 = columns[2*k + 1];
                     p[k] = (KIND == SEP_BARS) ? bars_pixel(c0, c1, 2*py, omy0, omy1) : waveform_pixel(c0, c1, 2*py, inside_lut);
                 }
-                o0 = p[0] | (p[1] << 24); o1 = (p[1] >> 8) | (p[2] << 16); o2 = (p[2] >> 16) | (p[3] << 8);
+                const FourPixels row = pack_four_pixels(p);
+                o0 = row.d0; o1 = row.d1; o2 = row.d2;
                 rebuild(py + 1);
             }
         } else if constexpr (KIND == SEP_BARS) {
@@ -926,12 +993,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == SEP
             o0 = d0; o1 = d1; o2 = d2;
         }
         if (active) {
-            uint32_t* row = (uint32_t*)(out + (long)(a.top_down ? a.h - 1 - py : py)*pitch);
-            // non-temporal (`global_store_dwordx3 ... nt`): nobody on the device reads a frame back, so its lines need not stay in
-            // the L2 — bars 308 -> 261 us per 60 frames of 4K (5.7 TB/s written = 0.71 of the HBM roof), waveform 293 -> 289 (its
-            // time is the special rows around the wave, not the stores)
-            typedef uint32_t Triple __attribute__((ext_vector_type(3), aligned(4)));
-            __builtin_nontemporal_store(Triple{o0, o1, o2}, (Triple*)row);
+            store_four_pixels(out + (long)(a.top_down ? a.h - 1 - py : py)*pitch, o0, o1, o2);
         }
     }
 }
