@@ -374,6 +374,9 @@ __device__ __forceinline__ void scalar_step(ScalarState& s, double target, const
     if (integrate) s.integral += (s.value*c.dt);                      // :248-249
 }
 
+// the larger of two bit patterns (plain `max` here is sf::max(float, float) of sfmath.hpp, which would convert them)
+__device__ __forceinline__ unsigned larger_bits(unsigned a, unsigned b) { return a > b ? a : b; }
+
 // THREADS x PER >= n values. One wave (THREADS == 64, up to 256 values: the 115-bin stereo spectrogram of the benchmark) needs no
 // barrier at all — the early-out's maximum is a wave reduction; larger states take 1024 threads and two barriers per frame. The
 // frame loop is latency bound (a batch is 60 dependent steps of a few hundred values), so the next frame's targets and
@@ -400,7 +403,7 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
                                                         float* __restrict__ snap, double* __restrict__ snap64) {
     constexpr int WAVES = THREADS/64;
     if (KEEPER_WAVE && threadIdx.x >= THREADS) n = 0;                 // the keeper's wave holds no values
-    __shared__ float red[WAVES > 1 ? WAVES : 1];
+    __shared__ unsigned red[WAVES > 1 ? WAVES : 1];
     __shared__ int skip_shared;
     float value[PER], deriv[PER], prev[PER], target[PER], upcoming[PER], accel_kept[PER];
 #pragma unroll
@@ -428,12 +431,16 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
         const DynCoeffF32 c = c_next;
         const FrameClock clock_now = clock_next; const float loud_now[2] = {loud_next[0], loud_next[1]}; const DynCoeffF64 vol_now = vol_next, std_now = std_next;
         if (keeper && f + 1 < nframes) keeper_fetch(f + 1);
-        float worst = 0.0f;
+        // np.abs(target - value).max() hands a NaN on (dynamics.py:222: the comparison is then false and the system steps; a -inf target
+        // of a log magnitude on digital silence gives -inf - -inf two frames later). fmaxf drops a NaN operand and would freeze the whole
+        // array there, so the maximum is taken over the BIT PATTERNS of the absolute differences: among floats without a sign the unsigned
+        // order is the float order, and every NaN lies above infinity. Lanes past n keep contributing 0.
+        unsigned worst = 0u;
 #pragma unroll
         for (int e = 0; e < PER; e++) {
             const int i = threadIdx.x + e*THREADS;
             target[e] = upcoming[e];
-            if (i < n) worst = fmaxf(worst, fabsf(target[e] - value[e]));
+            if (i < n) worst = larger_bits(worst, __float_as_uint(fabsf(target[e] - value[e])));
         }
         if (f + 1 < nframes) {                                        // in flight while this frame is worked on
             c_next = coeff[f + 1];
@@ -444,17 +451,17 @@ __global__ __launch_bounds__(THREADS + (KEEPER_WAVE ? 64 : 0)) void k_dynamics_s
             }
         }
         if (c.dt != 0.0f) {
-            for (int m = 32; m >= 1; m >>= 1) worst = fmaxf(worst, __shfl_xor(worst, m));
+            for (int m = 32; m >= 1; m >>= 1) worst = larger_bits(worst, (unsigned)__shfl_xor((int)worst, m));
             bool skip;
             if constexpr (WAVES == 1) {
-                skip = worst < precision;                             // np.abs(target - value).max() < precision
+                skip = __uint_as_float(worst) < precision;            // np.abs(target - value).max() < precision
             } else {
                 if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = worst;
                 __syncthreads();
                 if (threadIdx.x == 0) {
-                    float w = red[0];
-                    for (int k = 1; k < WAVES; k++) w = fmaxf(w, red[k]);
-                    skip_shared = (w < precision) ? 1 : 0;
+                    unsigned w = red[0];
+                    for (int k = 1; k < WAVES; k++) w = larger_bits(w, red[k]);
+                    skip_shared = (__uint_as_float(w) < precision) ? 1 : 0;
                 }
                 __syncthreads();
                 skip = skip_shared != 0;
