@@ -103,7 +103,18 @@ template <class I> static int launch_visualizer_tables_and_kernel(Context* ctx, 
     const size_t pixel_entries = tier ? (size_t)frames*((size_t)a.w + a.h)*sizeof(float4) : 0;
     const size_t bars2 = tier ? (size_t)frames*sp.height*2*sizeof(float2) : 0;
     const size_t classes = tier ? (size_t)frames*t.blocks_x*t.blocks_y*8 : 0;
-    const size_t needed = entries + blocks + ysteps + pixel_entries + bars2 + classes;
+    // the strip plan (visualizer_fast.hpp k_visualizer_strip_plan): the float32-cell 2x instances; SHADERFLOW_VIS_STRIP_PLAN=0 launches their
+    // in-kernel form (A/B measurements, and the test that holds the two forms to the same bytes)
+    using Kernel = VisualizerStrip<PITCH, ROWS, STRIP_S ? STRIP_S : 2, STRIP_S ? WALK : 1, CG, HALF>;
+    constexpr bool CAN_PLAN = STRIP_S == 2 && !HALF;
+    const char* plan_env = getenv("SHADERFLOW_VIS_STRIP_PLAN");
+    const bool planned = CAN_PLAN && !(plan_env && atoi(plan_env) == 0);
+    const size_t strips = (size_t)frames*t.blocks_y*Kernel::ROW_GROUPS;
+    // (the weight images only where the kernel reads them: VisualizerStrip::PLAN_COLW)
+    constexpr bool PLAN_IMAGES = CAN_PLAN && VIS_STRIP_PLAN_COLW && ROWS <= Kernel::COLW_SLOTS;
+    const size_t plan_records = planned ? strips*sizeof(int4) : 0, plan_colw = planned && PLAN_IMAGES ? strips*WALK*Kernel::COLW_SLOTS*sizeof(float2) : 0;
+    static_assert(!CAN_PLAN || (WALK*Kernel::COLW_SLOTS*sizeof(float2)) % 16 == 0, "what follows the weight images stays 16-byte aligned");
+    const size_t needed = entries + blocks + ysteps + plan_records + plan_colw + pixel_entries + bars2 + classes;
     if (ctx->vis_tables_bytes < needed) {
         hipStreamSynchronize(s);
         hipFree(ctx->vis_tables); ctx->vis_tables = nullptr; ctx->vis_tables_bytes = 0;
@@ -116,6 +127,10 @@ template <class I> static int launch_visualizer_tables_and_kernel(Context* ctx, 
     t.block_y = t.block_x + (size_t)frames*t.blocks_x;
     t.ysteps = STRIP_S ? (float4*)(t.block_y + (size_t)frames*t.blocks_y) : nullptr;
     char* after = (char*)ctx->vis_tables + entries + blocks + ysteps;
+    int4* records = planned ? (int4*)after : nullptr;
+    float2* images = planned && PLAN_IMAGES ? (float2*)(after + plan_records) : nullptr;
+    t.strip_plan = records; t.strip_colw = images;
+    after += plan_records + plan_colw;
     t.pixel_columns = tier ? (float4*)after : nullptr;
     t.pixel_rows = tier ? t.pixel_columns + (size_t)frames*a.w : nullptr;
     float2* spread = tier ? (float2*)(after + pixel_entries) : nullptr;
@@ -129,6 +144,12 @@ template <class I> static int launch_visualizer_tables_and_kernel(Context* ctx, 
                            (long)a.spectrogram_stride, frames, sp.height, sp.repeat_y, spread);
     }
     hipLaunchKernelGGL(k_visualizer_axes, dim3((a.wr + 127)/128 + (a.hr + 127)/128, frames), dim3(128), 0, s, a, t);
+    if constexpr (CAN_PLAN) {
+        if (planned) {
+            const int per_frame = t.blocks_y*Kernel::ROW_GROUPS;      // one wave per strip, four to a block
+            hipLaunchKernelGGL((k_visualizer_strip_plan<WALK, Kernel::ROW_GROUPS, Kernel::ROWBYTES, Kernel::COLW_SLOTS>), dim3((per_frame + 3)/4, frames), dim3(256), 0, s, a, t, records, images);
+        }
+    }
     if constexpr (STRIP_S >= 2) {
         if (tier) {
             const long tiles = (long)t.blocks_x*t.blocks_y*8;
@@ -137,7 +158,13 @@ template <class I> static int launch_visualizer_tables_and_kernel(Context* ctx, 
     }
     if constexpr (STRIP_S != 0) {
         g_last_kernel = "k_visualizer_strip<" + std::to_string(PITCH) + ", " + std::to_string(ROWS) + ", " + std::to_string(STRIP_S) + ", " + std::to_string(WALK) + ", " + std::to_string(WAVES) + ", " + std::to_string(CG) + (HALF ? ", true>" : ", false>");
-        hipLaunchKernelGGL((k_visualizer_strip<PITCH, ROWS, STRIP_S, WALK, WAVES, CG, HALF>), dim3(t.blocks_x*t.blocks_y, 1, frames), dim3(512), 0, s, a, t);
+        if constexpr (CAN_PLAN) {
+            if (planned) hipLaunchKernelGGL((k_visualizer_strip<PITCH, ROWS, STRIP_S, WALK, WAVES, CG, HALF, true>), dim3(t.blocks_x*t.blocks_y, 1, frames), dim3(512), 0, s, a, t);
+            else {
+                g_last_kernel += " in-kernel choices";
+                hipLaunchKernelGGL((k_visualizer_strip<PITCH, ROWS, STRIP_S, WALK, WAVES, CG, HALF>), dim3(t.blocks_x*t.blocks_y, 1, frames), dim3(512), 0, s, a, t);
+            }
+        } else hipLaunchKernelGGL((k_visualizer_strip<PITCH, ROWS, STRIP_S, WALK, WAVES, CG, HALF>), dim3(t.blocks_x*t.blocks_y, 1, frames), dim3(512), 0, s, a, t);
     } else {
         g_last_kernel = "k_visualizer_fast<" + std::to_string(PITCH) + ", " + std::to_string(ROWS) + ", 128, " + std::to_string(WAVES) + ">";
         hipLaunchKernelGGL((k_visualizer_fast<PITCH, ROWS, 128, WAVES>), dim3(t.blocks_x*t.blocks_y, 1, frames), dim3(512), 0, s, a, t);

@@ -39,7 +39,7 @@ struct VisTables {
     float4* rows;                        // [frame][hr][VIS_ENTRY_QUADS]
     int4* block_x;                       // [frame][blocks_x] = { x0, tw, fits, 0 }: window of background cells of a block column
     int4* block_y;                       // [frame][blocks_y] = { y0, th, fits, 0 }
-    float4* ysteps;                      // [frame][hr][10] = { y*(y+), y*(y-), row bytes(y+), row bytes(y-) } of the diagonal taps' walk steps (frac = r - y*; float16 cells: the fractions themselves); may be null
+    float4* ysteps;                      // [frame][hr][10] = { y*(y+), y*(y-), row bytes(y+), row bytes(y-) } of the diagonal taps' walk steps (frac = r - y*; float16 cells: the fractions themselves; with a strip plan bit 0 of row bytes(y+) is the walk's crossing flag); may be null
     int blocks_x, blocks_y;              // blocks per row / column of the sample grid
     int block_columns, block_rows;       // samples per block along x / y
     int tile_pitch, tile_rows;           // LDS tile the offsets are computed for (cells)
@@ -51,7 +51,22 @@ struct VisTables {
     float pixel_reach_uv;                // how far a supersample can lie from its pixel's centre, in iCamera.gluv units (with a margin: 0.3 of the pixel's diagonal)
     float pixel_reach_agluv;             // ... in agluv units
     const uint8_t* wave_classes;         // [frame][blocks_y*blocks_x][8 waves]: 1 = the wave's tile takes the pixel tier (k_visualizer_classify)
+    // the STRIP PLAN (round 9, k_visualizer_strip_plan): what every wave of a row strip decides from the strip's row entries alone, once per strip
+    const int4* strip_plan;              // [frame][blocks_y*ROW_GROUPS] = { byte offset of the column line's first cell row, its cell count, rows that exist, new-cell-row mask }; null: no plan
+    const float2* strip_colw;            // [frame][blocks_y*ROW_GROUPS][WALK][COLW_SLOTS] = the strip's aligned column-line weights (VisualizerStrip::Shared::colw)
 };
+
+// Build-time knobs of the plan's three parts (tools/variants.sh measures each alone): the row lines' new-cell-row mask, the column lines'
+// extent and weight image, the diagonal walk's crossing flag
+#ifndef VIS_STRIP_PLAN_ROWS
+#define VIS_STRIP_PLAN_ROWS 1
+#endif
+#ifndef VIS_STRIP_PLAN_COLW
+#define VIS_STRIP_PLAN_COLW 1
+#endif
+#ifndef VIS_STRIP_PLAN_DIAG
+#define VIS_STRIP_PLAN_DIAG 1
+#endif
 
 // { amplitude, spread }: the bar of a spectrogram texel and how far the bars a NEIGHBOURING position could pick differ from it — the bins
 // on either side (wrapped as the sampler wraps them) and, for the first and the last bin, the other channel (visualizer.frag:52 switches
@@ -174,12 +189,25 @@ __device__ __forceinline__ void visualizer_axis_entry(const RenderArgs& a, const
             const float dstep = (a.tap_x[11] - a.tap_x[10])*ax, dfirst = a.tap_x[10]*ax;
             const float row_bytes = (float)(t.tile_pitch*t.cell_bytes);
             float4* ys = t.ysteps + ((long)frame*n + k)*10;
+            const bool shared_sides = t.cell_bytes != 8;                // VisualizerStrip::SHARED_SIDES: y* for the float32-cell instances, the fractions themselves for the float16 ones
+            // The CROSSING FLAG of a launch with a strip plan (float32 cells): bit 0 of row bytes(y+) says that a side of this walk step lies in
+            // another row of cells than the same side of row k - 1 — the question the strip kernel asks at every (row, step). Row k - 1 in the
+            // window of row k's OWN block: the operations of that row's entry when both lie in one block, hence in one strip; a strip's first
+            // row folds without asking. The offsets are multiples of the tile's row bytes, an even number (VisualizerStrip): the bit is free
+            const bool crossing_flags = VIS_STRIP_PLAN_DIAG && shared_sides && t.strip_plan;
+            const float r_before = crossing_flags ? centre_tap(k - 1, dummy0, dummy1, dummy2, dummy3) - (float)origin : r;
             for (int w = 0; w < 10; w++) {
                 const float d = fmaf((float)w, dstep, dfirst);
                 const float yp = r + d, ym = r - d;
                 const float ayp = __builtin_amdgcn_fractf(yp), aym = __builtin_amdgcn_fractf(ym);
-                const bool shared_sides = t.cell_bytes != 8;            // VisualizerStrip::SHARED_SIDES: y* for the float32-cell instances, the fractions themselves for the float16 ones
-                ys[w] = make_float4(shared_sides ? (yp - ayp) - d : ayp, shared_sides ? (ym - aym) + d : aym, __int_as_float((int)((yp - ayp)*row_bytes)), __int_as_float((int)((ym - aym)*row_bytes)));
+                int bytes_p = (int)((yp - ayp)*row_bytes);
+                const int bytes_m = (int)((ym - aym)*row_bytes);
+                if (crossing_flags) {
+                    const float bp = r_before + d, bm = r_before - d;
+                    const int before_p = (int)((bp - __builtin_amdgcn_fractf(bp))*row_bytes), before_m = (int)((bm - __builtin_amdgcn_fractf(bm))*row_bytes);
+                    bytes_p |= (before_p != bytes_p || before_m != bytes_m) ? 1 : 0;
+                }
+                ys[w] = make_float4(shared_sides ? (yp - ayp) - d : ayp, shared_sides ? (ym - aym) + d : aym, __int_as_float(bytes_p), __int_as_float(bytes_m));
             }
         }
     }
@@ -665,7 +693,7 @@ struct VisualizerFast {
 // (Round 6: the measured dead ends that used to sit here as VIS_STRIP_* build knobs — adjacent-row folds, the fractions through LDS or
 // vector memory, the two sides' U summed once, blue packed into a split accumulator, the rows' scalar loads issued together, a store
 // per row instead of the sweep — are gone from the source; what each cost is profiles/r05_variants.txt and HISTORY.)
-template <int TILE_PITCH, int TILE_ROWS, int S, int WALK, int COLUMN_GROUPS = 8/S, bool HALF_CELLS = (S == 1)>
+template <int TILE_PITCH, int TILE_ROWS, int S, int WALK, int COLUMN_GROUPS = 8/S, bool HALF_CELLS = (S == 1), bool PLAN = false>
 struct VisualizerStrip {
     // S x S supersamples per pixel (2 or 4), or S == 1: no resolve, the RGBA8 samples go to iScreen (the two-pass configuration).
     // A block is 512 threads = 8 waves = COLUMN_GROUPS groups of 64 sample columns x ROW_GROUPS groups of WALK consecutive rows.
@@ -694,6 +722,14 @@ struct VisualizerStrip {
     // accumulation per side and the fractions in the table — measured: 1080p at 2x 32.52 -> 32.72 ms, without SSAA 16.10 -> 16.87 ms per
     // 300 frames with the shared form (profiles/r08_strip_diagonal_sides.txt)
     static constexpr bool SHARED_SIDES = !HALF;
+    // Round 9, the strip plan (VisTables::strip_plan, k_visualizer_strip_plan): a wave's scalar choices depend on (frame, by, row group) alone
+    // and every one of the blocks_x*COLUMN_GROUPS waves that walk a row strip used to derive them again — the row lines' "another row of
+    // cells?", the column line's extent and aligned weights, the diagonal walk's "did a side move?". The PLAN form of the float32-cell 2x
+    // instances reads them: a 16-byte record by a scalar load, the weights staged with the row entries, a flag bit in the walk-step table.
+    // A kernel of its own beside the in-kernel form (SHADERFLOW_VIS_STRIP_PLAN=0): both inside one listing would not fit the instruction cache
+    static_assert(!PLAN || (S == 2 && !HALF), "the plan is built for the float32-cell 2x instances");
+    static constexpr bool PLAN_ROWS = PLAN && VIS_STRIP_PLAN_ROWS, PLAN_DIAG = PLAN && VIS_STRIP_PLAN_DIAG;
+    static_assert(!PLAN_DIAG || (ROWBYTES % 2 == 0), "bit 0 of a row offset carries the walk's crossing flag");
     __device__ __forceinline__ static void load_cell(const char* p, Quad& q0, Quad& q1, Quad& q2) {
         q0 = *(const Quad*)p; q1 = *(const Quad*)(p + PLANE); q2 = *(const Quad*)(p + 2*PLANE);
     }
@@ -708,11 +744,16 @@ struct VisualizerStrip {
     // in ONE vector register plus an immediate offset — no VALU instruction at all: per WAVE, aligned to the strip's first cell and zero
     // padded: ds_read_b64 at v_k + r*COLW_SLOTS*8
     static constexpr int COLW_SLOTS = VIS_LINE_CELLS + 6;              // cells a strip's column can span: the 8 slots of a line + the rows of cells its samples cross
+    // the plan's weight image serves the column lines of tiles the aligned table always holds (taller tiles keep the in-kernel derivation
+    // and its fallback loop); it is per ROW GROUP — the waves of a group's column groups read the same weights — and staged with the row entries
+    static constexpr bool PLAN_COLW = PLAN && VIS_STRIP_PLAN_COLW && TILE_ROWS <= COLW_SLOTS;
+    // (-DVIS_STRIP_PLAN_COLW=2, the other copy route, for measurements: every wave copies its strip's image into a slice of its own)
+    static constexpr bool PLAN_COLW_WAVE = PLAN_COLW && VIS_STRIP_PLAN_COLW == 2;
     struct Shared {
         float4 cells[(CELLS_BYTES > EXCHANGE_BYTES ? CELLS_BYTES : EXCHANGE_BYTES)/16 + 1];     // (float16 cells without SSAA) later: uint32 texels[RROWS][COLS], then the RGB8 rows at STAGED
         float4 row_entries[RROWS][VIS_ENTRY_QUADS];
         float4 zeros;                                                  // weights of a slot that does not exist
-        float2 colw[8][WALK][COLW_SLOTS];                              // per wave: weights[r][k - first]
+        float2 colw[PLAN_COLW && !PLAN_COLW_WAVE ? ROW_GROUPS : 8][WALK][COLW_SLOTS];     // per wave (the plan's: per row group): weights[r][k - first]
     };
     static constexpr int STAGED = (int)sizeof(uint32_t)*RROWS*COLS;    // byte offset of the staged RGB8 rows inside the (dead) cell tile, after the texels
     static_assert(S == 1 || STAGED + PIXEL_ROWS*BLOCK_PX*3 == EXCHANGE_BYTES, "the texel exchange and the staged rows live in the cell tile");
@@ -794,7 +835,15 @@ struct VisualizerStrip {
         const int row0 = group*WALK;                                  // first row of the wave inside the block
         const int jr0 = by*RROWS + row0;                              // and inside the frame
         // sample rows of this wave that exist (the frame's height need not be a multiple of the block's)
-        const int rows = (a.hr - jr0 < WALK) ? (a.hr - jr0 < 0 ? 0 : a.hr - jr0) : WALK;
+        // the strip's record of the plan: { first cell row of the column line (bytes), its cells, rows, new-cell-row mask } — one scalar load
+        // (constant address space: written by an earlier kernel, like the tape's constants below)
+        [[maybe_unused]] int4 plan = make_int4(0, 0, 0, 0);
+        if constexpr (PLAN) {
+            typedef const int __attribute__((address_space(4))) * constant_ints;
+            const constant_ints record = (constant_ints)(uintptr_t)(t.strip_plan + ((long)frame*t.blocks_y + by)*ROW_GROUPS + group);
+            plan = make_int4(record[0], record[1], record[2], record[3]);
+        }
+        const int rows = PLAN ? plan.z : (a.hr - jr0 < WALK) ? (a.hr - jr0 < 0 ? 0 : a.hr - jr0) : WALK;
 
         const int4 wx = t.block_x[(long)frame*t.blocks_x + bx], wy = t.block_y[(long)frame*t.blocks_y + by];
         const bool fits = wx.z && wy.z;
@@ -818,6 +867,11 @@ struct VisualizerStrip {
             const int jr = by*RROWS + row;
             sh.row_entries[row][quad] = t.rows[((long)frame*a.hr + (jr < a.hr ? jr : a.hr - 1))*VIS_ENTRY_QUADS + quad];
         }
+        if constexpr (PLAN_COLW && !PLAN_COLW_WAVE) {
+            // the weight images of the block's row groups, contiguous in the plan
+            constexpr int IMAGE = ROW_GROUPS*WALK*COLW_SLOTS;
+            for (int e = tid; e < IMAGE; e += THREADS) (&sh.colw[0][0][0])[e] = t.strip_colw[((long)frame*t.blocks_y + by)*IMAGE + e];
+        }
         if (tid == 0) sh.zeros = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         __syncthreads();
         SF_TICK(a, 0);                                                // prologue: tables, staging the cell tile, the first barrier
@@ -840,11 +894,26 @@ struct VisualizerStrip {
                 const float n[8] = {c3.x, c3.z, c4.x, c4.z, c5.x, c5.z, c6.x, c6.z}, s[8] = {c3.y, c3.w, c4.y, c4.w, c5.y, c5.w, c6.y, c6.w};
                 float P[3] = {0.0f, 0.0f, 0.0f}, Q[3] = {0.0f, 0.0f, 0.0f};
                 int previous = -2*ROWBYTES;                           // (no row of cells: neither equal nor adjacent to a real one)
+                // the plan: the first row's cell row by a scalar load of its entry (where the diagonal walk takes the rows' coordinates from),
+                // one row of cells further wherever the record's mask has the row's bit — no lane read, no compare
+                [[maybe_unused]] int planned_row = 0;
+                if constexpr (PLAN_ROWS) planned_row = __float_as_int(((const float*)(t.rows + ((long)frame*a.hr + (jr0 < a.hr ? jr0 : a.hr - 1))*VIS_ENTRY_QUADS))[2]);
 #pragma unroll
                 for (int r = 0; r < WALK; r++) if (r < rows) {
                     const float4 r0 = sh.row_entries[row0 + r][0];
-                    const int cell_row = __builtin_amdgcn_readfirstlane(__float_as_int(r0.z));       // the wave's lanes share their rows
-                    if (cell_row != previous) {
+                    int cell_row;
+                    bool another;
+                    if constexpr (PLAN_ROWS) {
+                        // (bit 0 is always set, and asked like the others: a first row that folds unconditionally joins the code before it
+                        // into one scheduling region, whose live values no longer fit the 80 registers)
+                        another = (plan.w & (1 << r)) != 0;
+                        cell_row = planned_row;
+                    } else {
+                        cell_row = __builtin_amdgcn_readfirstlane(__float_as_int(r0.z));             // the wave's lanes share their rows
+                        another = cell_row != previous;
+                    }
+                    if (another) {
+                        if constexpr (PLAN_ROWS) { if (r > 0) cell_row = planned_row = planned_row + ROWBYTES; }
                         previous = cell_row;
                         const char* line = tile + (__float_as_int(c0.w) + cell_row);
                         P[0] = P[1] = P[2] = Q[0] = Q[1] = Q[2] = 0.0f;
@@ -863,7 +932,38 @@ struct VisualizerStrip {
             }
             SF_TICK(a, 1);                                            // row-lines
             // ---- the column-lines: the strip's column of cells fetched and folded with fx once, every sample takes the cells its slots cover ----
-            {
+            // cells [first, last) of the strip's column against the aligned weights at `weights`: weights[r][k - first] = (n, s) of row r for cell k
+            auto aligned_column = [&](const float2* weights, const char* cell_k, int first, int last) {
+                int vzero;
+                asm("v_mov_b32 %0, 0" : "=v"(vzero));                   // the table's address lives in a VECTOR register: ds_read_b64 v, v_k offset:r*COLW_SLOTS*8
+                // (NOT `asm volatile`: a side-effecting asm counts as a possible store, after which the compiler no longer proves the
+                // per-frame tables unclobbered and fetches them with vector instead of scalar loads — 78 -> 100 registers)
+                const char* weights_k = (const char*)weights + vzero;
+                float U0 = 0.0f, U1 = 0.0f, U2 = 0.0f, V0 = 0.0f, V1 = 0.0f, V2 = 0.0f;
+                for (int k = first; k < last; k++) {
+                    Quad q0, q1, q2;
+                    load_cell(cell_k, q0, q1, q2);
+                    U0 = fmaf(fx, F(q0.w), F(q0.x)); U1 = fmaf(fx, F(q1.x), F(q0.y)); U2 = fmaf(fx, F(q1.y), F(q0.z));
+                    V0 = fmaf(fx, F(q2.y), F(q1.z)); V1 = fmaf(fx, F(q2.z), F(q1.w)); V2 = fmaf(fx, F(q2.w), F(q2.x));
+#pragma unroll
+                    for (int r = 0; r < WALK; r++) {
+                        const float2 w = *(const float2*)(weights_k + r*COLW_SLOTS*8);
+                        acc[r][0] = fmaf(w.x, U0, acc[r][0]); acc[r][1] = fmaf(w.x, U1, acc[r][1]); acc[r][2] = fmaf(w.x, U2, acc[r][2]);
+                        acc[r][0] = fmaf(w.y, V0, acc[r][0]); acc[r][1] = fmaf(w.y, V1, acc[r][1]); acc[r][2] = fmaf(w.y, V2, acc[r][2]);
+                    }
+                    weights_k += 8; cell_k += ROWBYTES;
+                }
+            };
+            if constexpr (PLAN_COLW) {
+                // the plan: the line's first row of cells and its cell count from the record, the weights staged with the row entries
+                const float2* weights = &sh.colw[PLAN_COLW_WAVE ? wave : group][0][0];
+                if constexpr (PLAN_COLW_WAVE) {
+                    const float2* image = t.strip_colw + (((long)frame*t.blocks_y + by)*ROW_GROUPS + group)*(WALK*COLW_SLOTS);
+#pragma unroll
+                    for (int e = lane; e < WALK*COLW_SLOTS; e += 64) (&sh.colw[wave][0][0])[e] = image[e];
+                }
+                aligned_column(weights, tile + __float_as_int(c0.z) + plan.x, 0, plan.y);
+            } else {
                 int start[WALK];
                 int last = 0;
 #pragma unroll
@@ -887,26 +987,7 @@ struct VisualizerStrip {
                         const bool covered = r < rows && slot >= 0 && slot < VIS_LINE_CELLS;
                         mine[e] = covered ? *(const float2*)((const char*)sh.row_entries[row0 + r] + 48 + slot*8) : make_float2(0.0f, 0.0f);
                     }
-                    int vzero;
-                    asm("v_mov_b32 %0, 0" : "=v"(vzero));                   // the table's address lives in a VECTOR register: ds_read_b64 v, v_k offset:r*COLW_SLOTS*8
-                    // (NOT `asm volatile`: a side-effecting asm counts as a possible store, after which the compiler no longer proves the
-                    // per-frame tables unclobbered and fetches them with vector instead of scalar loads — 78 -> 100 registers)
-                    const char* weights_k = (const char*)mine + vzero;
-                    const char* cell_k = column_cells + first*ROWBYTES;
-                    float U0 = 0.0f, U1 = 0.0f, U2 = 0.0f, V0 = 0.0f, V1 = 0.0f, V2 = 0.0f;
-                    for (int k = first; k < last; k++) {
-                        Quad q0, q1, q2;
-                        load_cell(cell_k, q0, q1, q2);
-                        U0 = fmaf(fx, F(q0.w), F(q0.x)); U1 = fmaf(fx, F(q1.x), F(q0.y)); U2 = fmaf(fx, F(q1.y), F(q0.z));
-                        V0 = fmaf(fx, F(q2.y), F(q1.z)); V1 = fmaf(fx, F(q2.z), F(q1.w)); V2 = fmaf(fx, F(q2.w), F(q2.x));
-#pragma unroll
-                        for (int r = 0; r < WALK; r++) {
-                            const float2 w = *(const float2*)(weights_k + r*COLW_SLOTS*8);
-                            acc[r][0] = fmaf(w.x, U0, acc[r][0]); acc[r][1] = fmaf(w.x, U1, acc[r][1]); acc[r][2] = fmaf(w.x, U2, acc[r][2]);
-                            acc[r][0] = fmaf(w.y, V0, acc[r][0]); acc[r][1] = fmaf(w.y, V1, acc[r][1]); acc[r][2] = fmaf(w.y, V2, acc[r][2]);
-                        }
-                        weights_k += 8; cell_k += ROWBYTES;
-                    }
+                    aligned_column(mine, column_cells + first*ROWBYTES, first, last);
                 } else
                 for (int k = first; k < last; k++) {
                     // a run of cells longer than the aligned table (tiles taller than COLW_SLOTS rows only): the weights of all rows of a cell
@@ -1048,7 +1129,7 @@ struct VisualizerStrip {
                     };
                     // both sides folded in full (their cells are fetched at once): a walk step's first row, and a side that jumped
                     auto fold_both = [&](int r) {
-                        previous[0] = __float_as_int(y[r].z); previous[1] = __float_as_int(y[r].w);
+                        previous[0] = __float_as_int(y[r].z) & (PLAN_DIAG ? ~1 : ~0); previous[1] = __float_as_int(y[r].w);     // (without the plan's crossing flag)
                         float up[3], um[3];
                         fold(previous[0], up, Vs[0]);
                         fold(previous[1], um, Vs[1]);
@@ -1079,11 +1160,17 @@ struct VisualizerStrip {
                             // here on telling a jump from a crossing first made the walk SLOWER than the two accumulations it replaces)
                             // ONE branch (two xor, one or) for a row that stays where it is; what moved is sorted out behind it. Offsets are
                             // multiples of ROWBYTES: a difference that is neither 0 nor ROWBYTES is above it as an unsigned number
-                            const int cp = __float_as_int(y[r].z), cm = __float_as_int(y[r].w);
-                            // (in asm: written in C++ the compiler turns the test back into two compares, four selects and two ands)
-                            int moved_p, moved;
-                            asm("s_xor_b32 %0, %1, %2" : "=s"(moved_p) : "s"(cp), "s"(previous[0]) : "scc");
-                            asm("s_xor_b32 %0, %1, %2\n\ts_or_b32 %0, %0, %3" : "=&s"(moved) : "s"(cm), "s"(previous[1]), "s"(moved_p) : "scc");
+                            // The plan: k_visualizer_axes asked the question once per (row, step) of the frame — bit 0 of row bytes(y+) — and a
+                            // row that stays costs one bit test and the branch; `previous` is compared behind it only
+                            const int cp = __float_as_int(y[r].z) & (PLAN_DIAG ? ~1 : ~0), cm = __float_as_int(y[r].w);
+                            int moved;
+                            if constexpr (PLAN_DIAG) moved = __float_as_int(y[r].z) & 1;
+                            else {
+                                // (in asm: written in C++ the compiler turns the test back into two compares, four selects and two ands)
+                                int moved_p;
+                                asm("s_xor_b32 %0, %1, %2" : "=s"(moved_p) : "s"(cp), "s"(previous[0]) : "scc");
+                                asm("s_xor_b32 %0, %1, %2\n\ts_or_b32 %0, %0, %3" : "=&s"(moved) : "s"(cm), "s"(previous[1]), "s"(moved_p) : "scc");
+                            }
                             if (moved != 0) {
                                 const unsigned dp = (unsigned)(cp - previous[0]), dm = (unsigned)(cm - previous[1]);
                                 if ((dp > dm ? dp : dm) > (unsigned)ROWBYTES) fold_both(r);
@@ -1201,9 +1288,49 @@ struct VisualizerStrip {
     }
 };
 
-template <int TILE_PITCH, int TILE_ROWS, int S, int WALK, int MIN_WAVES, int COLUMN_GROUPS = 8/S, bool HALF_CELLS = (S == 1)>
+template <int TILE_PITCH, int TILE_ROWS, int S, int WALK, int MIN_WAVES, int COLUMN_GROUPS = 8/S, bool HALF_CELLS = (S == 1), bool PLAN = false>
 __global__ __launch_bounds__(512, MIN_WAVES) void k_visualizer_strip(const RenderArgs a, const VisTables t) {
-    VisualizerStrip<TILE_PITCH, TILE_ROWS, S, WALK, COLUMN_GROUPS, HALF_CELLS>::run(a, t);
+    VisualizerStrip<TILE_PITCH, TILE_ROWS, S, WALK, COLUMN_GROUPS, HALF_CELLS, PLAN>::run(a, t);
+}
+
+// The strip plan (round 9): one wave per (frame, row strip) — the WALK sample rows of row group `group` of block row `by`, strip = by*ROW_GROUPS +
+// group, rows strip*WALK … — derives from the strip's row entries what each of the blocks_x*COLUMN_GROUPS waves that walk the strip used to
+// derive for itself: the record and the aligned weight image of VisualizerStrip::run's column lines, with that function's own integer
+// operations on the same entries. Launched after k_visualizer_axes on the same stream.
+template <int WALK, int ROW_GROUPS, int ROWBYTES, int COLW_SLOTS>
+__global__ __launch_bounds__(256) void k_visualizer_strip_plan(const RenderArgs a, const VisTables t, int4* __restrict__ plan, float2* __restrict__ colw) {
+    const int strips = t.blocks_y*ROW_GROUPS;
+    const int strip = blockIdx.x*4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, frame = blockIdx.y;
+    if (strip >= strips) return;
+    const int jr0 = strip*WALK;
+    const int rows = (a.hr - jr0 < WALK) ? (a.hr - jr0 < 0 ? 0 : a.hr - jr0) : WALK;
+    // (the rows behind the frame's last one: its entry, as the strip kernel stages them)
+    auto entry = [&](int r) { const int jr = jr0 + r; return t.rows + ((long)frame*a.hr + (jr < a.hr ? jr : a.hr - 1))*VIS_ENTRY_QUADS; };
+    const int first = __float_as_int(entry(0)[0].w)/ROWBYTES;
+    float2* image = colw ? colw + ((long)frame*strips + strip)*(WALK*COLW_SLOTS) : nullptr;
+    for (int e = lane; image && e < WALK*COLW_SLOTS; e += 64) {           // (no images: the instance's column lines keep their in-kernel weights)
+        const int r = e / COLW_SLOTS, j = e - r*COLW_SLOTS;
+        const float4* row = entry(r);
+        const int begin = __float_as_int(row[0].w)/ROWBYTES;
+        const int slot = j + first - begin;
+        const bool covered = r < rows && slot >= 0 && slot < VIS_LINE_CELLS;
+        image[e] = covered ? *(const float2*)((const char*)row + 48 + slot*8) : make_float2(0.0f, 0.0f);
+    }
+    if (lane == 0) {
+        int last = 0, mask = 1, before = 0;
+        for (int r = 0; r < WALK; r++) {
+            const float4 q0 = entry(r)[0];
+            const int cell_row = __float_as_int(q0.z);
+            if (r < rows) last = __float_as_int(q0.w)/ROWBYTES + VIS_LINE_CELLS;       // (the lines' first cells do not decrease with the row)
+            if (r > 0 && cell_row != before) mask |= 1 << r;
+            before = cell_row;
+        }
+        plan[(long)frame*strips + strip] = make_int4(first*ROWBYTES, last > first ? last - first : 0, rows, mask);
+        // (the strip kernel ADVANCES the row lines' cell row by one row of cells where the mask says so. That is every change a block that fits
+        // its tile can see: its BLOCK_ROWS rows span fewer rows of cells than the tile has, and a tile has fewer than BLOCK_ROWS, so two
+        // neighbouring rows lie less than a texel apart; and the row coordinate does not fall with the row — what the column lines' `last`
+        // has always rested on. Blocks that do not fit take blur_direct and read no plan)
+    }
 }
 
 template <int TILE_PITCH, int TILE_ROWS, int BLOCK_PX, int MIN_WAVES>

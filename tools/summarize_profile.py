@@ -2,6 +2,7 @@
 """Summarises a tools/profile_bench.sh output directory: per-kernel time (kernel-trace stats) and PMC counters
 (mean per dispatch) of the dominant kernels. Plain text, meant to be committed under profiles/."""
 import csv
+import re
 import sys
 from collections import defaultdict
 from pathlib import Path
@@ -10,8 +11,16 @@ root = Path(sys.argv[1])
 
 
 def short(name: str) -> str:
-    name = name.replace("sf::", "").replace("void ", "")
-    return name.split("(")[0][:70]
+    name = name.replace("sf::", "").replace("void ", "").split("(")[0]
+    # the strip kernel's eighth template argument is its plan switch: the library (sfx_last_kernel, which bench.py looks a kernel up by)
+    # names the planned form by the seven arguments of the instance and the other form with a suffix
+    # (only the float32-cell 2x instances have both forms)
+    plan = re.fullmatch(r"(k_visualizer_strip<(?:[^,<>]+, ){6}[^,<>]+), (true|false)>", name)
+    if plan:
+        arguments = plan.group(1).split("<")[1].split(", ")
+        both = arguments[2] == "2" and arguments[6] == "false"
+        name = plan.group(1) + ("> in-kernel choices" if both and plan.group(2) == "false" else ">")
+    return name[:70]
 
 
 print(f"# profile summary of {root}")
